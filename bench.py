@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: denoiser-forward throughput of ZigMa on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,13 @@ metric  (BASELINE.json): denoiser-forward latents/sec = B*L tokens per second of
         ZigMa E=640, depth=18, L=32x32, zigzagN8 — workload = BASELINE configs[1]: the README model
         (in_ch=3, img 32, has_text with 77x768 context) in bf16 at B=64 per GPU, synthetic x / t / y.
 step    = one ZigMa.forward over the per-rank batch (inputs resident in HBM before the timed region).
+          W warm-up steps and one more untimed forward precede exactly K timed steps; ms_per_step = timed seconds / K.
+plain run : only what the headline needs — set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.
+--full    : also everything below (scan roofline with HIP events inside the timed steps, the two output checks, box_calib,
+            cpu_baseline); --no-check / --no-cpu-baseline / --no-scan-events leave parts of it out.
+--dump-outputs DIR : after the timed steps, the velocities of the last timed step (what a caller of ZigMa.forward receives; with
+            N > 1 the gathered velocities of all ranks) as DIR/velocity.npy, float32 — at most 64 MB (beyond that a fixed, seeded
+            sample of whole samples).  Weights and inputs are seeded: the same arguments give the same inputs in every run.
 N > 1   = batch-sharded replicas (weak scaling: B=64 per rank); the path has no collective inside the
           forward — ranks only meet at the timing barriers and at the final all_gather of the velocities
           (the analogue of accelerator.gather in sample_acc.py:435), which is inside the timed region.
@@ -29,7 +36,7 @@ cpu_baseline : on the host cores, bounded sample (forwards of the same model at 
             outputs), `kind: "port-torch"`, `threads` = torch threads used.  (The numpy oracle, `kind: "port"`, is the last resort.)
 check       : one forward OUTSIDE the timed region compared with the same model run through the unfused composition
             (library projections, no epilogue fusion, the two-kernel conv / x_proj): finite + norm-wise distance.
-N > 1 without a launcher: `python bench.py --gpus N` re-executes itself under torch.distributed.run with N ranks.
+N > 1 without a launcher: `python bench.py --gpus N` runs itself as a child job under torch.distributed.run with N ranks.
 """
 import argparse
 import json
@@ -426,10 +433,29 @@ def cpu_baseline(wl, name, limit_s=240):
     return None
 
 
+DUMP_LIMIT = 64 << 20       # bytes, all --dump-outputs files together
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """`arrays`: name -> tensor with the sample index first.  Each is written as directory/<name>.npy in float32; a tensor over its share
+    of DUMP_LIMIT is written as a fixed, seeded sample of whole samples (sorted indices), so that two runs with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            k = max(1, share // max(a[0].nbytes, 1))
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def respawn_under_launcher(n):
-    """`python bench.py --gpus N` with no launcher around it: become `python -m torch.distributed.run ... bench.py ...`
-    (one rank per GPU, rendezvous on 127.0.0.1) — the analogue of `accelerate launch` in the reference (README.md:165)."""
+    """`python bench.py --gpus N` with no launcher around it: run `python -m torch.distributed.run ... bench.py ...` as a child job
+    (one rank per GPU, rendezvous on 127.0.0.1) and exit with its status — the analogue of `accelerate launch` in the reference
+    (README.md:165).  A child, not an exec: this process has already opened the GPU."""
     import socket
+    import subprocess
     have = torch.cuda.device_count()
     if have < n:
         raise SystemExit(f"bench.py: --gpus {n} but only {have} GPU(s) are visible; refusing to report a smaller job")
@@ -438,9 +464,10 @@ def respawn_under_launcher(n):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -455,8 +482,14 @@ def main():
     ap.add_argument("--scan-events-every", type=int, default=7, help="bracket every n-th scan launch of the timed region with HIP events (1: all)")
     ap.add_argument("--no-check", action="store_true",
                     help="skip the untimed self-check forward (kernel traces of the timed path: its unfused composition runs library GEMMs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: scan roofline (HIP events in the timed steps), output checks, box_calib, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's velocities as DIR/velocity.npy (float32, at most 64 MB)")
     ap.add_argument("--cpu-baseline-only", default=None, help=argparse.SUPPRESS)      # child-process leg of cpu_baseline()
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:
         fn = {"reference": cpu_baseline_reference, "port-torch": cpu_baseline_port_torch}.get(args.cpu_baseline_only, cpu_baseline_port)
         print(json.dumps(fn(WORKLOADS[args.workload])), flush=True)
@@ -485,22 +518,27 @@ def main():
     gathered = torch.empty((world * batch,) + wl["x"], device=device) if world > 1 else None
 
     timer = ScanTimer(every=args.scan_events_every)
-    timer.install()
+    if args.full:
+        timer.install()
+    last = {}
 
     def step():
         with torch.no_grad():
             v = model(x, t, y)
         if world > 1:
             ss.gather_samples(v, world, out=gathered)
+        last["v"] = v
         return v
 
     for _ in range(args.warmup):          # scan-event timing only inside the timed region
         step()
-    v_check = step()                      # (every rank: the step holds the gather)
-    check = check_against_unfused(model, x, t, y, v_check) if (rank == 0 and not args.no_check) else None       # outside the timed region
-    timer.enabled = not args.no_scan_events
+    v_check = step()                      # (every rank: the step holds the gather; the timed region starts warm even at --warmup 0)
+    check = check_against_unfused(model, x, t, y, v_check) if (args.full and rank == 0 and not args.no_check) else None       # outside the timed region
+    timer.enabled = args.full and not args.no_scan_events
     elapsed = ss.timed_steps(step, args.steps, 0, device, world)
     timer.enabled = False
+    if args.dump_outputs and rank == 0:   # what the caller of the timed path receives from its last step
+        dump_outputs(args.dump_outputs, dict(velocity=gathered if world > 1 else last["v"]))
 
     if rank == 0:
         Di, N = 2 * wl["model"]["embed_dim"], 16
@@ -545,13 +583,15 @@ def main():
                     config=dict(workload=f"{args.workload}: ZigMa(in_ch=3,img=32,E=640,depth=18,zigzagN8,has_text 77x768), "
                                          f"B={batch}/GPU, bf16, one forward per step",
                                 global_batch=world * batch, seq_len=L, parallelism=f"batch-sharded x{world}"),
-                    roofline=roof, check=check)
-        if not args.no_check:
+                    full=args.full)
+        if args.full:
+            line.update(roofline=roof, check=check)
+        if args.full and not args.no_check:
             line["box_calib"] = box_calib(device)
             ref = check_against_reference(model, wl, x, t, y)        # (overwrites the model's weights: last use of the model)
             if ref is not None:
                 line["check"] = dict(check or {}, **ref)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl, args.workload)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -506,38 +506,57 @@ def test_drop_path_is_applied_once_per_block_in_train_mode(monkeypatch):
     assert rel_err(outs[0].numpy(), g["out"]) > 1e-2       # the mock really changes the result in train mode
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
 def test_extension_shims_under_the_reference_python(monkeypatch):
     """the reference's OWN `mamba_inner_fn` (MambaInnerFn.forward) runs on the shim modules.
-    Kernels are replaced by the oracle stand-ins here (CPU); what is checked is the call surface — argument
-    order, views/strides the reference passes, allocation conventions, return arity."""
+    Its two extension calls are replayed from tests/golden/shim_calls_mamba_inner.npz (recorded from the reference's Python by
+    oracle/make_golden_shim_calls.py): entry-point names, argument order, the views / strides / aliasing the reference passes
+    (x and z are the two halves of one xz buffer, delta is a transposed view), the result arity it unpacks.  Kernels are replaced
+    by the oracle stand-ins here (CPU); each result is compared with the reference's own pure-torch function on the same operands,
+    the inputs must come back untouched (callee allocates), and out_proj of the gated scan output must give mamba_inner_fn's output."""
     import importlib
     import sys
-    import types
     import kernel_standins
+    import torch.nn.functional as F
     kernel_standins.install(monkeypatch)
     from zigma_amd import _lib, extension_shims
     monkeypatch.setattr(_lib, "require_device", lambda *a: torch.device("cpu"))
     for name in ("selective_scan_cuda", "causal_conv1d_cuda"):
         monkeypatch.delitem(sys.modules, name, raising=False)
     ss, cc = extension_shims.install()
-    monkeypatch.syspath_prepend("/root/reference/dis_causal_conv1d")
-    for pkg, path in (("dis_mamba", "/root/reference/dis_mamba"), ("dis_mamba.mamba_ssm", "/root/reference/dis_mamba/mamba_ssm"),
-                      ("dis_mamba.mamba_ssm.ops", "/root/reference/dis_mamba/mamba_ssm/ops")):
-        m = types.ModuleType(pkg)
-        m.__path__ = [path]
-        monkeypatch.setitem(sys.modules, pkg, m)
-    for name in ("causal_conv1d", "causal_conv1d.causal_conv1d_interface", "dis_mamba.mamba_ssm.ops.selective_scan_interface"):
-        monkeypatch.delitem(sys.modules, name, raising=False)
-    ssi = importlib.import_module("dis_mamba.mamba_ssm.ops.selective_scan_interface")
-    assert ssi.selective_scan_cuda is ss and ssi.causal_conv1d_cuda is cc
+    assert importlib.import_module("selective_scan_cuda") is ss and importlib.import_module("causal_conv1d_cuda") is cc
+    rec = load_golden("shim_calls_mamba_inner.npz")
+    assert list(rec["calls"]) == ["causal_conv1d_cuda.causal_conv1d_fwd", "selective_scan_cuda.fwd"]
+    storages = [torch.from_numpy(rec[f"s{k}"].copy()) for k in range(sum(k.startswith("s") and k[1:].isdigit() for k in rec))]
+
+    def replay(i):
+        mod, fn = str(rec["calls"][i]).split(".")
+        args = []
+        for j, kind in enumerate(rec[f"c{i}_kinds"]):
+            if kind == "none":
+                args.append(None)
+            elif kind == "bool":
+                args.append(bool(rec[f"c{i}_a{j}_value"]))
+            else:
+                off, nd, *rest = rec[f"c{i}_a{j}_view"].tolist()
+                args.append(torch.as_strided(storages[int(rec[f"c{i}_a{j}_storage"])], rest[:nd], rest[nd:], off))
+        with torch.no_grad():
+            res = getattr(importlib.import_module(mod), fn)(*args)
+        assert (len(res) if isinstance(res, (list, tuple)) else -1) == int(rec[f"c{i}_nret"]), (mod, fn)
+        return args, res
+
+    (x, w, b, silu), conv_out = replay(0)
+    assert x.stride() == (9216, 96, 1) and silu is True                  # the x half of xz, not copied by the caller
+    assert conv_out.shape == x.shape and rel_err(conv_out.numpy(), rec["c0_expect"]) < 5e-6
+    (u, delta, A, B, C, D, z, db, softplus), (out, last, out_z) = replay(1)
+    assert z.storage_offset() == 4608 and z.untyped_storage().data_ptr() == storages[0].untyped_storage().data_ptr()
+    assert delta.stride() == (96, 192, 1) and B.shape == (2, 1, 16, 96) and softplus is True
+    assert out.shape == delta.shape and out_z.shape == z.shape and last.shape[:2] == u.shape[:2]
+    assert rel_err(out.numpy(), rec["c1_expect_out"]) < 5e-6 and rel_err(out_z.numpy(), rec["c1_expect_out_z"]) < 5e-6
+    for k, s in enumerate(storages):
+        assert np.array_equal(s.numpy(), rec[f"s{k}"]), f"storage {k} written by the callee"
     g = load_golden("mamba_inner.npz")
-    T = lambda k: torch.from_numpy(g[k])
-    with torch.no_grad():
-        out = ssi.mamba_inner_fn(T("xz"), T("conv_w"), T("conv_b"), T("x_proj_w"), T("dt_proj_w"), T("out_proj_w"),
-                                 T("out_proj_b"), T("A"), None, None, T("D"), delta_bias=T("delta_bias"),
-                                 delta_softplus=True)
-    assert rel_err(out.numpy(), g["out"]) < 5e-6
+    y = F.linear(out_z.transpose(1, 2), torch.from_numpy(g["out_proj_w"]), torch.from_numpy(g["out_proj_b"]))
+    assert rel_err(y.numpy(), g["out"]) < 5e-6
 
 
 def test_sequence_split_policy():

@@ -78,3 +78,24 @@ def test_bench_refuses_a_multi_gpu_run_it_cannot_launch():
     with pytest.raises(SystemExit) as e:
         bench.respawn_under_launcher(have + 2)
     assert "refusing" in str(e.value)
+
+
+def test_bench_dump_outputs_float32_bounded_and_fixed(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: float32 files, at most DUMP_LIMIT bytes in all; beyond it the same seeded sample of whole
+    samples in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 * 1024)
+    v = torch.randn(100, 3, 16, 16).to(torch.bfloat16)            # 3 KB per sample, 300 KB in all
+    small = torch.randn(4, 3, 8, 8).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dict(velocity=v))
+    a, b = (np.load(tmp_path / d / "velocity.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.nbytes <= 64 * 1024 and a.shape[1:] == (3, 16, 16) and a.shape[0] == 21
+    assert np.array_equal(a, b)
+    full = v.float().numpy()
+    rows = [int(np.flatnonzero((full == r).all(axis=(1, 2, 3)))[0]) for r in a]
+    assert rows == sorted(set(rows))                                  # whole samples, in batch order, no repeats
+    bench.dump_outputs(str(tmp_path / "c"), dict(velocity=small))
+    assert np.array_equal(np.load(tmp_path / "c" / "velocity.npy"), small.float().numpy())
