@@ -605,10 +605,11 @@ def test_video_temporal_layers_train_without_transposing_copies():
 
 
 @pytest.mark.parametrize("M,K,N,bias", [(65536, 640, 2560, False), (16384, 1280, 640, False), (8192, 512, 640, True), (4096, 640, 512, False)])
-def test_linear_train_fn_on_the_own_kernels(M, K, N, bias, monkeypatch):
+def test_linear_train_fn_own_kernels_vs_library(M, K, N, bias, monkeypatch):
     """wgrad.LinearTrainFn (round 4): forward product and dX on zigma_linear_fwd (weight-stationary / tiled kernels) — asserted from the call
     trace — against float64 on the same bf16 operands and against the library path (F.linear + autograd) within bf16 bounds; dW through
     the slab-wise product as before (reference: autograd's linear backward behind mamba_simple.py:290-294, model_zigma.py:104-135)."""
+    import zigma_amd.routing as zr
     import zigma_amd.wgrad as wg
     from zigma_amd import _lib
     g = torch.Generator(device="cpu").manual_seed(M + K)
@@ -616,7 +617,7 @@ def test_linear_train_fn_on_the_own_kernels(M, K, N, bias, monkeypatch):
     w = (torch.randn(N, K, generator=g) * K ** -0.5).to("cuda", torch.bfloat16).requires_grad_(True)
     b = (torch.randn(N, generator=g) * 0.1).to("cuda", torch.bfloat16).requires_grad_(True) if bias else None
     dy = torch.randn(M, N, generator=g).to("cuda", torch.bfloat16)
-    monkeypatch.setattr(wg, "OWN_TRAIN_GEMMS", True)
+    monkeypatch.setattr(zr, "POLICY", "auto")
     trace = []
     monkeypatch.setattr(_lib, "TRACE", trace)
     y = wg.linear_train(x, w, b)
@@ -628,7 +629,7 @@ def test_linear_train_fn_on_the_own_kernels(M, K, N, bias, monkeypatch):
     x.grad = w.grad = None
     if b is not None:
         b.grad = None
-    monkeypatch.setattr(wg, "OWN_TRAIN_GEMMS", False)
+    monkeypatch.setattr(zr, "POLICY", "off")                     # the library path: F.linear and dY @ W
     y2 = wg.linear_train(x, w, b)
     y2.backward(dy)
     rows = torch.randint(0, M, (512,), generator=g).to("cuda")
@@ -639,6 +640,6 @@ def test_linear_train_fn_on_the_own_kernels(M, K, N, bias, monkeypatch):
     assert rel_err(got[1][rows].double().cpu().numpy(), ref_dx.cpu().numpy()) < 2.5e-3
     assert rel_err(got[0].float().cpu().numpy(), y2.detach().float().cpu().numpy()) < 2e-3
     assert rel_err(got[1].float().cpu().numpy(), x.grad.float().cpu().numpy()) < 2e-3
-    assert torch.equal(got[2], w.grad)                            # (the weight gradient does not depend on the switch)
+    assert torch.equal(got[2], w.grad)                            # (the weight gradient does not depend on the policy)
     if b is not None:
         assert torch.equal(got[3], b.grad)

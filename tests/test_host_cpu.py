@@ -96,6 +96,9 @@ def test_knobs_env_override():
     bad = subprocess.run([sys.executable, "-c", "import zigma_amd.mamba_simple"], cwd=ROOT, env=dict(os.environ, ZIGMA_KNOBS="mamba_simple.NO_SUCH=1"),
                          capture_output=True, text=True)
     assert bad.returncode != 0 and "no knob" in bad.stderr
+    bad = subprocess.run([sys.executable, "-c", "import zigma_amd.model_zigma"], cwd=ROOT, env=dict(os.environ, ZIGMA_KNOBS="linear.X=1"),
+                         capture_output=True, text=True)
+    assert bad.returncode != 0 and "names no module with knobs" in bad.stderr
 
 
 def test_no_routing_environment_switches():
@@ -149,6 +152,19 @@ def test_routing_table():
     # the 128-feature-panel form holds at most 32 panels — in_proj of an E = 1280 / 1536 model must not be claimed for it
     assert not zr.serves_ws(16384, 5120, 1280) and not zr.serves_ws(16384, 6144, 1536) and zr.serves_ws(16384, 4096, 1280)
     assert zr.route("in_proj", 16384, 5120, 1280).kernel == "tiled" and zr.route("in_proj", 16384, 6144, 1536).kernel == "tiled"
+    # the training path (forward product and dX of every block projection): weight-stationary where it serves, then tiled, then the library
+    for E in (512, 640, 768, 1024):
+        for tokens in (4096, 8192, 16384, 65536, 4096 + 8, 100):
+            for n, k in ((4 * E, E), (E, 4 * E), (E, 2 * E), (2 * E, E), (512, E), (E, 512)):
+                want = ("ws" if zr.serves_ws(tokens, n, k) and zr.ws_panel_width(k) == 256 else "ws128" if zr.serves_ws(tokens, n, k)
+                        else "tiled" if zr.serves_tiled(tokens, n, k) else "library")
+                assert zr.route("train", tokens, n, k) == zr.Route(want, False, "train." + want), (E, tokens, n, k)
+    assert zr.route("train", 65536, 2560, 640).row == "train.ws" and zr.route("train", 65536, 640, 1280).row == "train.ws128"
+    assert zr.route("train", 65536, 640, 2560).row == "train.tiled" and zr.route("train", 65536, 100, 640).row == "train.library"
+    # the text projections (B x 77 rows padded to 256): tiled wherever it serves
+    assert zr.route("text", 5120, 18 * 2 * 512, 640) == zr.Route("tiled", False, "text.tiled") and zr.route("text", 256, 640, 768).row == "text.tiled"
+    assert zr.route("text", 256, 100, 768).row == "text.library"
+    assert [r.row for r in zr.candidates("in_proj", 65536, 2560, 640)] == ["in_proj.ws", "in_proj.halves", "in_proj.library"]
     # (iv) knobs
     try:
         zr.DISABLED = {"in_proj.ws"}
@@ -157,8 +173,13 @@ def test_routing_table():
         assert zr.route("out_proj", 65536, 640, 1280).row == "out_proj.library"
         zr.DISABLED, zr.POLICY = "", "off"
         assert all(zr.route(role, 65536, n, k).kernel == "library" for role, n, k in (("in_proj", 2560, 640), ("to_out", 640, 512)))
+        assert all(zr.route(role, 65536, 2560, 640) == zr.Route("library", False, "policy.off") for role in ("text", "train"))
         zr.POLICY = "all"
         assert zr.route("in_proj", 65536, 2560, 640) == zr.Route("tiled", False, "policy.all") and zr.route("out_proj", 16384, 640, 1280).fuse_add
+        assert zr.route("train", 65536, 2560, 640).row == "train.ws" and zr.route("text", 5120, 640, 768).row == "text.tiled"      # as under "auto"
+        zr.POLICY, zr.DISABLED = "auto", "train.ws+train.ws128+text.tiled"
+        assert zr.route("train", 65536, 2560, 640).row == "train.tiled" and zr.route("train", 65536, 640, 1280).row == "train.tiled"
+        assert zr.route("text", 5120, 640, 768).row == "text.library"
     finally:
         zr.DISABLED, zr.POLICY = "", "auto"
     with pytest.raises(ValueError):

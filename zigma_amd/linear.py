@@ -1,7 +1,7 @@
 """Dense projections on the hand-written MFMA kernel (zigma_linear_fwd): in_proj / out_proj of the Mamba mixer and
 to_q / to_out of the cross-attention (reference call sites mamba_simple.py:290-294, selective_scan_interface.py:365,
-model_zigma.py:104-135, all `F.linear`).  Under autograd the callers go through wgrad.LinearTrainFn, whose forward product and dX use the same kernels (its own eligibility
-check runs with autograd off); linear_eligible itself refuses tensors that require grad."""
+model_zigma.py:104-135, all `F.linear`), the text projections and the training path's forward product and dX (wgrad.LinearTrainFn, whose plan()
+runs with autograd off); linear_eligible itself refuses tensors that require grad.  Which kernel serves which call: plan() and zigma_amd/routing.py."""
 import torch
 
 from . import _lib
@@ -34,15 +34,12 @@ LINEAR_WS_FLAG = 0x4000          # zigma_linear_params_t.flags: ZIGMA_LINEAR_WS 
 
 
 def linear_ws_eligible(x, weight, bias=None):
-    """limits of the weight-stationary kernel (csrc/linear_ws.hip: a W panel lives in the registers of a workgroup, only the tokens stream): bf16, no
-    bias; k = 512 or 640 with 256-feature panels (n % 256 == 0), or k = 1280 / 1536 with 128-feature panels (n % 128 == 0: the out_proj shapes, used
-    below the tiled 4-wave kernel's floor); n <= 8192, tokens % 512 == 0 and enough of them for every workgroup of an XCD to own a tile, x rows a multiple
-    of 128 elements apart — on top of linear_eligible's alignment rules."""
-    if bias is not None or not linear_eligible(x, weight, None):
-        return False
+    """limits of the weight-stationary kernel (csrc/linear_ws.hip: a W panel lives in the registers of a workgroup, only the tokens stream):
+    linear_eligible's, the shape limits of routing.serves_ws (k = 512 / 640 with 256-feature panels, k = 1280 / 1536 with 128-feature panels, at
+    most 32 panels, whole 512-token tiles for every workgroup of an XCD) and the tensor limits of _TENSOR_LIMITS["ws"] (no bias, x rows a multiple
+    of 128 elements apart)."""
     n, k = weight.shape
-    # (routing.serves_ws mirrors linear_ws_panel of the C side, including its 32-panel limit: n <= 4096 for the 128-feature form — ADVICE r5)
-    return routing.serves_ws(x.numel() // k, n, k) and x.stride(-2) % 128 == 0
+    return linear_eligible(x, weight, bias) and routing.serves_ws(x.numel() // k, n, k) and _TENSOR_LIMITS["ws"](x, bias)
 
 
 LINEAR_SM_FLAG = 0x8000          # zigma_linear_params_t.flags: ZIGMA_LINEAR_SM (csrc/linear_sm.hip)
@@ -50,16 +47,21 @@ LINEAR_SM_FLAG = 0x8000          # zigma_linear_params_t.flags: ZIGMA_LINEAR_SM 
 
 def linear_sm_eligible(x, weight, bias=None):
     """limits of the few-token tiled kernel (csrc/linear_sm.hip: tiles of 128 tokens x n / 4 features, one per workgroup — 8192 tokens x 640
-    features are exactly 256 tiles): bf16, k % 64 == 0 and k >= 128, tokens % 128 == 0 (tiles of 160, 192 or 128 features), an optional bf16
-    bias on an 8-byte boundary — on top of linear_eligible's alignment rules.  The gated residual epilogue: gated_residual_eligible, as for the
-    tiled kernels."""
-    if not linear_eligible(x, weight, bias):
-        return False
-    if bias is not None and bias.data_ptr() % 8:
-        return False
+    features are exactly 256 tiles): linear_eligible's, the shape limits of routing.serves_sm (k >= 128, whole 128-token tiles) and the tensor
+    limits of _TENSOR_LIMITS["sm"] (a bias on an 8-byte boundary).  The gated residual epilogue: gated_residual_eligible, as for the tiled kernels."""
     n, k = weight.shape
-    m = x.numel() // k
-    return k >= 128 and m % 128 == 0 and m >= 128        # (n % 128 == 0 by linear_eligible)
+    return linear_eligible(x, weight, bias) and routing.serves_sm(x.numel() // k, n, k) and _TENSOR_LIMITS["sm"](x, bias)
+
+
+# What each kernel family asks of the tensors on top of linear_eligible and its shape limits (routing._SERVES)
+_TENSOR_LIMITS = {
+    "ws": lambda x, bias: bias is None and x.stride(-2) % 128 == 0,         # (no epilogue operands in this kernel)
+    "sm": lambda x, bias: bias is None or bias.data_ptr() % 8 == 0,
+    "tiled": lambda x, bias: True,
+    "tiled_halves": lambda x, bias: bias is None and x.dim() == 3,          # (each half is a tiled call on half of the weight rows)
+    "library": lambda x, bias: True,
+}
+_TENSOR_LIMITS["ws128"] = _TENSOR_LIMITS["ws"]
 
 
 def linear(x, weight, bias=None, silu_from_col=None, out=None, _probe_flags=0, residual=None, gate=None, weight_stationary=False, few_tokens=False):
@@ -104,41 +106,43 @@ def gated_residual_eligible(x, residual, gate):
             and 256 * residual.stride(1) * 2 < 2 ** 31)
 
 
-def project(role, x, weight, bias=None, residual=None, gate=None):
-    """The block loop's projections through ONE dispatch (zigma_amd/routing.py): role in_proj | out_proj | to_q | to_out.
-    residual (B, L, n) + gate (B, n): the result is residual + gate[:, None] * (x @ weight.T + bias) — in the serving kernel's epilogue where the table says
-    so and the kernel's limits are met, as an addcmul behind the product otherwise.  Calls the own kernels cannot take (fp32 / fp16 models, CPU tensors,
-    autograd) go to wgrad.linear_train (F.linear; under autograd with the slab-wise weight gradient)."""
-    from .wgrad import linear_train
+def plan(role, x, weight, bias=None, residual=None, gate=None):
+    """The ONE decision which kernel serves a projection (routing.ROLES) on these tensors: the first route of the table (routing.candidates) whose
+    kernel's shape and tensor limits the call meets; a route the tensors refuse is logged in routing.REFUSED and the walk goes on.  Calls no own kernel
+    can take (fp32 / fp16 models, CPU tensors, autograd) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
+    epilogue (the route fuses, residual / gate are given and meet the epilogue's limits, no autograd)."""
     n, k = weight.shape
-    tokens = x.numel() // max(k, 1)
-    own = linear_eligible(x, weight, bias)
-    r = routing.route(role, tokens, n, k) if own else routing.Route("library", False, "not-bf16-inference")
-    kern = r.kernel
-    if own and kern != "library":
-        ok = {"ws": lambda: bias is None and linear_ws_eligible(x, weight), "ws128": lambda: bias is None and linear_ws_eligible(x, weight),
-              "sm": lambda: linear_sm_eligible(x, weight, bias), "tiled": lambda: True,
-              "tiled_halves": lambda: bias is None and x.dim() == 3 and linear_eligible(x, weight[:n // 2])}[kern]()
-        if not ok:
-            routing.REFUSED.append((role, tokens, n, k, kern))
-            del routing.REFUSED[:-64]
-            kern = "library"
-    fuse = residual is not None and r.fuse_add and kern in ("sm", "tiled") and not torch.is_grad_enabled() and gated_residual_eligible(x, residual, gate)
-    if kern == "library":
-        y = linear_train(x, weight, bias)
-    elif kern == "tiled_halves":
+    if not linear_eligible(x, weight, bias):
+        return routing.Route("library", False, "not-bf16-inference")
+    tokens = x.numel() // k
+    for r in routing.candidates(role, tokens, n, k):
+        if _TENSOR_LIMITS[r.kernel](x, bias):
+            fuse = r.fuse_add and residual is not None and not torch.is_grad_enabled() and gated_residual_eligible(x, residual, gate)
+            return r._replace(fuse_add=fuse)
+        routing.REFUSED.append((role, tokens, n, k, r.kernel))
+        del routing.REFUSED[:-64]
+
+
+def run(r, x, weight, bias=None, residual=None, gate=None, silu_from_col=None):
+    """x @ weight.T (+ bias) on the kernel of plan()'s route r — with residual + gate[:, None] * (.) in its epilogue if r.fuse_add; a library route
+    is wgrad.linear_train (F.linear; under autograd with the slab-wise weight gradient).  silu_from_col: the weight-stationary kernel's SiLU epilogue."""
+    if r.kernel == "library":
+        from .wgrad import linear_train
+        return linear_train(x, weight, bias)
+    if r.kernel == "tiled_halves":
+        n = weight.shape[0]
         y = torch.empty(*x.shape[:-1], n, device=x.device, dtype=x.dtype)
         o2 = y.view(-1, n)
         linear(x, weight[:n // 2], out=o2[:, :n // 2])
         linear(x, weight[n // 2:], out=o2[:, n // 2:])
-    elif fuse:
-        return linear(x, weight, bias, residual=residual, gate=gate, few_tokens=kern == "sm")
-    else:
-        y = linear(x, weight, bias, weight_stationary=kern in ("ws", "ws128"), few_tokens=kern == "sm")
-    return y if residual is None else torch.addcmul(residual, gate.unsqueeze(1), y)
+        return y
+    return linear(x, weight, bias, silu_from_col=silu_from_col, residual=residual if r.fuse_add else None, gate=gate if r.fuse_add else None,
+                  weight_stationary=r.kernel in ("ws", "ws128"), few_tokens=r.kernel == "sm")
 
 
-def fuses_gated_add(role, tokens, n, k):
-    """will project(role, ...) carry the gated add in the projection's epilogue for this shape (bf16 inference)?"""
-    r = routing.route(role, tokens, n, k)
-    return r.fuse_add and r.kernel in ("sm", "tiled")
+def project(role, x, weight, bias=None, residual=None, gate=None):
+    """The projections through ONE dispatch (plan, then run).  residual (B, L, n) + gate (B, n): the result is residual + gate[:, None] * (x @ weight.T
+    + bias) — in the serving kernel's epilogue where plan() fuses the add, as an addcmul behind the product otherwise."""
+    r = plan(role, x, weight, bias, residual, gate)
+    y = run(r, x, weight, bias, residual, gate)
+    return y if residual is None or r.fuse_add else torch.addcmul(residual, gate.unsqueeze(1), y)

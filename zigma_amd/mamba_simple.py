@@ -15,8 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _knobs
-from . import routing
-from .linear import fuses_gated_add, gated_residual_eligible, linear, linear_ws_eligible, project
+from .linear import plan, project, run
 from .selective_scan_interface import mamba_inner_tok
 
 NO_COPY_TEMPORAL = True      # video "t" layers on strided views (False: the transposing-copy form; A/B in the tests)
@@ -151,24 +150,16 @@ class Mamba(nn.Module):
             dt_proj.bias.copy_(inv_dt)
         dt_proj.bias._no_reinit = True
 
-    def forward(self, hidden_states, inference_params=None, residual=None, gate=None):
-        """residual (B, L, E) + gate (B, E): returns residual + gate[:, None] * mixer(hidden_states) — the block's gated branch add
-        (reference model_zigma.py:441-445), carried by out_proj's epilogue where the routing table says so (linear.project)."""
+    def forward(self, hidden_states, inference_params=None):
         y = self._mamba_inner_forward(hidden_states, inference_params)
-        return project("out_proj", y, self.out_proj.weight, self.out_proj.bias, residual=residual, gate=gate)
+        return project("out_proj", y, self.out_proj.weight, self.out_proj.bias)
 
-    def out_add_fusable(self, residual, gate):
-        """True when forward(..., residual=, gate=) will carry the gated add in out_proj's epilogue (no-grad, bf16, 256-row samples, and a row of the
-        routing table that fuses at this size)"""
-        lin = self.out_proj
-        if torch.is_grad_enabled() or not residual.is_cuda or residual.dtype != torch.bfloat16 or residual.dim() != 3:
-            return False
-        y = torch.empty(residual.shape[0], residual.shape[1], self.d_inner, device="meta", dtype=residual.dtype)   # shape / dtype stand-in
-        tokens = residual.shape[1] * residual.shape[0]
-        return (fuses_gated_add("out_proj", tokens, lin.weight.shape[0], self.d_inner)
-                and lin.weight.dtype == torch.bfloat16 and self.d_inner % 64 == 0
-                and lin.weight.shape[0] % 128 == 0 and gated_residual_eligible(y, residual, gate)
-                and (lin.bias is None or lin.bias.dtype == torch.bfloat16))
+    def forward_gated(self, hidden_states, residual, gate):
+        """(out, fused) with residual (B, L, E) + gate (B, E), the block's gated branch add (reference model_zigma.py:441-445): fused -> out =
+        residual + gate[:, None] * mixer(hidden_states) from out_proj's epilogue (where linear.plan fuses it); else out = mixer(hidden_states)"""
+        y = self._mamba_inner_forward(hidden_states)
+        r = plan("out_proj", y, self.out_proj.weight, self.out_proj.bias, residual, gate)
+        return run(r, y, self.out_proj.weight, self.out_proj.bias, residual, gate), r.fuse_add
 
     def _scan_consts(self, sfx):
         """(A = -exp(A_log), D, dt_bias) in float32, as the reference passes them to the scan
@@ -209,15 +200,12 @@ class Mamba(nn.Module):
         batch, seqlen, _ = hidden_states.shape
         A, Dp, dtb = self._scan_consts("")
         st = self.scan_type
-        zact = (GATE_IN_IN_PROJ and not torch.is_grad_enabled() and self.in_proj.bias is None and hidden_states.is_cuda
-                and hidden_states.dtype == torch.bfloat16 and (st == "v1" or st.startswith(("zigzagN", "hilbertN", "randomN")))
-                and self.d_state == 16 and seqlen % 16 == 0 and self.d_inner % 128 == 0 and batch <= 65535
-                and routing.route("in_proj", batch * seqlen, 2 * self.d_inner, hidden_states.shape[-1]).kernel == "ws"      # (256-feature panels only: the
-                and linear_ws_eligible(hidden_states, self.in_proj.weight))                                                  # narrow form has no SiLU epilogue)
-        if zact:      # in_proj writes (x, silu(z)); the scan (hot kernel: 16-bit, 16 states, whole tiles) multiplies by the gate as it finds it
-            xz = linear(hidden_states, self.in_proj.weight, weight_stationary=True, silu_from_col=self.d_inner)
-        else:
-            xz = project("in_proj", hidden_states, self.in_proj.weight, self.in_proj.bias)      # (B, L, 2*Di) token-major
+        r = plan("in_proj", hidden_states, self.in_proj.weight, self.in_proj.bias)
+        # (the hot scan kernel: 16-bit, 16 states, whole tiles, no backward; only the 256-feature panels of the weight-stationary kernel have the SiLU epilogue)
+        zact = (GATE_IN_IN_PROJ and r.kernel == "ws" and not torch.is_grad_enabled() and (st == "v1" or st.startswith(("zigzagN", "hilbertN", "randomN")))
+                and self.d_state == 16 and seqlen % 16 == 0 and self.d_inner % 128 == 0 and batch <= 65535)
+        # zact: in_proj writes (x, silu(z)); the scan multiplies by the gate as it finds it
+        xz = run(r, hidden_states, self.in_proj.weight, self.in_proj.bias, silu_from_col=self.d_inner if zact else None)     # (B, L, 2*Di) token-major
         fwd = lambda t, perm: mamba_inner_tok(t, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight,
                                                self.dt_proj.weight, A, Dp, dtb,
                                                perm=perm, out_rows=self._out_rows if perm is self._perm else None,

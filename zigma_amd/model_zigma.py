@@ -32,10 +32,8 @@ from torch import Tensor
 from .attention import attention_math, cross_attn, cross_attn_eligible, cross_attn_train
 from . import embed as _embed
 from .layernorm import RMSNorm, block_norm, glue_bwd_eligible, layer_norm_fn, rms_norm_fn, scale_reduce_bwd
-from . import routing
-from .linear import linear, linear_eligible, project
+from .linear import plan, project, run
 from .mamba_simple import Mamba
-from .wgrad import linear_train
 from .scan_paths import hilbert_path, reverse_permut_np, zigzag_path
 
 
@@ -266,35 +264,29 @@ class Pending:
         return torch.addcmul(self.base, self.gate.unsqueeze(1), self.branch)
 
 
+def _text_linear(x, weight, bias=None):
+    """x @ weight.T (+ bias) for a row count the projection kernel's 256-row tiles do not divide (B x 77 text tokens): the rows are
+    copied into a zero-padded buffer, the kernel the dispatch picks for the "text" role runs on the padded count, the real rows come back as
+    a view; F.linear on the real rows where the dispatch picks the library.  Reference call sites: model_zigma.py:668 (y_embedder),
+    :104-112 (to_k / to_v of every block, here one batched product)."""
+    k = x.shape[-1]
+    m = x.numel() // k
+    xp = x.new_zeros(-(-m // 256) * 256, k)
+    xp[:m] = x.reshape(m, k)
+    r = plan("text", xp, weight, bias)
+    if r.kernel == "library":
+        return F.linear(x, weight, bias)
+    return run(r, xp, weight, bias)[:m].view(*x.shape[:-1], weight.shape[0])
+
+
 # out_proj on the own projection kernel WITH the block's gated add `n + gate_msa * mixer(.)` in its epilogue, instead of the library
 # GEMM + the add inside the following norm kernel.  Per block (profiles/r02_b_bench_kernel_stats.csv vs r02_d_*): out_proj 127 -> 150 us,
 # pre-attention add + norm 68 -> 47, and with to_out's gated add: to_out 63 -> 78, pre-mixer add + norm 119 -> 102 — time moves from
 # the HBM-bound norm kernels into the projection epilogues, the forward is 0.1-0.3 % faster.
-TEXT_PROJ_OWN = True      # (knob: ZIGMA_KNOBS="model_zigma.TEXT_PROJ_OWN=False")
-# y_embedder and the batched K / V projection of all blocks (B x 77 text rows) on zigma_linear_fwd, rows padded to 256
-
-
-def _padded_own_linear(x, weight, bias):
-    """x @ weight.T (+ bias) for a row count the projection kernel's 256-row tiles do not divide (B x 77 text tokens): the rows are
-    copied into a zero-padded buffer, the kernel runs on the padded count, the real rows come back as a view.  None when the own
-    kernel does not take the operands (then the caller keeps F.linear).  Reference call sites: model_zigma.py:668 (y_embedder),
-    :104-112 (to_k / to_v of every block, here one batched product)."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16) or (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)):
-        return None
-    k = x.shape[-1]
-    m = x.numel() // k
-    mp = -(-m // 256) * 256
-    xp = x.new_zeros(mp, k)
-    xp[:m] = x.reshape(m, k)
-    if routing.POLICY == "off" or not linear_eligible(xp, weight, bias):
-        return None
-    return linear(xp, weight, bias)[:m].view(*x.shape[:-1], weight.shape[0])
-
-
 FUSE_OUT_PROJ_ADD = True       # (module-level knob for tests / tools; no environment switch)
 FUSE_OUT_PROJ_ADD_NO_TEXT = True     # the same for blocks without the attention branch (tools/outproj_notext_ab.py: 14.82 -> 14.78 ms on config 3's model)
 from . import _knobs  # noqa: E402
-_knobs.apply(globals(), "model_zigma")      # ZIGMA_KNOBS="model_zigma.TO_Q_WS_MAX_TOKENS=0,..." (A/B tools)
+_knobs.apply(globals(), "model_zigma")      # ZIGMA_KNOBS="model_zigma.FUSE_OUT_PROJ_ADD=False,..." (A/B tools)
 
 
 class Block(nn.Module):
@@ -328,23 +320,19 @@ class Block(nn.Module):
         _, residual, n, xm = block_norm(pend.base, self.norm.weight, self.norm.bias, residual, self.norm.eps, is_rms,
                                         residual_in_fp32=self.residual_in_fp32, branch=pend.branch, gate=pend.gate,
                                         shift=mod[:, 0:E], scale=mod[:, E:2 * E])
-        # (with the attention branch the following LayerNorm call shrinks to one read + one write; without it the next block's norm reads one
-        # tensor instead of base + branch — round 2's 8-wave kernel lost 0.7-0.9 % there against the library, the 4-wave one wins 0.25 %)
-        if FUSE_OUT_PROJ_ADD and self.has_text and self.mixer.out_add_fusable(n, mod[:, 2 * E:3 * E]):
-            # n + gate_msa * mixer(xm) in out_proj's epilogue (own projection kernel): the following norm reads one tensor, writes one
-            h = self.mixer(xm, residual=n, gate=mod[:, 2 * E:3 * E])
-            _, _, _, xa = block_norm(h, None, None, None, self.norm_msa.eps, False, residual_in_fp32=False,
-                                     shift=mod[:, 3 * E:4 * E], scale=mod[:, 4 * E:5 * E], want_x=False, want_y=False, want_res_out=False)
-            return Pending(self.msa(xa, text=text, mask=None, kv=kv, residual=h, gate=mod[:, 5 * E:6 * E])), residual
-        if FUSE_OUT_PROJ_ADD_NO_TEXT and not self.has_text and self.mixer.out_add_fusable(n, mod[:, 2 * E:3 * E]):
-            return Pending(self.mixer(xm, residual=n, gate=mod[:, 2 * E:3 * E])), residual
-        mix = self.mixer(xm)
+        # n + gate_msa * mixer(xm) in out_proj's epilogue where the dispatch fuses it (with the attention branch the following LayerNorm call shrinks to
+        # one read + one write; without it the next block's norm reads one tensor instead of base + branch — round 2's 8-wave kernel lost 0.7-0.9 %
+        # there against the library, the 4-wave one wins 0.25 %); otherwise the add rides in the next norm kernel
+        g = mod[:, 2 * E:3 * E]
+        fuse = FUSE_OUT_PROJ_ADD if self.has_text else FUSE_OUT_PROJ_ADD_NO_TEXT
+        y, fused = self.mixer.forward_gated(xm, n, g) if fuse else (self.mixer(xm), False)
+        pend = Pending(y) if fused else Pending(n, y, g)
         if not self.has_text:
-            return Pending(n, mix, mod[:, 2 * E:3 * E]), residual
-        h, _, _, xa = block_norm(n, None, None, None, self.norm_msa.eps, False, residual_in_fp32=False, branch=mix,
-                                 gate=mod[:, 2 * E:3 * E], shift=mod[:, 3 * E:4 * E], scale=mod[:, 4 * E:5 * E],
-                                 want_x=True, want_y=False, want_res_out=False)
+            return pend, residual
+        h, _, _, xa = block_norm(pend.base, None, None, None, self.norm_msa.eps, False, residual_in_fp32=False, branch=pend.branch,
+                                 gate=pend.gate, shift=mod[:, 3 * E:4 * E], scale=mod[:, 4 * E:5 * E], want_x=True, want_y=False, want_res_out=False)
         # h + gate_msa * attention(xa): the add rides in to_out's epilogue (one read of att less for the next block's add + norm)
+        h = pend.base if fused else h
         return Pending(self.msa(xa, text=text, mask=None, kv=kv, residual=h, gate=mod[:, 5 * E:6 * E])), residual
 
     def forward(self, x: Tensor, residual: Optional[Tensor] = None, c=None, text=None, inference_params=None, skip=None):
@@ -585,8 +573,7 @@ class ZigMa(nn.Module):
         t = self.t_embedder(t)                                                  # (N, D)
         if self.has_text:
             yp = y.to(pdtype)
-            ye = _padded_own_linear(yp, self.y_embedder.weight, self.y_embedder.bias) if TEXT_PROJ_OWN else None
-            y = ye if ye is not None else self.y_embedder(yp)                   # (B, n_ctx, D)
+            y = _text_linear(yp, self.y_embedder.weight, self.y_embedder.bias)     # (B, n_ctx, D)
             c = t + y.mean(dim=1)
         elif self.num_classes > 0:
             c = t + self.y_embedder(y, self.training)
@@ -667,8 +654,7 @@ class ZigMa(nn.Module):
         kvs = None
         if self.has_text:
             inner = blocks[0].msa.to_k.weight.shape[0]
-            kv_own = _padded_own_linear(text, Wkv, None) if TEXT_PROJ_OWN else None
-            kv_all = (kv_own if kv_own is not None else F.linear(text, Wkv)).view(text.shape[0], text.shape[1], n, 2, inner)
+            kv_all = _text_linear(text, Wkv).view(text.shape[0], text.shape[1], n, 2, inner)
             kvs = [(kv_all[:, :, i, 0], kv_all[:, :, i, 1]) for i in range(n)]
         return mods, kvs
 

@@ -1,12 +1,14 @@
-"""ONE routing table for the dense projections of the block loop.
+"""ONE routing table for every dense projection with a hand-written kernel.
 
     route(role, tokens, n, k) -> Route(kernel, fuse_add, row)
 
-role   = which projection of the reference's Block is asked for — it fixes the epilogue the call carries:
+role   = which projection is asked for — it fixes the epilogue the call carries:
            "in_proj"  x @ W_in^T            (mamba_simple.py:290-294), no epilogue
            "out_proj" y @ W_out^T           (selective_scan_interface.py:365), optionally the block's gated add n + gate * (.)
            "to_q"     xa @ W_q^T            (model_zigma.py:104-106), no epilogue
            "to_out"   o @ W_o^T + bias      (model_zigma.py:128-135), bias + the block's gated add h + gate * (.)
+           "text"     y_embedder and the batched to_k / to_v of all blocks (model_zigma.py:668, :104-112) on rows the caller padded to 256
+           "train"    the forward product and dX = dY W of wgrad.LinearTrainFn (the training path of all four block projections)
 kernel = which kernel family of zigma_linear_fwd serves it (KERNELS below), or "library" (F.linear = hipBLASLt) — every cell that falls
          to the library is an explicit row of the table or the explicit last row, and tests/test_host_cpu.py::test_routing_table sweeps
          E x tokens and compares the library cells with a reviewed list.
@@ -14,12 +16,13 @@ fuse_add = the caller hands the gated residual to the kernel's epilogue (True) o
 
 The table holds POLICY (what is fastest where, with the measurement that decided it); the shape LIMITS of each kernel family are the
 `serves_*` functions, mirrored from the C side (csrc/linear_ws.hip linear_ws_panel, csrc/linear_sm.hip linear_sm_blocks, csrc/linear4w.hip
-linear4w_variant, zigma_linear_fwd) — a row never returns a kernel whose limits the shape does
-not meet.  Pointer / stride alignment is checked on the tensors by linear.py's `*_eligible` predicates when the call is made; a refusal there
-lands on the library and is counted in REFUSED (never silent: tests assert it stays empty on the shipped shapes).
+linear4w_variant, zigma_linear_fwd) — a row never returns a kernel whose limits the shape does not meet.  linear.plan walks candidates() and
+checks each kernel's limits on the tensors (pointer / stride alignment, bias); a row the tensors refuse is counted in REFUSED and the walk goes on
+to the next row (never silent: tests assert REFUSED stays empty on the shipped shapes).
 
 Knobs (tools / tests; no environment variable of their own — ZIGMA_KNOBS="routing.POLICY=off,routing.DISABLED=in_proj.ws+to_q.sm"):
-  POLICY    "auto" the table;  "all" every projection the tiled kernels can serve runs on them (fused epilogues on);  "off" library only
+  POLICY    "auto" the table;  "all" every block projection the tiled kernels can serve runs on them (fused epilogues on; "text" and "train"
+            as under "auto");  "off" library only, every role
   DISABLED  row ids skipped ("+"-separated string or a set): A/B of one row against what the table holds below it
 """
 from collections import namedtuple
@@ -40,7 +43,7 @@ KERNELS = ("ws", "ws128", "sm", "tiled", "tiled_halves", "library")
 POLICY = "auto"
 DISABLED = ""
 INF = 1 << 40
-REFUSED = []          # (role, tokens, n, k, kernel) of calls a table row chose and the tensor-level check of linear.py turned down (the last 64 of them)
+REFUSED = []          # (role, tokens, n, k, kernel) of rows a call matched and the tensor-level check of linear.py turned down (the last 64 of them)
 
 
 # ---- shape limits of the kernel families (C side mirrored) ---------------------------------------------------------------------------------
@@ -120,8 +123,17 @@ TABLE = (
     Row("to_out.tiled", "to_out", (64, INF), (128, 4096), (8, INF), "tiled", True,
         "the library cannot fuse bias + gated add: 54 us (67 in the forward) against 70 + the add (round 3)"),
     Row("to_out.library", "to_out", (1, INF), (1, INF), (1, INF), "library", False, "shapes the tiled kernels do not serve"),
+    # -- text: B x 77 text rows padded to 256, tiled wherever it serves
+    Row("text.tiled", "text", (1, INF), (1, INF), (1, INF), "tiled", False, "y_embedder and the batched K / V of all blocks in one launch each"),
+    Row("text.library", "text", (1, INF), (1, INF), (1, INF), "library", False, "shapes the tiled kernels do not serve"),
+    # -- train: forward product and dX of the training path, weight-stationary where it serves the shape (no bias), then tiled
+    Row("train.ws", "train", (1, INF), (1, INF), (1, INF), "ws", False, "round 4: the forward and dX of in_proj (k = 640) and to_q"),
+    Row("train.ws128", "train", (1, INF), (1, INF), (1, INF), "ws128", False, "round 4: out_proj's forward (k = 1280)"),
+    Row("train.tiled", "train", (1, INF), (1, INF), (1, INF), "tiled", False, "every other product the tiled kernels serve"),
+    Row("train.library", "train", (1, INF), (1, INF), (1, INF), "library", False, "shapes the tiled kernels do not serve"),
 )
-ROLES = ("in_proj", "out_proj", "to_q", "to_out")
+BLOCK_ROLES = ("in_proj", "out_proj", "to_q", "to_out")
+ROLES = BLOCK_ROLES + ("text", "train")
 
 _knobs.apply(globals(), "routing")
 
@@ -134,16 +146,18 @@ def _disabled():
     return DISABLED if isinstance(DISABLED, (set, frozenset)) else {s for s in str(DISABLED).split("+") if s}
 
 
-def route(role, tokens, n, k):
-    """the table's decision for a bf16 inference call of `role` with `tokens` rows, n output and k input features"""
+def candidates(role, tokens, n, k):
+    """the routes the table offers a bf16 inference call of `role` with `tokens` rows, n output and k input features, best first; the last is the library"""
     if role not in ROLES:
         raise ValueError(f"routing: unknown role {role!r}")
     if POLICY == "off":
-        return Route("library", False, "policy.off")
-    if POLICY == "all":
+        yield Route("library", False, "policy.off")
+        return
+    if POLICY == "all" and role in BLOCK_ROLES:
         if serves_tiled(tokens, n, k):
-            return Route("tiled", role in ("out_proj", "to_out"), "policy.all")
-        return Route("library", False, "policy.all")
+            yield Route("tiled", role in ("out_proj", "to_out"), "policy.all")
+        yield Route("library", False, "policy.all")
+        return
     off = _disabled()
     for row in TABLE:
         if row.role != role or row.id in off or not (_in(k, row.k) and _in(n, row.n) and _in(tokens, row.tokens)):
@@ -151,9 +165,16 @@ def route(role, tokens, n, k):
         if not _SERVES[row.kernel](tokens, n, k):
             continue
         if row.id in ("in_proj.tiled_wide_k", "in_proj.tiled_narrow", "out_proj.tiled") and not serves_4w(tokens, n, k):
-            continue              # (these two rows are only faster than what follows them on the 4-wave kernel)
-        return Route(row.kernel, row.fuse_add, row.id)
+            continue              # (these rows are only faster than what follows them on the 4-wave kernel)
+        yield Route(row.kernel, row.fuse_add, row.id)
+        if row.kernel == "library":
+            return
     raise AssertionError("routing: the table's last row of every role matches everything")
+
+
+def route(role, tokens, n, k):
+    """the table's decision for this shape (the first of candidates())"""
+    return next(candidates(role, tokens, n, k))
 
 
 def kernel_name(route_or_kernel, tokens=None, n=None, k=None):

@@ -6,16 +6,13 @@ CUs and run at 0.03 ... 0.5 PFLOP/s (tools/wgrad_split_probe.py: in_proj 450 us,
 into S slabs as a BATCHED GEMM (the slab index is the library's batch dimension) the same products fill the chip; the S partial
 results (bf16, like a GEMM output) are added in fp32: in_proj 332 us, out_proj 303 -> 149, to_q 259 -> 76, to_out 271 -> 66,
 x_proj 227 -> 72, dt_proj 205 -> 64 us — 17 ms of a 122 ms training step.  `LinearTrainFn` is F.linear with that backward; since round 4 its forward product and dX run on the hand-written projection kernels
-(zigma_linear_fwd) where one serves the shape — `OWN_TRAIN_GEMMS`."""
-import os
-
+(zigma_linear_fwd) where one serves the shape — the "train" rows of zigma_amd/routing.py (routing.POLICY="off": the library for both)."""
 import torch
 import torch.nn.functional as F
 
+from .linear import plan, run
+
 SPLIT_WGRAD = True        # False: one GEMM (A/B in tools/train_probe.py)
-# forward projection and dX = dY W of the training path on the hand-written MFMA kernels (zigma_linear_fwd: weight-stationary / tiled) where they
-# serve the shape; dW stays the slab-wise batched product below.  "0": the library for both (A/B in tools/train_probe.py)
-OWN_TRAIN_GEMMS = True
 
 
 _BMM_OUT_DTYPE = {}      # (device type, index, dtype) -> bool
@@ -43,29 +40,9 @@ def _bmm_takes_out_dtype(x):
     return hit
 
 
-def _own_linear(x, weight, bias=None, transposed=False):
-    """x @ weight^T (+ bias) on zigma_linear_fwd if a kernel of it serves the call (autograd is off in here), else None.
-    transposed: the product wanted is x @ weight (dX = dY W) — the transposed copy of the weight is only made once a kernel is known to
-    take the call (eligibility is decided on shapes, dtypes and alignment, which the copy does not change)"""
-    from . import routing
-    from .linear import linear, linear_eligible, linear_ws_eligible
-    if not OWN_TRAIN_GEMMS or routing.POLICY == "off" or not x.is_cuda or x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
-        return None
-    if transposed:
-        wt = _ContiguousLike(weight)
-        if not ((bias is None and linear_ws_eligible(x, wt)) or linear_eligible(x, wt, bias)):
-            return None
-        weight = weight.t().contiguous()
-    if bias is None and linear_ws_eligible(x, weight):
-        return linear(x, weight, weight_stationary=True)
-    if linear_eligible(x, weight, bias):
-        return linear(x, weight, bias)
-    return None
-
-
 class _ContiguousLike:
-    """Stand-in for `weight.t().contiguous()` in the eligibility predicates of linear.py, which read device, dtype, shape, strides and the
-    16-byte alignment of data_ptr (a fresh allocation is aligned) — so the decision can be taken before the copy is made."""
+    """Stand-in for `weight.t().contiguous()` in linear.plan, whose limits read device, dtype, shape, strides and the 16-byte alignment of
+    data_ptr (a fresh allocation is aligned) — so the kernel is chosen before the copy is made, and the copy is only made for a kernel."""
 
     def __init__(self, weight):
         self.is_cuda, self.dtype, self.device, self.requires_grad = weight.is_cuda, weight.dtype, weight.device, False
@@ -120,8 +97,8 @@ class LinearTrainFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias):
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
-        out = _own_linear(x, weight, bias)
-        return F.linear(x, weight, bias) if out is None else out
+        r = plan("train", x, weight, bias)            # (autograd is off in here)
+        return F.linear(x, weight, bias) if r.kernel == "library" else run(r, x, weight, bias)
 
     @staticmethod
     def backward(ctx, dy):
@@ -130,8 +107,8 @@ class LinearTrainFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dyc = dy2 if dy2.is_contiguous() else dy2.contiguous()
-            dx = _own_linear(dyc, weight, transposed=True)         # dX = dY W = dY (W^T)^T: the same kernels on the transposed weight (a few MB)
-            dx = (dy2 @ weight).view(x.shape) if dx is None else dx.view(x.shape)
+            r = plan("train", dyc, _ContiguousLike(weight))        # dX = dY W = dY (W^T)^T: the same kernels on the transposed weight (a few MB)
+            dx = (dy2 @ weight if r.kernel == "library" else run(r, dyc, weight.t().contiguous())).view(x.shape)
         if ctx.needs_input_grad[1]:
             dw = wgrad(dy2, x.reshape(-1, x.shape[-1]))
         if ctx.has_bias and ctx.needs_input_grad[2]:
