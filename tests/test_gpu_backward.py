@@ -604,6 +604,31 @@ def test_video_temporal_layers_train_without_transposing_copies():
     assert worst[0] < 2e-2, worst
 
 
+def test_v2_partial_freeze_trains_the_reversed_sweep():
+    """`v2` with every parameter frozen except x_proj_b: the reversed sweep alone records autograd (it used to take the inference branch
+    with add_to= and raise).  Its gradient matches the one from the same model with nothing frozen, up to bf16 roundings (the frozen run's
+    in_proj and first sweep take the inference kernels)."""
+    from zigma_amd.mamba_simple import Mamba
+    torch.manual_seed(0)
+    m = Mamba(d_model=128, d_state=16, scan_type="v2", device=DEV, dtype=torch.bfloat16).train()
+    h = torch.randn(2, 256, 128, device=DEV, dtype=torch.bfloat16)
+    wgt = torch.randn(2, 256, 128, device=DEV)
+    grads, outs = {}, {}
+    for frozen in (True, False):
+        m.zero_grad(set_to_none=True)
+        for n, p in m.named_parameters():
+            p.requires_grad_(not frozen or n == "x_proj_b.weight")
+        out = m(h.clone().requires_grad_(not frozen))
+        (out.float() * wgt).sum().backward()
+        grads[frozen], outs[frozen] = m.x_proj_b.weight.grad.float(), out.detach().float()
+        assert all(p.grad is None for n, p in m.named_parameters() if frozen and n != "x_proj_b.weight")
+    for p in m.parameters():
+        p.requires_grad_(True)
+    assert float(grads[True].abs().max()) > 0
+    assert rel_err(N(outs[True]), N(outs[False])) < 2e-2
+    assert rel_err(N(grads[True]), N(grads[False])) < 2e-2, rel_err(N(grads[True]), N(grads[False]))
+
+
 @pytest.mark.parametrize("M,K,N,bias", [(65536, 640, 2560, False), (16384, 1280, 640, False), (8192, 512, 640, True), (4096, 640, 512, False)])
 def test_linear_train_fn_own_kernels_vs_library(M, K, N, bias, monkeypatch):
     """wgrad.LinearTrainFn (round 4): forward product and dX on zigma_linear_fwd (weight-stationary / tiled kernels) — asserted from the call

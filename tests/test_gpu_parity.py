@@ -580,6 +580,63 @@ def test_scan_tok2_accumulating_form(Bsz, L, Di, R, use_perm, io, monkeypatch):
     assert rel_err(N(got), N(got2)) < (4e-3 if io == "bf16" else 6e-4)
 
 
+def test_inner_plan_is_what_the_library_serves(monkeypatch):
+    """plan_inner's choice for every mamba_inner_tok call equals what the library ran, from the call trace: the one-pass conv + x_proj or
+    the x_proj kernel exactly when the front says so, the dt_proj kernel exactly for dt == "kernel", the scan's dt_x for dt_proj inside
+    it, its carry buffer x for a sequence split and ZIGMA_SCAN_ACCUMULATE for accumulate.  A refused call would raise (UNSUPPORTED)."""
+    import zigma_amd.selective_scan_interface as ssi
+    from zigma_amd import _lib
+    bf = torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(5)
+    plans, real = [], ssi.plan_inner
+    monkeypatch.setattr(ssi, "plan_inner", lambda *a, **k: (plans.append(real(*a, **k)), plans[-1])[1])
+    cases = []
+    for Bsz in (1, 4, 16, 64):
+        for L in (256, 1024, 4096):
+            for Di in (1280, 1536):
+                for rp in (0, 16):
+                    cases.append((Bsz, L, Di, rp, None))
+                    if rp == 0 and L != 1024:
+                        cases += [(Bsz, L, Di, rp, "add_to"), (Bsz, L, Di, rp, "z_preactivated")]
+                    if L == 1024 and Bsz in (1, 16):
+                        cases.append((Bsz, L, Di, rp, "train"))
+    seen = set()
+    for Bsz, L, Di, rp, form in cases:
+        R, Nst = Di // 32, 16
+        rnd = lambda *s, sc=1.0, dt=bf: (sc * torch.randn(*s, device=DEV, generator=g)).to(dt)
+        xz, cw, cb = rnd(Bsz, L, 2 * Di), rnd(Di, 1, 4, sc=0.5), rnd(Di, sc=0.1)
+        xw, dw = rnd(R + 2 * Nst, Di, sc=Di ** -0.5), rnd(Di, R, sc=R ** -0.5)
+        A, D, db = -torch.rand(Di, Nst, device=DEV, generator=g) - 0.5, rnd(Di, dt=torch.float32), rnd(Di, dt=torch.float32) - 3
+        perm = None if rp else torch.randperm(L, device=DEV, generator=g).to(torch.int32)
+        train = form == "train"
+        if train:
+            xz.requires_grad_(True)
+        _lib.TRACE = []
+        try:
+            with torch.set_grad_enabled(train):
+                ssi.mamba_inner_tok(xz, cw, cb, xw, dw, A, D, db, perm=perm, reset_period=rp, z_preactivated=form == "z_preactivated",
+                                    add_to=rnd(Bsz, L, Di) if form == "add_to" else None)
+            trace = _lib.TRACE
+        finally:
+            _lib.TRACE = None
+        p = plans.pop()
+        names = [fn for fn, _, _ in trace]
+        scans = [pb for fn, _, pb in trace if fn == "zigma_selective_scan_fwd"]
+        case = (Bsz, L, Di, rp, form, p)
+        assert len(scans) == 1, case
+        assert ("zigma_conv_x_proj_fwd" in names) == (p.front == "conv_x_proj"), case
+        assert ("zigma_x_proj_fwd" in names) == (p.front == "conv+x_proj"), case
+        assert ("zigma_dt_proj_softplus_fwd" in names) == (p.dt == "kernel"), case
+        assert bool(scans[0].dt_x) == (p.dt in ("in_scan", "in_split")), case
+        assert bool(scans[0].x) == (p.chunk_len > 0), case
+        assert bool(scans[0].flags & _lib.SCAN_ACCUMULATE) == p.accumulate, case
+        assert bool(scans[0].flags & _lib.SCAN_Z_PREACTIVATED) == (form == "z_preactivated"), case
+        seen |= {p.front, p.dt, ("accumulate", p.accumulate), ("split", p.chunk_len > 0)}
+    assert not plans
+    assert seen >= {"conv_x_proj", "conv+x_proj", "conv+linear", "in_scan", "in_split", "kernel", "linear",
+                    ("accumulate", True), ("split", True)}, seen
+
+
 @pytest.mark.parametrize("io", ["bf16", "f16"])
 @pytest.mark.parametrize("T,nseq,K", [(16, 2, 40), (32, 3, 12), (16, 4, 256)])
 def test_dt_proj_in_kernel_with_reset_period(T, nseq, K, io, monkeypatch):

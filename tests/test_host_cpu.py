@@ -594,6 +594,86 @@ def test_sequence_split_policy():
         assert c % 16 == 0 and c >= 32 and -(-1024 // c) >= 2
 
 
+def _tok2_split_eligible(batch, d_inner, seqlen, chunk_len):
+    """the shape part of tok2_split_eligible() (zigma_amd/csrc/scan_tok2.inc), restated for the sweep below"""
+    chunk_len = chunk_len if chunk_len > 0 else 2048
+    n_chunks = (seqlen + chunk_len - 1) // chunk_len
+    return chunk_len % 16 == 0 and 2 <= n_chunks <= 65535 and (d_inner // 64) * batch < 768
+
+
+def test_split_chunks_pass_the_c_side_split_limits(monkeypatch):
+    """split_chunk_len under the default knobs only returns chunks the C side's sequence split accepts, and split_limits_ok refuses
+    exactly what tok2_split_eligible refuses — including the chunks a raised SPLIT_MAX_WGS produces and more than 65535 chunks."""
+    import zigma_amd.selective_scan_interface as ssi
+    Ls = (16, 32, 48, 128, 240, 256, 272, 1008, 1024, 1040, 2048, 4080, 4096, 4112, 8192, 16384, 65552, 1 << 20)
+    Dis = (64, 128, 640, 1280, 1536, 3072, 4096)
+
+    def sweep():
+        hits = []
+        for b in range(1, 1025):
+            for di in Dis:
+                for L in Ls:
+                    c = ssi.split_chunk_len(b, di, L)
+                    if c:
+                        hits.append((b, di, L, c, ssi.split_limits_ok(b, di, L, c)))
+        return hits
+    hits = sweep()
+    assert len(hits) > 1000 and all(ok for *_, ok in hits)
+    assert all(_tok2_split_eligible(b, di, L, c) for b, di, L, c, _ in hits)
+    monkeypatch.setattr(ssi, "SPLIT_MAX_WGS", 1024)
+    hits = sweep()
+    refused = [h for h in hits if not h[4]]
+    assert refused and all(b * (di // 64) >= 768 for b, di, *_ in refused)
+    assert all(ok == _tok2_split_eligible(b, di, L, c) for b, di, L, c, ok in hits)
+    assert ssi.split_limits_ok(1, 64, 16 * 65535, 16) and not ssi.split_limits_ok(1, 64, 16 * 65536, 16)
+    assert not ssi.split_limits_ok(1, 64, 1024, 24) and not ssi.split_limits_ok(1, 64, 1024, 1024) and not ssi.split_limits_ok(1, 64, 1024, 0)
+
+
+def test_inner_plan_rules(monkeypatch):
+    """plan_inner: the front, dt and accumulate rules in their order, with the kernels' eligibility predicates patched (CPU tensors)"""
+    import zigma_amd.selective_scan_interface as ssi
+    bf = torch.bfloat16
+    B, L, Di, R, N = 64, 1024, 1280, 40, 16
+    xz, w, cb = torch.zeros(B, L, 2 * Di, dtype=bf), torch.zeros(Di, 4, dtype=bf), torch.zeros(Di, dtype=bf)
+    xw, dw, A, db = torch.zeros(R + 2 * N, Di, dtype=bf), torch.zeros(Di, R, dtype=bf), torch.zeros(Di, N), torch.zeros(Di)
+    seen = []
+    for name in ("conv_x_proj_eligible", "x_proj_eligible", "dt_in_scan_eligible", "dt_proj_eligible"):
+        monkeypatch.setattr(ssi, name, lambda *a, _n=name, **k: (seen.append(_n), True)[1])
+    P = lambda xz=xz, **k: ssi.plan_inner(xz[:, :, :Di], xz[:, :, Di:], w, cb, xw, dw, A, db, **k)
+    assert P() == ssi.InnerPlan("conv_x_proj", "in_scan", 0, False)
+    assert P(add_to=xz[:, :, :Di]) == ssi.InnerPlan("conv_x_proj", "in_scan", 0, True)
+    assert P(train=True) == ssi.InnerPlan("conv_x_proj", "linear", 0, False)
+    assert P(B_proj_bias=db) == ssi.InnerPlan("conv_x_proj", "kernel", 0, False)
+    assert P(delta_softplus=False) == ssi.InnerPlan("conv_x_proj", "linear", 0, False)
+    seen.clear()
+    assert P() == ssi.InnerPlan("conv_x_proj", "in_scan", 0, False) and seen == ["conv_x_proj_eligible", "dt_in_scan_eligible"]
+    monkeypatch.setattr(ssi, "ACCUMULATE_IN_SCAN", False)
+    assert P(add_to=xz[:, :, :Di]).accumulate is False
+    monkeypatch.setattr(ssi, "USE_CONV_X_PROJ", False)
+    assert P().front == "conv+x_proj" and P(train=True).front == "conv+linear"
+    monkeypatch.setattr(ssi, "USE_X_PROJ_KERNEL", False)
+    assert P().front == "conv+linear"
+    small = xz[:4, :, :]                                             # 80 workgroups: the sequence split, chunks of 112 steps
+    assert P(small) == ssi.InnerPlan("conv+linear", "in_split", 112, False)
+    assert P(small, add_to=small[:, :, :Di]) == ssi.InnerPlan("conv+linear", "in_split", 112, False)
+    assert P(small, z_preactivated=True).dt == "kernel" and P(small, train=True) == ssi.InnerPlan("conv+linear", "linear", 0, False)
+    assert ssi.plan_inner(small[:, :, :Di], small[:, :, Di:], w, cb, xw, dw, A, None).dt == "kernel"
+    monkeypatch.setattr(ssi, "DT_PROJ_IN_SPLIT", False)
+    assert P(small) == ssi.InnerPlan("conv+linear", "kernel", 112, False)
+    monkeypatch.setattr(ssi, "DT_PROJ_IN_SCAN", False)
+    assert P().dt == "kernel"
+    monkeypatch.setattr(ssi, "dt_proj_eligible", lambda *a: False)
+    assert P().dt == "linear"
+
+
+def test_differentiable_predicate():
+    from zigma_amd.selective_scan_interface import differentiable
+    a, b = torch.zeros(2), torch.zeros(2, requires_grad=True)
+    assert not differentiable(a, None) and differentiable(a, None, b)
+    with torch.no_grad():
+        assert not differentiable(a, b)
+
+
 def test_linear_train_fn_matches_autograd_and_slab_rule():
     """zigma_amd.wgrad: LinearTrainFn (F.linear with the slab-wise weight gradient) gives autograd's gradients; the slab rule returns a
     power of two that divides the rows into slabs of at least 256 rows (multiples of 8)."""

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import _knobs
 from .linear import plan, project, run
-from .selective_scan_interface import mamba_inner_tok
+from .selective_scan_interface import differentiable, mamba_inner_tok, z_preactivated_eligible
 
 NO_COPY_TEMPORAL = True      # video "t" layers on strided views (False: the transposing-copy form; A/B in the tests)
 # Which kernel serves in_proj / out_proj at which size is zigma_amd/routing.py (ONE table, with the measurement behind every row).
@@ -201,26 +201,23 @@ class Mamba(nn.Module):
         A, Dp, dtb = self._scan_consts("")
         st = self.scan_type
         r = plan("in_proj", hidden_states, self.in_proj.weight, self.in_proj.bias)
-        # (the hot scan kernel: 16-bit, 16 states, whole tiles, no backward; only the 256-feature panels of the weight-stationary kernel have the SiLU epilogue)
-        zact = (GATE_IN_IN_PROJ and r.kernel == "ws" and not torch.is_grad_enabled() and (st == "v1" or st.startswith(("zigzagN", "hilbertN", "randomN")))
-                and self.d_state == 16 and seqlen % 16 == 0 and self.d_inner % 128 == 0 and batch <= 65535)
-        # zact: in_proj writes (x, silu(z)); the scan multiplies by the gate as it finds it
+        # zact: in_proj writes (x, silu(z)) — only the 256-feature panels of the weight-stationary kernel have that epilogue — and the scan
+        # multiplies by the gate as it finds it (v2 and the video types read xz elsewhere too)
+        zact = (GATE_IN_IN_PROJ and r.kernel == "ws" and self.d_inner % 128 == 0 and (st == "v1" or st.startswith(("zigzagN", "hilbertN", "randomN")))
+                and z_preactivated_eligible(batch, seqlen, self.d_state))
         xz = run(r, hidden_states, self.in_proj.weight, self.in_proj.bias, silu_from_col=self.d_inner if zact else None)     # (B, L, 2*Di) token-major
-        fwd = lambda t, perm: mamba_inner_tok(t, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight,
-                                               self.dt_proj.weight, A, Dp, dtb,
-                                               perm=perm, out_rows=self._out_rows if perm is self._perm else None,
+        weights = (self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight, A, Dp, dtb)
+        fwd = lambda t, perm: mamba_inner_tok(t, *weights, perm=perm, out_rows=self._out_rows if perm is self._perm else None,
                                                delta_softplus=True, z_preactivated=zact)
         if st == "v1":
             y = fwd(xz, None)
         elif st == "v2":
             A_b, Dp_b, dtb_b = self._scan_consts("_b")
             y = fwd(xz, None)
-            if torch.is_grad_enabled() and (xz.requires_grad or self.conv1d_b.weight.requires_grad):
-                y = y + mamba_inner_tok(xz, self.conv1d_b.weight, self.conv1d_b.bias, self.x_proj_b.weight, self.dt_proj_b.weight, A_b, Dp_b, dtb_b,
-                                        perm=self._reversed_table(seqlen, xz.device), delta_softplus=True)      # both already in token order
-            else:       # inference: the reversed sweep ADDS itself to y (in its scan's epilogue where the hot kernel serves the call) — no `out + out_b.flip` pass
-                y = mamba_inner_tok(xz, self.conv1d_b.weight, self.conv1d_b.bias, self.x_proj_b.weight, self.dt_proj_b.weight, A_b, Dp_b, dtb_b,
-                                    perm=self._reversed_table(seqlen, xz.device), delta_softplus=True, add_to=y)
+            b = (xz, self.conv1d_b.weight, self.conv1d_b.bias, self.x_proj_b.weight, self.dt_proj_b.weight, A_b, Dp_b, dtb_b)
+            kw = dict(perm=self._reversed_table(seqlen, xz.device), delta_softplus=True)       # both sweeps already in token order
+            # inference: the reversed sweep ADDS itself to y (in its scan's epilogue where the hot kernel serves the call) — no `out + out_b.flip` pass
+            y = y + mamba_inner_tok(*b, **kw) if differentiable(*b) else mamba_inner_tok(*b, **kw, add_to=y)
         elif st.startswith(("zigzagN", "hilbertN", "randomN")):
             if self.extras:
                 raise NotImplementedError("extras > 0 is never produced by ZigMa (model_zigma.py:686)")
@@ -239,16 +236,14 @@ class Mamba(nn.Module):
                 # backward kernels take the same views and d(xz) comes back as a view of a (b t, k, c) allocation.
                 perm_bt, out_bt = self._tiled_tables(batch, T)
                 xv = xz.view(batch * T, K, C2).transpose(0, 1)
-                if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (
-                        xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight, A, Dp, dtb)):
-                    y = mamba_inner_tok(xv, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight, A, Dp, dtb,
-                                        perm=perm_bt, out_rows=out_bt, delta_softplus=True, reset_period=T)
+                args = (xv,) + weights
+                if differentiable(*args):
+                    y = mamba_inner_tok(*args, perm=perm_bt, out_rows=out_bt, delta_softplus=True, reset_period=T)
                     y = y.transpose(0, 1).reshape(batch, seqlen, C2 // 2)        # (k, b t, c) view of a (b t, k, c) tensor: no copy
                 else:
                     y = torch.empty(batch, seqlen, C2 // 2, device=xz.device, dtype=xz.dtype)
-                    mamba_inner_tok(xv, self.conv1d.weight, self.conv1d.bias,
-                                    self.x_proj.weight, self.dt_proj.weight, A, Dp, dtb, perm=perm_bt, out_rows=out_bt,
-                                    delta_softplus=True, reset_period=T, out=y.view(batch * T, K, C2 // 2).transpose(0, 1))
+                    mamba_inner_tok(*args, perm=perm_bt, out_rows=out_bt, delta_softplus=True, reset_period=T,
+                                    out=y.view(batch * T, K, C2 // 2).transpose(0, 1))
             elif s_or_t == "t":     # b (t k) c -> (b k) t c : one transposing copy in, one out
                 xt = xz.view(batch, T, K, C2).transpose(1, 2).reshape(batch * K, T, C2)
                 yt = fwd(xt, self._perm)

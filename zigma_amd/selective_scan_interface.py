@@ -10,28 +10,34 @@ order and error behaviour) for the FORWARD path:
 
 plus `mamba_inner_tok`, the token-major fused form the ZigMa block uses on MI355X: conv, scan and
 the zigzag gather/scatter run on (B, L, C) activations straight out of / into the projection GEMMs,
-so none of the reference's transposes, `index_select`s or `cat`s exist.
+so none of the reference's transposes, `index_select`s or `cat`s exist.  `plan_inner` is the one place that chooses its kernels (conv +
+x_proj front, where dt_proj runs, the sequence split, the accumulating epilogue); `mamba_inner_tok` and `MambaInnerTokFn` carry the plan out.
 
 Backward: `scan_bwd_tok` binds zigma_selective_scan_bwd; `MambaInnerTokFn` is the autograd
 form of `mamba_inner_tok` (MambaInnerFn.backward, :367-434) that the blocks use when autograd is recording.  The
 (B, D, L)-layout entry points (`selective_scan_fn`, `mamba_inner_fn`) stay forward-only.
 """
 
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _knobs, _lib
 from .causal_conv1d_interface import causal_conv1d_raw, conv_bwd_tok
 from .wgrad import wgrad
 
 
-SPLIT_SMALL_BATCH = True     # tools/latency_probe.py flips this to measure the effect of the small-batch sequence split
-# module-level knobs for the A/B tools and tests (tools/, tests/ set them directly; no environment switches)
+SPLIT_SMALL_BATCH = True             # tools/latency_probe.py flips this to measure the effect of the small-batch sequence split
+SPLIT_MAX_WGS = 200                  # ... and sweeps this: split when batch * d_inner / 64 is at most this many workgroups (tools/split_threshold_probe.py)
 USE_CONV_X_PROJ = True               # conv + SiLU + x_proj in one kernel (u written once, never read back); False: the two kernels
 CONV_X_PROJ_MIN_POSITIONS = 16384    # below: too few workgroups (128 positions each)
+USE_X_PROJ_KERNEL = True             # own MFMA kernel for the skinny x_proj instead of the library GEMM (same speed stand-alone)
 DT_PROJ_FLAGS = 0                    # 1: four-byte stores (A/B probe of dt_proj.hip)
-USE_X_PROJ_KERNEL = True      # own MFMA kernel for the skinny x_proj instead of the library GEMM (same speed stand-alone)
-SPLIT_MAX_WGS = 200          # ... and sweeps this: split when batch * d_inner / 64 is at most this many workgroups (tools/split_threshold_probe.py)
+DT_PROJ_IN_SCAN = True               # dt_proj + softplus in the scan's tile prologue (MFMA) instead of a kernel of its own
+DT_PROJ_IN_SPLIT = True              # sequence-split mode: dt_proj + softplus inside the split's first pass, which writes delta for the second (round 6)
+ACCUMULATE_IN_SCAN = True            # `v2`: the second sweep's add in its scan epilogue (False: the in-place add; A/B in tests / tools)
+_knobs.apply(globals(), "selective_scan_interface")      # the knobs above: tools/ and tests/ set them directly, ZIGMA_KNOBS at import
 
 
 def split_chunk_len(batch, d_inner, seqlen, reset_period=0):
@@ -52,6 +58,12 @@ def split_chunk_len(batch, d_inner, seqlen, reset_period=0):
     per = -(-seqlen // -(-768 // wgs))                            # steps per chunk that give ~768 workgroups
     chunk = min(2048, max(32, (per + 15) // 16 * 16))
     return chunk if -(-seqlen // chunk) >= 2 else 0
+
+
+def split_limits_ok(batch, d_inner, seqlen, chunk_len):
+    """The C side's limits of the sequence split (tok2_split_eligible, csrc/scan_tok2.inc): < 768 workgroups, whole-tile chunks, 2 <= n_chunks
+    <= 65535.  Every chunk split_chunk_len returns under the default knobs passes; SPLIT_MAX_WGS >= 768 (a probe setting) can break that."""
+    return chunk_len > 0 and chunk_len % 16 == 0 and batch * (d_inner // 64) < 768 and 2 <= -(-seqlen // chunk_len) <= 65535
 
 
 def _as_bgnl(M, name):
@@ -257,15 +269,6 @@ def conv_x_proj(x_half, conv_w, conv_b, x_proj_weight, perm=None, _flags=0):
     return u, x_dbl
 
 
-ACCUMULATE_IN_SCAN = True     # `v2`: the second sweep's add in its scan epilogue (False: the in-place add; A/B in tests / tools)
-DT_PROJ_IN_SPLIT = True       # sequence-split mode: dt_proj + softplus inside the split's first pass, which writes delta for the second (round 6)
-DT_PROJ_IN_SCAN = True     # dt_proj + softplus in the scan's tile prologue (MFMA) instead of a kernel of its own
-
-
-from . import _knobs  # noqa: E402
-_knobs.apply(globals(), "selective_scan_interface")      # (SPLIT_MAX_WGS, CONV_X_PROJ_MIN_POSITIONS, ... for the A/B tools)
-
-
 def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z=None):
     """limits of the in-kernel dt_proj of scan_tok2_kernel (zigma_scan_params_t.dt_x), mirroring tok2_dtp_ok() / tok2_layout_ok() /
     tok_eligible() of csrc/: bf16 / fp16, whole-sequence mode of the hot kernel (dstate == 16, seqlen % 16 == 0, d_inner % 64 == 0; reset_period a
@@ -418,6 +421,63 @@ def scan_bwd_tok(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus,
     return du, ddelta, dA, dB, dC, dD, dz, dbias
 
 
+def differentiable(*tensors):
+    """grad mode on and any of the tensors requires grad: the call must record autograd (MambaInnerTokFn)"""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def z_preactivated_eligible(batch, seqlen, d_state):
+    """scan-side limits of a gate in_proj pre-activated (ZIGMA_SCAN_Z_PREACTIVATED): the hot kernel's inference form, 16 states, whole tiles, one grid"""
+    return d_state == 16 and seqlen % 16 == 0 and batch <= 65535 and not torch.is_grad_enabled()
+
+
+class _Fresh:
+    """A contiguous (B, L, C) tensor the front has yet to allocate, as the eligibility predicates read it.  Every u and x_dbl is a new
+    allocation in xz's dtype on xz's device, so the plan judges them before anything launches."""
+    def __init__(self, like, *shape):
+        self.is_cuda, self.dtype, self.shape, self._strides = like.is_cuda, like.dtype, shape, (shape[1] * shape[2], shape[2], 1)
+    stride, numel = (lambda self, i: self._strides[i]), (lambda self: self.shape[0] * self._strides[0])
+    dim, is_contiguous, data_ptr = (lambda self: 3), (lambda self: True), (lambda self: 0)      # (the caching allocator aligns every block)
+
+
+InnerPlan = namedtuple("InnerPlan", "front dt chunk_len accumulate")
+
+
+def plan_inner(x_half, z_half, conv_w, conv_b, x_proj_w, dt_proj_w, A, delta_bias, *, perm=None, reset_period=0, z_preactivated=False, out=None,
+               add_to=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True, train=False):
+    """The one place that chooses the kernels of the Mamba inner, from mamba_inner_tok's arguments (xz as its two halves, conv_w as
+    (d_inner, width)); knobs and predicates are looked up as module globals at call time.  Returns InnerPlan:
+    front       "conv_x_proj" (one kernel) | "conv+x_proj" (conv kernel, x_proj kernel) | "conv+linear" (conv kernel, library GEMM)
+    dt          "in_scan" (dt_proj + softplus in the scan's tile prologue) | "in_split" (in the split's first pass, which writes delta)
+                | "kernel" (zigma_dt_proj_softplus_fwd) | "linear" (library GEMM; the scan adds the bias and applies softplus)
+    chunk_len   0: the scan takes the whole sequence; else the chunk length of the sequence split
+    accumulate  add_to rides in the scan's epilogue (ZIGMA_SCAN_ACCUMULATE); else an in-place add behind the scan"""
+    Bsz, L, Di = x_half.shape
+    R, N = dt_proj_w.shape[1], A.shape[1]
+    u, x_dbl = _Fresh(x_half, Bsz, L, Di), _Fresh(x_half, Bsz, L, x_proj_w.shape[0])
+    front = ("conv_x_proj" if USE_CONV_X_PROJ and conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_w, perm, reset_period)
+             else "conv+x_proj" if not train and USE_X_PROJ_KERNEL and x_proj_eligible(u, x_proj_w)
+             else "conv+linear")     # training never takes the x_proj kernel (the rule as it has always been; no measurement either way)
+    if train:                        # the training scan: whole sequence (it writes the backward's checkpoints), delta from the GEMM
+        return InnerPlan(front, "linear", 0, False)
+    chunk = split_chunk_len(Bsz, Di, L, reset_period)
+    inside = (delta_softplus and B_proj_bias is None and C_proj_bias is None
+              and (DT_PROJ_IN_SPLIT and delta_bias is not None and not z_preactivated and split_limits_ok(Bsz, Di, L, chunk) if chunk
+                   else DT_PROJ_IN_SCAN)
+              and dt_in_scan_eligible(u, x_dbl, dt_proj_w, reset_period, out if add_to is None else add_to, dstate=N, z=z_half))
+    dt = ("in_split" if chunk else "in_scan") if inside else "kernel" if delta_softplus and dt_proj_eligible(x_dbl, R, dt_proj_w) else "linear"
+    return InnerPlan(front, dt, chunk, add_to is not None and dt == "in_scan" and ACCUMULATE_IN_SCAN)
+
+
+def _run_front(plan, x_half, conv_w, conv_b, x_proj_w, perm, reset_period):
+    """u = silu(conv(x_half)) in SCAN order and x_dbl = u @ x_proj_w.T, as plan.front says"""
+    if plan.front == "conv_x_proj":
+        return conv_x_proj(x_half, conv_w, conv_b, x_proj_w, perm)      # one pass: read x, write u and x_dbl
+    u = torch.empty(x_half.shape, device=x_half.device, dtype=x_half.dtype)
+    causal_conv1d_raw(x_half.transpose(1, 2), conv_w, conv_b, True, out=u.transpose(1, 2), x_row_index=perm, reset_period=reset_period)
+    return u, (x_proj(u, x_proj_w) if plan.front == "conv+x_proj" else F.linear(u, x_proj_w))
+
+
 class MambaInnerTokFn(torch.autograd.Function):
     """Autograd form of the token-major Mamba inner (conv + SiLU -> x_proj -> dt_proj -> gated selective scan) with the
     zigzag reordering fused into the kernels' row tables in BOTH directions (no index_select / index_add / cat):
@@ -426,34 +486,24 @@ class MambaInnerTokFn(torch.autograd.Function):
     through x_row_index).  Mirrors MambaInnerFn (selective_scan_interface.py:296-434) without its out_proj."""
 
     @staticmethod
-    def forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period=0):
+    def forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan):
         # reset_period > 0 (the video temporal layers): xz is the (k, b * t, 2 Di) strided VIEW of the (b * t, k, 2 Di) projection output —
         # batch = pixel, sequence = the frames of every sample one after the other, conv window and state restart every t steps; the
         # result and d(xz) are views of (b * t, k, .) allocations, so neither direction pays a transposing copy
         Bsz, L, C2 = xz.shape
         Di, R, N = C2 // 2, dt_proj_w.shape[1], A.shape[1]
-        w = conv_w.reshape(Di, -1)
-        x_half, z_half = xz[:, :, :Di], xz[:, :, Di:]
-        if USE_CONV_X_PROJ and conv_x_proj_eligible(x_half, w, conv_b, x_proj_w, perm, reset_period):
-            u, x_dbl = conv_x_proj(x_half, w, conv_b, x_proj_w, perm)      # one pass; the backward takes u and x_dbl as saved
-        else:
-            u = torch.empty(Bsz, L, Di, device=xz.device, dtype=xz.dtype)
-            causal_conv1d_raw(x_half.transpose(1, 2), w, conv_b, True, out=u.transpose(1, 2), x_row_index=perm, reset_period=reset_period)
-            x_dbl = F.linear(u, x_proj_w)
-        delta = F.linear(x_dbl[:, :, :R], dt_proj_w)
+        u, x_dbl = _run_front(plan, xz[:, :, :Di], conv_w.reshape(Di, -1), conv_b, x_proj_w, perm, reset_period)   # the backward takes both as saved
+        delta = F.linear(x_dbl[:, :, :R], dt_proj_w)                     # (plan.dt is "linear" and plan.chunk_len 0 in training)
         Bm, Cm = x_dbl[:, :, R:R + N], x_dbl[:, :, R + N:R + 2 * N]
-        strided = not xz.is_contiguous()
         out = torch.empty(Bsz, L, Di, device=xz.device, dtype=xz.dtype)
         # (strided input = a transposed view: hand the result back as the same kind of view of an (L, Bsz, Di) allocation)
-        y = torch.empty(L, Bsz, Di, device=xz.device, dtype=xz.dtype).transpose(0, 1) if strided else torch.empty(Bsz, L, Di, device=xz.device, dtype=xz.dtype)
+        y = torch.empty(L, Bsz, Di, device=xz.device, dtype=xz.dtype).transpose(0, 1) if not xz.is_contiguous() else torch.empty_like(out)
         # the states before every 16-step tile, for the backward's reverse sweep (the token-major kernel writes them on
         # its way: 4 * Di * N * L / 16 bytes per sample; anything else leaves the buffer alone and the backward recomputes)
-        ck = None
-        if Di % 64 == 0 and N in (8, 16):
-            ck = torch.empty(Bsz, Di // 64, (L + 15) // 16, N, 64, device=xz.device, dtype=torch.float32)
+        ck = torch.empty(Bsz, Di // 64, (L + 15) // 16, N, 64, device=xz.device, dtype=torch.float32) if Di % 64 == 0 and N in (8, 16) else None
         info = []
         scan_raw(u.transpose(1, 2), delta.transpose(1, 2), A, Bm.transpose(1, 2).unsqueeze(1),
-                 Cm.transpose(1, 2).unsqueeze(1), D, z_half.transpose(1, 2), delta_bias, True,
+                 Cm.transpose(1, 2).unsqueeze(1), D, xz[:, :, Di:].transpose(1, 2), delta_bias, True,
                  out=out.transpose(1, 2), out_z=y.transpose(1, 2), z_row_index=perm, out_row_index=out_rows, checkpoints=ck,
                  info=info, reset_period=reset_period)
         if ck is not None and info[1] != 1:          # the kernel that served the call does not write checkpoints
@@ -487,16 +537,7 @@ class MambaInnerTokFn(torch.autograd.Function):
         _, d_cw, d_cb = conv_bwd_tok(x_half, conv_w, conv_b, du, True, ctx.perm, dx=dxz[:, :, :Di], reset_period=rp)
         return (dxz, d_cw.to(conv_w.dtype).reshape(conv_w.shape), None if d_cb is None else d_cb.to(conv_b.dtype),
                 d_x_w.to(x_proj_w.dtype), d_dt_w.to(dt_proj_w.dtype), dA.to(A.dtype), dD.to(D.dtype),
-                None if dbias is None else dbias.to(delta_bias.dtype), None, None, None)
-
-
-def mamba_inner_tok_train(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, *,
-                          perm=None, out_rows=None, reset_period=0):
-    """Differentiable mamba_inner_tok (same row-table and reset_period semantics; a strided xz view gets a strided result view)."""
-    if D is None or delta_bias is None:
-        raise RuntimeError("the differentiable path expects D and delta_bias (ZigMa always has them)")
-    return MambaInnerTokFn.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, perm,
-                                 perm if out_rows is None else out_rows, int(reset_period))
+                None if dbias is None else dbias.to(delta_bias.dtype), None, None, None, None)
 
 
 def selective_scan_cuda_fwd(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus):
@@ -563,84 +604,47 @@ def mamba_inner_tok(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_we
           the inverse of perm; the caller passes out_rows = inverse(perm_rev) to reproduce exactly that.
     reset_period: > 0 = every batch row is a concatenation of independent sequences of that many steps (multiple of 16):
           conv window and SSM state restart there (the video temporal layers: batch = k, seqlen = b * t on strided views).
-    z_preactivated: the z half of xz already holds silu(z) (an in_proj epilogue wrote it; inference, 16-bit, d_state 16,
-          seqlen % 16 == 0 only — the hot kernel's ZIGMA_SCAN_Z_PREACTIVATED form).
+    z_preactivated: the z half of xz already holds silu(z) (an in_proj epilogue wrote it; where z_preactivated_eligible holds).
     add_to: optional (batch, seqlen, d_inner) tensor y0 in token order (inference only): the result is y0 + y, written INTO y0 and returned — the second
-          sweep of `v2` (mamba_simple.py:335-339).  Where the in-kernel dt_proj form of the scan serves the call the add rides in its epilogue
-          (ZIGMA_SCAN_ACCUMULATE: no elementwise pass); otherwise it is an in-place add behind the scan.
+          sweep of `v2` (mamba_simple.py:335-339), in the scan's epilogue or in place behind it (plan_inner: accumulate).
     Returns y (batch, seqlen, d_inner) in token order = out_z of the reference's scan, before out_proj.
     """
     if xz.dim() != 3 or xz.stride(2) != 1:
         raise RuntimeError("xz must be (batch, seqlen, 2*d_inner) with contiguous channels")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (
-            xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias)):
+    train = differentiable(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias)
+    if train:
         if B_proj_bias is not None or C_proj_bias is not None or not delta_softplus or out is not None or z_preactivated or add_to is not None:
             raise NotImplementedError("differentiable mamba_inner_tok: no B/C projection bias, softplus on, no out= / add_to=, no pre-activated gate")
-        return mamba_inner_tok_train(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias,
-                                     perm=perm, out_rows=out_rows, reset_period=reset_period)
-    Bsz, L, C2 = xz.shape
-    Di = C2 // 2
-    R = delta_proj_weight.shape[1]
-    N = A.shape[1]
-    w = conv1d_weight.reshape(Di, -1)
-    x_half, z_half = xz[:, :, :Di], xz[:, :, Di:]
-    if USE_CONV_X_PROJ and conv_x_proj_eligible(x_half, w, conv1d_bias, x_proj_weight, perm, reset_period):
-        u, x_dbl = conv_x_proj(x_half, w, conv1d_bias, x_proj_weight, perm)   # one pass: read x, write u (scan order) and x_dbl
-    else:
-        # depthwise causal conv + SiLU over the reordered sequence; u is in SCAN order
-        u = torch.empty(Bsz, L, Di, device=xz.device, dtype=xz.dtype)
-        causal_conv1d_raw(x_half.transpose(1, 2), w, conv1d_bias, True, out=u.transpose(1, 2), x_row_index=perm,
-                          reset_period=reset_period)
-        if USE_X_PROJ_KERNEL and x_proj_eligible(u, x_proj_weight):
-            x_dbl = x_proj(u, x_proj_weight)                             # (B, L, R + 2N)   read-bound MFMA kernel
-        else:
-            x_dbl = F.linear(u, x_proj_weight)                           # (B, L, R + 2N)   GEMM
-    return _inner_tok_tail(u, x_dbl, z_half, delta_proj_weight, A, D, delta_bias, perm, out_rows, B_proj_bias, C_proj_bias,
-                           delta_softplus, out, reset_period, z_preactivated, add_to)
-
-
-def _inner_tok_tail(u, x_dbl, z_half, delta_proj_weight, A, D, delta_bias, perm, out_rows, B_proj_bias, C_proj_bias,
-                    delta_softplus, out, reset_period, z_preactivated, add_to=None):
-    """dt_proj (+ softplus) and the scan over u (scan order), x_dbl, z (token order): the part of the inner function behind x_proj"""
-    Bsz, L, Di = u.shape
-    R = delta_proj_weight.shape[1]
-    N = A.shape[1]
-    if add_to is not None and out is not None:
+        if D is None or delta_bias is None:
+            raise RuntimeError("the differentiable path expects D and delta_bias (ZigMa always has them)")
+    elif add_to is not None and out is not None:
         raise RuntimeError("mamba_inner_tok: pass out= or add_to=, not both")
-    in_scan = (DT_PROJ_IN_SCAN and delta_softplus
-               and dt_in_scan_eligible(u, x_dbl, delta_proj_weight, reset_period, out if add_to is None else add_to, dstate=N, z=z_half)
-               and B_proj_bias is None and C_proj_bias is None and not split_chunk_len(Bsz, Di, L, reset_period))
-    chunk_len_split = split_chunk_len(Bsz, Di, L, reset_period)
-    in_split = (DT_PROJ_IN_SPLIT and not in_scan and chunk_len_split and delta_softplus and B_proj_bias is None and C_proj_bias is None and delta_bias is not None
-                and not z_preactivated and u.dtype == z_half.dtype and dt_in_scan_eligible(u, x_dbl, delta_proj_weight, reset_period, out if add_to is None else add_to, dstate=N, z=z_half)
-                and Bsz * (Di // 64) < 768 and chunk_len_split % 16 == 0 and -(-L // chunk_len_split) >= 2)
-    if in_scan:                      # dt_proj + bias + softplus inside the scan kernel's tile prologue: delta is never materialised
-        delta = None
-    elif in_split:                   # sequence split: the first pass forms delta and writes it into this workspace for the second (no dt_proj kernel)
+    Bsz, L, C2 = xz.shape
+    Di, R, N = C2 // 2, delta_proj_weight.shape[1], A.shape[1]
+    w, x_half, z_half = conv1d_weight.reshape(Di, -1), xz[:, :, :Di], xz[:, :, Di:]
+    plan = plan_inner(x_half, z_half, w, conv1d_bias, x_proj_weight, delta_proj_weight, A, delta_bias, perm=perm, reset_period=reset_period,
+                      z_preactivated=z_preactivated, out=out, add_to=add_to, B_proj_bias=B_proj_bias, C_proj_bias=C_proj_bias,
+                      delta_softplus=delta_softplus, train=train)
+    out_rows = perm if out_rows is None else out_rows
+    if train:
+        return MambaInnerTokFn.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, perm, out_rows,
+                                     int(reset_period), plan)
+    u, x_dbl = _run_front(plan, x_half, w, conv1d_bias, x_proj_weight, perm, reset_period)
+    delta = None                     # "in_scan": dt_proj + bias + softplus inside the scan kernel's tile prologue, delta never exists
+    if plan.dt == "in_split":        # the split's first pass forms delta and writes it into this workspace for the second
         delta = torch.empty(Bsz, L, Di, device=u.device, dtype=u.dtype)
-    elif delta_softplus and dt_proj_eligible(x_dbl, R, delta_proj_weight):   # K = dt_rank GEMM + bias + softplus in one write-bound MFMA kernel; scan skips its softplus
+    elif plan.dt == "kernel":        # K = dt_rank GEMM + bias + softplus in one write-bound MFMA kernel; the scan skips its softplus
         delta = dt_proj_softplus(x_dbl, R, delta_proj_weight, delta_bias, True)
         delta_bias, delta_softplus = None, False
-    else:
-        delta = F.linear(x_dbl[:, :, :R], delta_proj_weight)         # (B, L, Di)       GEMM
-    Bm, Cm = x_dbl[:, :, R:R + N], x_dbl[:, :, R + N:R + 2 * N]
-    if B_proj_bias is not None:
-        Bm = Bm + B_proj_bias.to(Bm.dtype)
-    if C_proj_bias is not None:
-        Cm = Cm + C_proj_bias.to(Cm.dtype)
-    acc = add_to is not None and in_scan and ACCUMULATE_IN_SCAN          # the scan's epilogue adds to add_to; else an in-place add behind it
-    y = add_to if acc else out if out is not None else torch.empty(Bsz, L, Di, device=u.device, dtype=u.dtype)
-    # few workgroups (small batch, or long sequences of few samples): hand the kernel a carry buffer and a chunk length so
-    # that it splits the sequence over ~768 workgroups (3 per CU): chunk-local states -> combine -> seeded second pass
-    xc, chunk_len = None, split_chunk_len(Bsz, Di, L, reset_period)
-    if chunk_len:
-        xc = torch.empty(Bsz, Di, -(-L // chunk_len), 2 * N, device=u.device, dtype=torch.float32)
-    else:
-        chunk_len = 2048
-    dt_inside = in_scan or in_split
-    scan_raw(u.transpose(1, 2), None if in_scan else delta.transpose(1, 2), A, Bm.transpose(1, 2).unsqueeze(1),
+    elif plan.dt == "linear":
+        delta = F.linear(x_dbl[:, :, :R], delta_proj_weight)
+    Bm, Cm = (M if b is None else M + b.to(M.dtype) for M, b in ((x_dbl[:, :, R:R + N], B_proj_bias), (x_dbl[:, :, R + N:R + 2 * N], C_proj_bias)))
+    dt_inside = plan.dt in ("in_scan", "in_split")
+    y = add_to if plan.accumulate else out if out is not None else torch.empty(Bsz, L, Di, device=u.device, dtype=u.dtype)
+    xc = torch.empty(Bsz, Di, -(-L // plan.chunk_len), 2 * N, device=u.device, dtype=torch.float32) if plan.chunk_len else None   # split carries
+    scan_raw(u.transpose(1, 2), None if delta is None else delta.transpose(1, 2), A, Bm.transpose(1, 2).unsqueeze(1),
              Cm.transpose(1, 2).unsqueeze(1), D, z_half.transpose(1, 2), delta_bias, delta_softplus,
-             out_z=y.transpose(1, 2), z_row_index=perm, out_row_index=perm if out_rows is None else out_rows,
-             want_out=False, x=xc, reset_period=reset_period, chunk_len=chunk_len, z_preactivated=z_preactivated,
-             dt_x=x_dbl if dt_inside else None, dt_w=delta_proj_weight if dt_inside else None, accumulate=acc)
-    return y if (add_to is None or acc) else add_to.add_(y)
+             out_z=y.transpose(1, 2), z_row_index=perm, out_row_index=out_rows, want_out=False, x=xc, reset_period=reset_period,
+             chunk_len=plan.chunk_len or 2048, z_preactivated=z_preactivated, dt_x=x_dbl if dt_inside else None,
+             dt_w=delta_proj_weight if dt_inside else None, accumulate=plan.accumulate)
+    return y if (add_to is None or plan.accumulate) else add_to.add_(y)
