@@ -92,7 +92,7 @@ typedef struct zigma_scan_params {
     int32_t io_dtype;   /* zigma_dtype_t of u, delta, z, out, out_z                                */
     int32_t bc_dtype;   /* zigma_dtype_t of VARIABLE B / C (reference: == io_dtype)               */
     int32_t chunk_len;  /* carry spacing for x; 0 -> 2048 (reference: selective_scan.cpp:307)      */
-    int32_t flags;      /* 0 or ZIGMA_SCAN_Z_PREACTIVATED (+ ZIGMA_SCAN_PROBE_* bits; others must be 0)      */
+    int32_t flags;      /* 0, ZIGMA_SCAN_Z_PREACTIVATED, ZIGMA_SCAN_ACCUMULATE (+ ZIGMA_SCAN_PROBE_* bits; others must be 0) */
 
     int64_t u_batch_stride, u_d_stride, u_l_stride;
     int64_t delta_batch_stride, delta_d_stride, delta_l_stride;

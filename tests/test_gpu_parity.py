@@ -672,7 +672,7 @@ def test_dt_proj_in_kernel_with_reset_period(T, nseq, K, io, monkeypatch):
 
 
 def test_scan_dt_in_kernel_limits():
-    """What the in-kernel dt_proj (zigma_scan_params_t.dt_x) refuses — the limits tok2_dtp_ok() states, each hit on its own: with dt_x
+    """What the in-kernel dt_proj (zigma_scan_params_t.dt_x) refuses — the limits plan_scan() states (csrc/scan_plan.h), each hit on its own: with dt_x
     set no other kernel serves the call, so the C side answers ZIGMA_ERR_UNSUPPORTED and the caller has to keep the dt_proj kernel."""
     from zigma_amd.selective_scan_interface import dt_in_scan_eligible, scan_raw
     Bsz, L, Di, R, Nst = 1, 32, 64, 40, 16
@@ -1473,3 +1473,24 @@ def test_batch_beyond_the_grid_limit_runs_in_slices():
                               xd[s_][:, :, Nst:].transpose(1, 2).unsqueeze(1), D, z[s_].transpose(1, 2), None, False, want_out=False)[1]
     y = run(slice(None))
     assert torch.equal(y[sel], run(sel))
+
+
+@pytest.mark.parametrize("name", sorted(__import__("scan_plan_cases").CASES))
+def test_scan_dispatch_case_table(name):
+    """every case of the dispatch table (tests/scan_plan_cases.py) through zigma_selective_scan_fwd: status, info, last kernel"""
+    import ctypes
+    import scan_plan_cases
+    from zigma_amd import _lib
+    case, want = scan_plan_cases.CASES[name]
+
+    def launch(P):
+        before = _lib.last_kernel()
+        rc = _lib.lib().zigma_selective_scan_fwd(ctypes.byref(P), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        return rc, (P.info[0], P.info[1]), before, _lib.last_kernel()
+    rc, info, before, after = scan_plan_cases.call(case, DEV, launch)
+    assert rc == want.status
+    if want.family is None:
+        assert info == (0, 0) and after == before          # nothing reported
+    else:
+        assert info == want.info and after == want.kernel

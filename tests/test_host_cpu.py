@@ -594,16 +594,55 @@ def test_sequence_split_policy():
         assert c % 16 == 0 and c >= 32 and -(-1024 // c) >= 2
 
 
-def _tok2_split_eligible(batch, d_inner, seqlen, chunk_len):
-    """the shape part of tok2_split_eligible() (zigma_amd/csrc/scan_tok2.inc), restated for the sweep below"""
-    chunk_len = chunk_len if chunk_len > 0 else 2048
-    n_chunks = (seqlen + chunk_len - 1) // chunk_len
-    return chunk_len % 16 == 0 and 2 <= n_chunks <= 65535 and (d_inner // 64) * batch < 768
+_PLAN_DRIVER = r"""
+#include "scan_plan.h"
+using namespace zigma;
+// what the library reports for a call: the plan, or for a sliced batch the plan of the slice that runs last
+extern "C" int plan(const zigma_scan_params_t *p, int *fields, const char **kernel) {
+    const ScanPlan top = plan_scan(*p);
+    ScanPlan s = top;
+    for (int b0 = 0; top.slice && b0 < p->batch && (b0 == 0 || s.family); b0 += top.slice) s = plan_scan(batch_slice(*p, b0, top.slice));
+    fields[0] = s.status; fields[1] = s.family; fields[2] = s.info1;
+    *kernel = s.kernel;
+    return s.status;
+}
+extern "C" int split_ok(const zigma_scan_params_t *p) { return tok2_split_ok(*p); }
+"""
 
 
-def test_split_chunks_pass_the_c_side_split_limits(monkeypatch):
+@pytest.fixture(scope="module")
+def scan_plan():
+    """plan_scan() of zigma_amd/csrc/scan_plan.h compiled on its own with g++ (no HIP): plan(params) -> status, family, info1, kernel;
+    split_ok(params)"""
+    from zigma_amd import _lib
+    with tempfile.TemporaryDirectory() as d:
+        src, so = os.path.join(d, "plan.cpp"), os.path.join(d, "libplan.so")
+        open(src, "w").write(_PLAN_DRIVER)
+        subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
+                        "-I", os.path.join(ROOT, "zigma_amd", "csrc"), src, "-o", so], check=True)
+        L = ctypes.CDLL(so)
+    L.plan.argtypes = [ctypes.POINTER(_lib.ScanParams), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
+    L.split_ok.argtypes = [ctypes.POINTER(_lib.ScanParams)]
+    names = ("status", "family", "info1")
+
+    def plan(P):
+        f, k = (ctypes.c_int * len(names))(), ctypes.c_char_p()
+        L.plan(ctypes.byref(P), f, ctypes.byref(k))
+        return dict(zip(names, f), kernel=k.value.decode() if k.value else None)
+    plan.split_ok = lambda P: bool(L.split_ok(ctypes.byref(P)))
+    return plan
+
+
+def _split_ok(scan_plan, batch, d_inner, seqlen, chunk_len):
+    from zigma_amd import _lib
+    P = _lib.ScanParams()
+    P.batch, P.dim, P.seqlen, P.chunk_len = batch, d_inner, seqlen, chunk_len
+    return scan_plan.split_ok(P)
+
+
+def test_split_chunks_pass_the_c_side_split_limits(monkeypatch, scan_plan):
     """split_chunk_len under the default knobs only returns chunks the C side's sequence split accepts, and split_limits_ok refuses
-    exactly what tok2_split_eligible refuses — including the chunks a raised SPLIT_MAX_WGS produces and more than 65535 chunks."""
+    exactly what tok2_split_ok (scan_plan.h, compiled) refuses — including the chunks a raised SPLIT_MAX_WGS produces and more than 65535 chunks."""
     import zigma_amd.selective_scan_interface as ssi
     Ls = (16, 32, 48, 128, 240, 256, 272, 1008, 1024, 1040, 2048, 4080, 4096, 4112, 8192, 16384, 65552, 1 << 20)
     Dis = (64, 128, 640, 1280, 1536, 3072, 4096)
@@ -619,14 +658,71 @@ def test_split_chunks_pass_the_c_side_split_limits(monkeypatch):
         return hits
     hits = sweep()
     assert len(hits) > 1000 and all(ok for *_, ok in hits)
-    assert all(_tok2_split_eligible(b, di, L, c) for b, di, L, c, _ in hits)
+    assert all(_split_ok(scan_plan, b, di, L, c) for b, di, L, c, _ in hits)
     monkeypatch.setattr(ssi, "SPLIT_MAX_WGS", 1024)
     hits = sweep()
     refused = [h for h in hits if not h[4]]
     assert refused and all(b * (di // 64) >= 768 for b, di, *_ in refused)
-    assert all(ok == _tok2_split_eligible(b, di, L, c) for b, di, L, c, ok in hits)
+    assert all(ok == _split_ok(scan_plan, b, di, L, c) for b, di, L, c, ok in hits)
     assert ssi.split_limits_ok(1, 64, 16 * 65535, 16) and not ssi.split_limits_ok(1, 64, 16 * 65536, 16)
     assert not ssi.split_limits_ok(1, 64, 1024, 24) and not ssi.split_limits_ok(1, 64, 1024, 1024) and not ssi.split_limits_ok(1, 64, 1024, 0)
+
+
+@pytest.mark.parametrize("name", sorted(__import__("scan_plan_cases").CASES))
+def test_scan_plan_case_table(name, scan_plan):
+    """plan_scan() (compiled) on the parameter block scan_raw builds for every case of the table: status, family, info, last kernel"""
+    import scan_plan_cases
+    case, want = scan_plan_cases.CASES[name]
+    got = scan_plan_cases.call(case, "cpu", scan_plan)
+    family = got["family"] or None
+    assert (got["status"], family, (family, got["info1"]) if family else None, got["kernel"]) == tuple(want)
+
+
+class _Dev:
+    """a contiguous GPU tensor as the eligibility predicates read it (shape, strides, dtype, address); nothing is allocated"""
+    def __init__(self, dtype, *shape, ptr=1 << 20):
+        self.is_cuda, self.dtype, self.shape, self._ptr = True, dtype, shape, ptr
+        self._strides = tuple(math.prod(shape[i + 1:]) for i in range(len(shape)))
+    stride, dim, data_ptr = (lambda self, i: self._strides[i]), (lambda self: len(self.shape)), (lambda self: self._ptr)
+
+
+def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
+    """dt_in_scan_eligible() (Python) says yes exactly where plan_scan() takes the in-kernel dt_proj form, for the parameter block
+    mamba_inner_tok passes: u and x_dbl fresh contiguous rows, z the second half of xz, B / C columns of x_dbl, no delta"""
+    from zigma_amd import _lib
+    from zigma_amd.selective_scan_interface import dt_in_scan_eligible
+    seen = set()
+    for dt in (torch.bfloat16, torch.float16, torch.float32):
+        for B in (1, 65536):
+            for L in (16, 24, 1024, 1 << 19):
+                for Di in (64, 96, 1280):
+                    for R in (16, 32, 40, 64, 72):
+                        for N in (8, 16):
+                            for rp in (0, 16, 24):
+                                for off in (0, 2):
+                                    W, es = R + 2 * N, 2 if dt != torch.float32 else 4
+                                    u, x_dbl, z = _Dev(dt, B, L, Di), _Dev(dt, B, L, W, ptr=(1 << 24) + off * es), _Dev(dt, B, L, 2 * Di)
+                                    w = _Dev(dt, Di, R, ptr=1 << 28)
+                                    P = _lib.ScanParams()
+                                    P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.reset_period = B, Di, L, N, 1, rp
+                                    P.io_dtype = P.bc_dtype = {torch.bfloat16: 2, torch.float16: 1, torch.float32: 0}[dt]
+                                    P.delta_softplus, P.is_variable_B, P.is_variable_C, P.chunk_len = 1, 1, 1, 2048
+                                    for name, t, d0 in (("u", u, 0), ("z", z, 1 << 26), ("out_z", u, 1 << 27)):
+                                        setattr(P, name, t.data_ptr() + d0)
+                                        setattr(P, f"{name}_batch_stride", t.stride(0)), setattr(P, f"{name}_l_stride", t.stride(1))
+                                        setattr(P, f"{name}_d_stride", 1)
+                                    for name, col in (("B", R), ("C", R + N)):
+                                        setattr(P, name, x_dbl.data_ptr() + col * es)
+                                        setattr(P, f"{name}_batch_stride", x_dbl.stride(0)), setattr(P, f"{name}_l_stride", x_dbl.stride(1))
+                                        setattr(P, f"{name}_dstate_stride", 1)
+                                    P.A, P.A_d_stride, P.A_dstate_stride = 1 << 29, N, 1
+                                    P.dt_x, P.dt_w, P.dt_rank = x_dbl.data_ptr(), w.data_ptr(), R
+                                    P.dt_x_batch_stride, P.dt_x_l_stride, P.dt_w_row_stride = x_dbl.stride(0), x_dbl.stride(1), w.stride(0)
+                                    pl = scan_plan(P)
+                                    planned = pl["status"] == 0 and pl["kernel"] is not None and "dtproj" in pl["kernel"]
+                                    assert dt_in_scan_eligible(u, x_dbl, w, rp, None, dstate=N, z=z) == planned, (dt, B, L, Di, R, N, rp, off, pl)
+                                    seen.add(planned)
+    assert seen == {True, False}
 
 
 def test_inner_plan_rules(monkeypatch):

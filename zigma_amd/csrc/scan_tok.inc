@@ -17,7 +17,10 @@
 // Rows (u, delta, z, out) are addressed as  buffer descriptor + fixed per-lane offset + scalar row offset, so
 // every piece of row arithmetic — including the zigzag row tables — runs on the scalar unit.
 #pragma once
+#include <type_traits>
+
 #include "scan_helpers.h"
+#include "scan_plan.h"
 
 namespace zigma {
 
@@ -301,44 +304,38 @@ __global__ void zigma_scan_combine_kernel(float *x, int64_t rows, int n_chunks, 
     }
 }
 
-template <typename IO, int NW>
-static int launch_tok_nw(const zigma_scan_params_t &p, hipStream_t stream) {
-    const bool even = p.seqlen % kLT == 0, has_z = p.z != nullptr, has_out = p.out != nullptr;
-    const int chunk_len = p.chunk_len > 0 ? p.chunk_len : 2048;
-    const int n_chunks = (p.seqlen + chunk_len - 1) / chunk_len;
-    // sequence split: only when the plain grid cannot fill the chip and the caller provided x (the carries ARE x)
-    const int64_t wgs = static_cast<int64_t>(p.dim / 64) * p.batch;
-    const bool split = p.x != nullptr && n_chunks >= 2 && wgs < 768;
-    dim3 grid(p.dim / 64, p.batch, split ? n_chunks : 1), block(64 * NW);
-#define ZIGMA_TOK(E_, Z_, O_, S_, PP_) hipLaunchKernelGGL((scan_tok_kernel<IO, NW, E_, Z_, O_, S_>), grid, block, 0, stream, PP_)
-    zigma_scan_params_t q = p;
-    if (split) {
-        if (even) ZIGMA_TOK(true, false, false, true, p); else ZIGMA_TOK(false, false, false, true, p);
-        const int64_t rows = static_cast<int64_t>(p.batch) * p.dim;
-        hipLaunchKernelGGL(zigma_scan_combine_kernel<IO>, dim3(static_cast<unsigned>((rows * p.dstate + 255) / 256)), dim3(256), 0, stream,
-                           reinterpret_cast<float *>(p.x), rows, n_chunks, p.dstate);
-        q.flags |= kFlagInitFromX;
-    }
-    if (even) {
-        if (has_z && has_out) ZIGMA_TOK(true, true, true, false, q);
-        else if (has_z) ZIGMA_TOK(true, true, false, false, q);
-        else ZIGMA_TOK(true, false, true, false, q);
-    } else {
-        if (has_z && has_out) ZIGMA_TOK(false, true, true, false, q);
-        else if (has_z) ZIGMA_TOK(false, true, false, false, q);
-        else ZIGMA_TOK(false, false, true, false, q);
-    }
-#undef ZIGMA_TOK
-    return check_launch();
+// calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...) for the run-time switches b0, b1, ...: one instantiation per combination
+template <typename F> static void with_flags(F &&f) { f(); }
+template <typename F, typename... R> static void with_flags(F &&f, bool b, R... rest) {
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 template <typename IO>
-static int launch_tok_io(const zigma_scan_params_t &p, hipStream_t stream) {
-    if (p.flags & ZIGMA_SCAN_Z_PREACTIVATED) return ZIGMA_ERR_UNSUPPORTED;      // scan_tok2_kernel only
-    if (p.info) { p.info[0] = ZIGMA_SCAN_KERNEL_TOK; p.info[1] = (p.checkpoints && p.z && p.out) ? 1 : 0; }
-    if (p.dstate == 16) { set_last_kernel("scan_tok_n16"); return launch_tok_nw<IO, 4>(p, stream); }
-    set_last_kernel("scan_tok_n8");
-    return launch_tok_nw<IO, 2>(p, stream);
+static void launch_combine(const zigma_scan_params_t &p, int n_chunks, hipStream_t stream) {
+    const int64_t rows = static_cast<int64_t>(p.batch) * p.dim;
+    hipLaunchKernelGGL(zigma_scan_combine_kernel<IO>, dim3(static_cast<unsigned>((rows * p.dstate + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<float *>(p.x), rows, n_chunks, p.dstate);
+}
+
+// sequence split: chunk-local carries (pass 1) -> running prefixes -> every chunk from its prefix (pass 2, which writes the outputs)
+template <typename IO>
+static int launch_tok(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream) {
+    const bool split = plan.form == kScanSplit;
+    with_flags([&](auto N4, auto E) {
+        constexpr int NW = N4 ? 4 : 2;
+        const dim3 grid(p.dim / 64, p.batch, split ? plan.n_chunks : 1), block(64 * NW);
+        zigma_scan_params_t q = p;
+        if (split) {
+            hipLaunchKernelGGL((scan_tok_kernel<IO, NW, E, false, false, true>), grid, block, 0, stream, p);
+            launch_combine<IO>(p, plan.n_chunks, stream);
+            q.flags |= kFlagInitFromX;
+        }
+        if (plan.z && plan.out) hipLaunchKernelGGL((scan_tok_kernel<IO, NW, E, true, true, false>), grid, block, 0, stream, q);
+        else if (plan.z) hipLaunchKernelGGL((scan_tok_kernel<IO, NW, E, true, false, false>), grid, block, 0, stream, q);
+        else hipLaunchKernelGGL((scan_tok_kernel<IO, NW, E, false, true, false>), grid, block, 0, stream, q);
+    }, plan.nw == 4, plan.even);
+    return check_launch();
 }
 
 }  // namespace zigma

@@ -539,130 +539,31 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
     }
 }
 
-// eligibility beyond tok_eligible(): what the kernel above assumes
-static bool tok2_layout_ok(const zigma_scan_params_t &p) {
-    if (p.dstate != 16 || p.seqlen % 16 != 0 || !p.z) return false;
-    if (p.out && (p.flags & ZIGMA_SCAN_Z_PREACTIVATED)) return false;           // the training form is not instantiated with a pre-activated gate
-#ifdef ZIGMA_SCAN_PROBES
-    if (p.checkpoints && !p.out && !(p.flags & 0x1000)) return false;           // (0x1000: the buffer carries the probe's time stamps)
-#elif defined(ZIGMA_DTP_DEBUG)
-    if (p.flags & 0x7000) return false;
-#else
-    if ((p.checkpoints && !p.out) || (p.flags & 0x7000)) return false;
-#endif
-    if (p.out && (static_cast<int64_t>(p.out_l_stride) * 2 > 0x7fffffff)) return false;
-    if (p.io_dtype == ZIGMA_F32) return false;
-    if (p.B_dstate_stride != 1 || p.C_dstate_stride != 1 || (p.B_l_stride & 1) || (p.C_l_stride & 1)) return false;
-    if ((reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C)) & 3) return false;
-    if ((p.B_batch_stride | p.C_batch_stride) & 1) return false;
-    if ((p.z_row_index == nullptr) != (p.out_row_index == nullptr)) return false;
-    if (static_cast<int64_t>(p.batch) * (p.dim / 64) > 0x7fffffff) return false;
-    return true;
-}
-static bool tok2_eligible(const zigma_scan_params_t &p) { return tok2_layout_ok(p) && !p.x; }
-// ZIGMA_SCAN_ACCUMULATE is served by the in-kernel dt_proj form only (every other path refuses the flag: see zigma_selective_scan_fwd)
-// dt_proj inside the kernel: the whole-sequence inference call (round 6: also with reset_period — the video temporal layers) on 16-bit operands with aligned x_dbl / W_dt rows, 32 <= dt_rank <= 64
-static bool tok2_dtp_ok(const zigma_scan_params_t &p) {
-#ifdef ZIGMA_DTP_DEBUG
-    if (p.dt_x && p.dt_w && tok2_layout_ok(p)) return true;
-#endif
-    return p.dt_x && p.dt_w && tok2_eligible(p) && !p.out && !p.checkpoints && p.reset_period >= 0 && p.reset_period % 16 == 0 && (p.io_dtype == ZIGMA_BF16 || p.io_dtype == ZIGMA_F16) &&
-           p.delta_softplus && p.dt_rank >= 32 && p.dt_rank <= 64 && p.dt_rank % 8 == 0 &&
-           p.dt_x_l_stride % 8 == 0 && p.dt_x_batch_stride % 8 == 0 && p.dt_w_row_stride % 8 == 0 && p.dt_x_l_stride >= 64 &&
-           reinterpret_cast<uintptr_t>(p.dt_x) % 16 == 0 && reinterpret_cast<uintptr_t>(p.dt_w) % 16 == 0 && static_cast<int64_t>(p.seqlen) * p.dt_x_l_stride * 2 < 0x7fffffff;
-}
-// sequence split WITH the in-kernel dt_proj (round 6): the first pass forms delta and writes it into the caller's `delta` workspace for the second
-static bool tok2_dtp_split_ok(const zigma_scan_params_t &p);
-// sequence split: the caller provided the carry tensor x, the chunks are whole tiles, and the plain grid cannot fill the chip
-static bool tok2_split_eligible(const zigma_scan_params_t &p) {
-    if (!tok2_layout_ok(p) || !p.x || p.out || p.reset_period > 0) return false;
-    const int chunk_len = p.chunk_len > 0 ? p.chunk_len : 2048;
-    const int n_chunks = (p.seqlen + chunk_len - 1) / chunk_len;
-    return chunk_len % 16 == 0 && n_chunks >= 2 && n_chunks <= 65535 && static_cast<int64_t>(p.dim / 64) * p.batch < 768;
-}
-
-static bool tok2_dtp_split_ok(const zigma_scan_params_t &p) {
-    return p.dt_x && p.dt_w && p.delta && p.delta != p.u && tok2_split_eligible(p) && !p.checkpoints && !(p.flags & (ZIGMA_SCAN_Z_PREACTIVATED | ZIGMA_SCAN_ACCUMULATE)) &&
-           (p.io_dtype == ZIGMA_BF16 || p.io_dtype == ZIGMA_F16) && p.delta_softplus && p.dt_rank >= 32 && p.dt_rank <= 64 && p.dt_rank % 8 == 0 &&
-           p.dt_x_l_stride % 8 == 0 && p.dt_x_batch_stride % 8 == 0 && p.dt_w_row_stride % 8 == 0 && p.dt_x_l_stride >= 64 &&
-           reinterpret_cast<uintptr_t>(p.dt_x) % 16 == 0 && reinterpret_cast<uintptr_t>(p.dt_w) % 16 == 0 && static_cast<int64_t>(p.seqlen) * p.dt_x_l_stride * 2 < 0x7fffffff;
-}
-
-template <typename IO, int MODE>
-static void launch_tok2_mode(const zigma_scan_params_t &p, hipStream_t stream, dim3 grid) {
-    const dim3 block(256);
-    const int n_slabs = p.dim / 64;
-    const bool sp = p.delta_softplus != 0 || p.delta_bias != nullptr, tab = p.z_row_index != nullptr;
-    const bool zact = (p.flags & ZIGMA_SCAN_Z_PREACTIVATED) != 0;
-#define ZIGMA_TOK2(S_, T_, Z_) hipLaunchKernelGGL((scan_tok2_kernel<IO, S_, T_, Z_, MODE>), grid, block, 0, stream, p, n_slabs)
-    if constexpr (MODE == 1) {            // no gate, no tables in the state-only pass
-        if (sp) ZIGMA_TOK2(true, false, false); else ZIGMA_TOK2(false, false, false);
-    } else if (MODE == 0 && p.out) {      // training forward: ungated y as well (+ checkpoints)
-#define ZIGMA_TOK2_OUT(S_, T_) hipLaunchKernelGGL((scan_tok2_kernel<IO, S_, T_, false, 0, true>), grid, block, 0, stream, p, n_slabs)
-        if (sp) { if (tab) ZIGMA_TOK2_OUT(true, true); else ZIGMA_TOK2_OUT(true, false); }
-        else { if (tab) ZIGMA_TOK2_OUT(false, true); else ZIGMA_TOK2_OUT(false, false); }
-#undef ZIGMA_TOK2_OUT
-    } else {
-        if (sp) {
-            if (tab) { if (zact) ZIGMA_TOK2(true, true, true); else ZIGMA_TOK2(true, true, false); }
-            else { if (zact) ZIGMA_TOK2(true, false, true); else ZIGMA_TOK2(true, false, false); }
-        } else {
-            if (tab) { if (zact) ZIGMA_TOK2(false, true, true); else ZIGMA_TOK2(false, true, false); }
-            else { if (zact) ZIGMA_TOK2(false, false, true); else ZIGMA_TOK2(false, false, false); }
-        }
-    }
-#undef ZIGMA_TOK2
-}
-
+// forms and switches: plan_scan() (scan_plan.h)
 template <typename IO>
-static int launch_tok2(const zigma_scan_params_t &p, hipStream_t stream) {
-    const unsigned wgs = static_cast<unsigned>(static_cast<int64_t>(p.batch) * (p.dim / 64));
-    if (p.x) {                                            // tok2_split_eligible(): chunk-local states -> combine -> seeded second pass
-        const int chunk_len = p.chunk_len > 0 ? p.chunk_len : 2048;
-        const int n_chunks = (p.seqlen + chunk_len - 1) / chunk_len;
-        const int64_t rows = static_cast<int64_t>(p.batch) * p.dim;
-        if (p.dt_x) {                                     // tok2_dtp_split_ok(): the first pass forms delta (MFMA + softplus) and writes it; the second reads it as before
-            if constexpr (sizeof(typename IO::raw) == 2) {
-                hipLaunchKernelGGL((scan_tok2_kernel<IO, true, false, false, 1, false, true>), dim3(wgs, n_chunks), dim3(256), 0, stream, p, p.dim / 64);
-                hipLaunchKernelGGL(zigma_scan_combine_kernel<IO>, dim3(static_cast<unsigned>((rows * p.dstate + 255) / 256)), dim3(256), 0, stream,
-                                   reinterpret_cast<float *>(p.x), rows, n_chunks, p.dstate);
-                zigma_scan_params_t q = p;                // (delta now holds softplus(dt_proj + bias))
-                q.dt_x = nullptr; q.dt_w = nullptr; q.delta_bias = nullptr; q.delta_softplus = 0;
-                launch_tok2_mode<IO, 2>(q, stream, dim3(wgs, n_chunks));
-                set_last_kernel("scan_tok2_n16_split_dtproj");
-                if (p.info) { p.info[0] = ZIGMA_SCAN_KERNEL_TOK2; p.info[1] = 0; }
-                return check_launch();
-            }
-            return ZIGMA_ERR_DTYPE;
+static int launch_tok2(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream) {
+    const bool split = plan.form == kScanSplit || plan.form == kScanSplitDtp;
+    const dim3 grid(static_cast<unsigned>(scan_slabs(p)), split ? plan.n_chunks : 1), block(256);
+    auto run = [&](void (*kernel)(zigma_scan_params_t, int), const zigma_scan_params_t &q) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, q, p.dim / 64);
+    };
+    if (plan.form == kScanDtp) {
+        with_flags([&](auto T, auto Z, auto R6, auto A) { run(scan_tok2_kernel<IO, true, T, Z, 0, false, true, R6, A>, p); },
+                   plan.tab, plan.zact, plan.r6, plan.acc);
+    } else if (!split) {
+        if (plan.out) with_flags([&](auto S, auto T) { run(scan_tok2_kernel<IO, S, T, false, 0, true>, p); }, plan.sp, plan.tab);
+        else with_flags([&](auto S, auto T, auto Z) { run(scan_tok2_kernel<IO, S, T, Z, 0>, p); }, plan.sp, plan.tab, plan.zact);
+    } else {            // chunk-local states (no gate, no tables) -> running prefixes -> the seeded second pass
+        zigma_scan_params_t q = p;
+        if (plan.form == kScanSplitDtp) {       // the first pass forms delta (MFMA + softplus) and writes it; the second reads it as a plain delta
+            run(scan_tok2_kernel<IO, true, false, false, 1, false, true>, p);
+            q.dt_x = nullptr; q.dt_w = nullptr; q.delta_bias = nullptr; q.delta_softplus = 0;
+        } else {
+            with_flags([&](auto S) { run(scan_tok2_kernel<IO, S, false, false, 1>, p); }, plan.sp);
         }
-        launch_tok2_mode<IO, 1>(p, stream, dim3(wgs, n_chunks));
-        hipLaunchKernelGGL(zigma_scan_combine_kernel<IO>, dim3(static_cast<unsigned>((rows * p.dstate + 255) / 256)), dim3(256), 0, stream,
-                           reinterpret_cast<float *>(p.x), rows, n_chunks, p.dstate);
-        launch_tok2_mode<IO, 2>(p, stream, dim3(wgs, n_chunks));
-    } else if (p.dt_x) {                                  // tok2_dtp_ok(): dt_proj + softplus inside the kernel (16-bit I/O)
-        if constexpr (sizeof(typename IO::raw) == 2) {
-            const int n_slabs = p.dim / 64;
-            const bool zact = (p.flags & ZIGMA_SCAN_Z_PREACTIVATED) != 0;
-            // six resident workgroups per CU where that saves a round of the grid (256 CUs: rounds of 1280 or of 1536 workgroups); probe bit 10 pins five
-            const bool r6 = (wgs + 1535) / 1536 < (wgs + 1279) / 1280 && !((p.flags >> ZIGMA_SCAN_PROBE_R5_SHIFT) & 1);
-            const bool acc = (p.flags & ZIGMA_SCAN_ACCUMULATE) != 0;
-#define ZIGMA_TOK2_DTP_(T_, Z_, A_) do { if (r6) hipLaunchKernelGGL((scan_tok2_kernel<IO, true, T_, Z_, 0, false, true, true, A_>), dim3(wgs), dim3(256), 0, stream, p, n_slabs); \
-                                         else hipLaunchKernelGGL((scan_tok2_kernel<IO, true, T_, Z_, 0, false, true, false, A_>), dim3(wgs), dim3(256), 0, stream, p, n_slabs); } while (0)
-#define ZIGMA_TOK2_DTP(T_, Z_) do { if (acc) ZIGMA_TOK2_DTP_(T_, Z_, true); else ZIGMA_TOK2_DTP_(T_, Z_, false); } while (0)
-            if (p.z_row_index) { if (zact) ZIGMA_TOK2_DTP(true, true); else ZIGMA_TOK2_DTP(true, false); }
-            else { if (zact) ZIGMA_TOK2_DTP(false, true); else ZIGMA_TOK2_DTP(false, false); }
-#undef ZIGMA_TOK2_DTP
-#undef ZIGMA_TOK2_DTP_
-            set_last_kernel(acc ? (r6 ? "scan_tok2_n16_dtproj_r6_acc" : "scan_tok2_n16_dtproj_acc") : r6 ? "scan_tok2_n16_dtproj_r6" : "scan_tok2_n16_dtproj");
-            if (p.info) { p.info[0] = ZIGMA_SCAN_KERNEL_TOK2; p.info[1] = 0; }
-            return check_launch();
-        }
-        return ZIGMA_ERR_DTYPE;
-    } else {
-        launch_tok2_mode<IO, 0>(p, stream, dim3(wgs));
+        launch_combine<IO>(p, plan.n_chunks, stream);
+        with_flags([&](auto S, auto T, auto Z) { run(scan_tok2_kernel<IO, S, T, Z, 2>, q); }, plan.sp, plan.tab, plan.zact);
     }
-    set_last_kernel("scan_tok2_n16");
-    if (p.info) { p.info[0] = ZIGMA_SCAN_KERNEL_TOK2; p.info[1] = (p.checkpoints && p.out && !(p.flags & 0x1000)) ? 1 : 0; }
     return check_launch();
 }
 

@@ -3,12 +3,7 @@
 #include "scan_tok2.inc"
 
 namespace zigma {
-int launch_scan_tok_f16(const zigma_scan_params_t &p, hipStream_t stream) {
-    if ((tok2_eligible(p) || tok2_split_eligible(p)) && !(p.flags & ZIGMA_SCAN_PROBE_V1)) return launch_tok2<F16>(p, stream);
-    return launch_tok_io<F16>(p, stream);
-}
-int launch_scan_tok_f16_dtp(const zigma_scan_params_t &p, hipStream_t stream) {        // p.dt_x set: no other kernel serves it
-    if (!(p.x ? tok2_dtp_split_ok(p) : tok2_dtp_ok(p)) || (p.flags & ZIGMA_SCAN_PROBE_V1)) return ZIGMA_ERR_UNSUPPORTED;
-    return launch_tok2<F16>(p, stream);
+int launch_scan_tok_f16(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream) {
+    return plan.family == ZIGMA_SCAN_KERNEL_TOK2 ? launch_tok2<F16>(p, plan, stream) : launch_tok<F16>(p, plan, stream);
 }
 }  // namespace zigma

@@ -2,5 +2,5 @@
 #include "scan_tok.inc"
 
 namespace zigma {
-int launch_scan_tok_f32(const zigma_scan_params_t &p, hipStream_t stream) { return launch_tok_io<F32>(p, stream); }
+int launch_scan_tok_f32(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream) { return launch_tok<F32>(p, plan, stream); }
 }  // namespace zigma

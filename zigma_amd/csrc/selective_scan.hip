@@ -8,11 +8,15 @@
 // cross-lane combine of a parallel scan is pure overhead, and B/C would be re-read through L2 by every
 // one of the 1280 channel rows of a sample.
 //
-// Two kernels:
+// Three kernels; scan_plan.h chooses one of them, its form and its template switches for every call:
 //
-//  scan_tok_kernel   — the hot path.  Token-major operands (channel contiguous), one LANE per
-//      channel, time runs sequentially inside the lane, so there is NO scan and no cross-lane
-//      combine: per (element, state) exactly v_mul, v_exp, v_mul, v_fma, v_fmac.  A workgroup owns a
+//  scan_tok2_kernel  — the hot path (scan_tok2.inc): 16-bit I/O, dstate 16, whole 16-step tiles, gated output;
+//      also the training form, the sequence split and dt_proj inside the kernel.
+//
+//  scan_tok_kernel   — the first-generation token-major kernel (scan_tok.inc), for the rest of the token-major
+//      layout: f32, dstate 8, ragged lengths, no gate, carries without a split.  Token-major operands (channel
+//      contiguous), one LANE per channel, time runs sequentially inside the lane, so there is NO scan and no
+//      cross-lane combine: per (element, state) exactly v_mul, v_exp, v_mul, v_fma, v_fmac.  A workgroup owns a
 //      64-channel slab of one sample; its NW waves split the dstate dimension (4 states each).  The
 //      B_l / C_l values of a 4-step group sit in ONE VGPR per operand (lane -> (step, state), the same
 //      16 values in every row of 16 lanes) and reach the FMAs as DPP row_newbcast operands: no SGPR
@@ -24,6 +28,7 @@
 //  scan_generic_kernel — any strides / constant or grouped B,C / any dstate <= 256: the reference's
 //      full call surface (selective_scan.cpp:233-305).  One row per NS lanes (one lane per state),
 //      butterfly reduction for y.  Compatibility path, not tuned.
+#include "scan_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
@@ -118,59 +123,39 @@ __global__ __launch_bounds__(64) void scan_generic_kernel(const zigma_scan_param
     }
 }
 
-// token-major kernel: scan_tok.inc, instantiated per I/O element type in scan_tok_{bf16,f16,f32}.hip
-int launch_scan_tok_bf16(const zigma_scan_params_t &p, hipStream_t stream);
-int launch_scan_tok_bf16_dtp(const zigma_scan_params_t &p, hipStream_t stream);
-int launch_scan_tok_f16(const zigma_scan_params_t &p, hipStream_t stream);
-int launch_scan_tok_f16_dtp(const zigma_scan_params_t &p, hipStream_t stream);
-int launch_scan_tok_f32(const zigma_scan_params_t &p, hipStream_t stream);
+// token-major kernels: scan_tok.inc, scan_tok2.inc, one launcher per I/O element type in scan_tok_{bf16,f16,f32}.hip
+int launch_scan_tok_bf16(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream);
+int launch_scan_tok_f16(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream);
+int launch_scan_tok_f32(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream);
 
 // =================================================================================================
 // host dispatch
 // =================================================================================================
 template <typename IO, typename BCT>
-static int launch_generic(const zigma_scan_params_t &p, hipStream_t stream) {
-    const int N = p.dstate;
+static void launch_generic(const zigma_scan_params_t &p, hipStream_t stream) {
+    void (*const kernels[])(zigma_scan_params_t) = {   // NS lanes per row: dstate rounded up to a power of two, at most 64; SPL states per lane
+        scan_generic_kernel<IO, BCT, 1, 1>, scan_generic_kernel<IO, BCT, 2, 1>, scan_generic_kernel<IO, BCT, 4, 1>,
+        scan_generic_kernel<IO, BCT, 8, 1>, scan_generic_kernel<IO, BCT, 16, 1>, scan_generic_kernel<IO, BCT, 32, 1>,
+        scan_generic_kernel<IO, BCT, 64, 1>, scan_generic_kernel<IO, BCT, 64, 2>, scan_generic_kernel<IO, BCT, 64, 4>};
+    int i = 0;
+    while ((1 << i) < p.dstate) ++i;
+    const int rpw = 64 >> (i < 6 ? i : 6);    // rows per wave
     const int64_t nrows = static_cast<int64_t>(p.batch) * p.dim;
-#define ZIGMA_GEN(NS_, SPL_)                                                                           \
-    {                                                                                                  \
-        const int rpw = 64 / NS_;                                                                      \
-        dim3 grid(static_cast<unsigned>((nrows + rpw - 1) / rpw)), block(64);                          \
-        hipLaunchKernelGGL((scan_generic_kernel<IO, BCT, NS_, SPL_>), grid, block, 0, stream, p);      \
-    }
-    if (N <= 1) ZIGMA_GEN(1, 1)
-    else if (N <= 2) ZIGMA_GEN(2, 1)
-    else if (N <= 4) ZIGMA_GEN(4, 1)
-    else if (N <= 8) ZIGMA_GEN(8, 1)
-    else if (N <= 16) ZIGMA_GEN(16, 1)
-    else if (N <= 32) ZIGMA_GEN(32, 1)
-    else if (N <= 64) ZIGMA_GEN(64, 1)
-    else if (N <= 128) ZIGMA_GEN(64, 2)
-    else ZIGMA_GEN(64, 4)
-#undef ZIGMA_GEN
-    set_last_kernel("scan_generic");
-    if (p.info) { p.info[0] = ZIGMA_SCAN_KERNEL_GENERIC; p.info[1] = 0; }
-    return check_launch();
+    hipLaunchKernelGGL(kernels[i], dim3(static_cast<unsigned>((nrows + rpw - 1) / rpw)), dim3(64), 0, stream, p);
 }
 
-// token-major fast path: channels contiguous in u / delta / z / out, input-dependent B and C (any
-// strides), dstate 16 (4 waves x 4 states) or 8 (2 waves), dim a multiple of the 64-channel slab.
-static bool tok_eligible(const zigma_scan_params_t &p) {
-    if (!p.is_variable_B || !p.is_variable_C || p.n_groups != 1) return false;
-    if (p.dim % 64 != 0 || (p.dstate != 16 && p.dstate != 8)) return false;
-    if (p.u_d_stride != 1 || p.delta_d_stride != 1) return false;
-    if (p.z && (p.z_d_stride != 1 || p.out_z_d_stride != 1)) return false;
-    if (p.out && p.out_d_stride != 1) return false;
-    const int chunk_len = p.chunk_len > 0 ? p.chunk_len : 2048;
-    if (p.x && chunk_len % 16 != 0) return false;  // carries are stored at tile ends
-    if (p.bc_dtype != p.io_dtype) return false;    // instantiation set: B/C in the activation dtype
-    // in-sample offsets are 32-bit in the kernel
-    const int64_t lim = ((int64_t(1) << 31) - 1) / 4, Lm = p.seqlen;  // byte offsets, up to 4-byte elements
-    const int64_t ls[] = {p.u_l_stride, p.delta_l_stride, p.z ? p.z_l_stride : 0, p.out ? p.out_l_stride : 0,
-                          p.z ? p.out_z_l_stride : 0, p.B_l_stride, p.C_l_stride};
-    for (int64_t s : ls)
-        if (s < 0 || s * Lm > lim) return false;
-    return true;
+// one planned call: report the kernel, launch it
+static int launch(const zigma_scan_params_t &p, const ScanPlan &plan, hipStream_t stream) {
+    if (!plan.family) return plan.status;
+    set_last_kernel(plan.kernel);
+    if (p.info) { p.info[0] = plan.family; p.info[1] = plan.info1; }
+    const zigma_scan_params_t q = scan_operands(p);
+    if (plan.family == ZIGMA_SCAN_KERNEL_GENERIC) {
+        ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, { ZIGMA_DISPATCH_DTYPE(p.bc_dtype, BCT, { launch_generic<IO, BCT>(q, stream); }) })
+        return check_launch();
+    }
+    return p.io_dtype == ZIGMA_BF16 ? launch_scan_tok_bf16(q, plan, stream)
+           : p.io_dtype == ZIGMA_F16 ? launch_scan_tok_f16(q, plan, stream) : launch_scan_tok_f32(q, plan, stream);
 }
 
 }  // namespace zigma
@@ -182,73 +167,12 @@ extern "C" int zigma_selective_scan_fwd(const zigma_scan_params_t *pp, void *str
     (void)hipGetLastError();  // a stale error of an unrelated earlier call is not ours to report
     const zigma_scan_params_t &p = *pp;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (p.batch < 0 || p.dim < 0 || p.seqlen < 0 || p.dstate < 1 || p.dstate > 256) return ZIGMA_ERR_SHAPE;  // MAX_DSTATE
-    if (p.n_groups < 1 || p.dim % p.n_groups != 0) return ZIGMA_ERR_SHAPE;
-#ifdef ZIGMA_SCAN_PROBES
-    constexpr int kProbeBits = 0x7000;          // timing probes of scan_tok2.inc (probe library of tools/ only)
-#else
-    constexpr int kProbeBits = 0;
-#endif
-    if (p.flags & ~(ZIGMA_SCAN_Z_PREACTIVATED | ZIGMA_SCAN_ACCUMULATE | ZIGMA_SCAN_PROBE_V1 | (1 << ZIGMA_SCAN_PROBE_PRIO_SHIFT) | (1 << ZIGMA_SCAN_PROBE_R5_SHIFT) | kProbeBits)) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.batch == 0 || p.dim == 0 || p.seqlen == 0) return ZIGMA_OK;  // empty (pointers may be NULL): nothing to launch
-    if (p.dt_x) {       // ABI 9: dt_proj inside the token-major hot kernel; `delta` is not read (the layout checks below see u's strides)
-        if (!p.u || !p.dt_w || !p.A || !p.B || !p.C || !p.z || !p.out_z) return ZIGMA_ERR_NULL;
-        if (p.reset_period < 0 || p.reset_period % 16 != 0) return ZIGMA_ERR_SHAPE;
-        zigma_scan_params_t q = p;
-        if (p.x) {      // sequence split (ABI 10): `delta` is a WORKSPACE of u's shape the first pass fills with softplus(dt_proj + bias) for the second
-            if (!p.delta || p.reset_period != 0) return p.delta ? ZIGMA_ERR_SHAPE : ZIGMA_ERR_NULL;
-        } else {
-            q.delta = p.u;
-            q.delta_batch_stride = p.u_batch_stride; q.delta_d_stride = p.u_d_stride; q.delta_l_stride = p.u_l_stride;
-        }
-        if ((p.io_dtype != ZIGMA_BF16 && p.io_dtype != ZIGMA_F16) || !tok_eligible(q) || p.batch > 65535) return ZIGMA_ERR_UNSUPPORTED;
-        return p.io_dtype == ZIGMA_BF16 ? launch_scan_tok_bf16_dtp(q, stream) : launch_scan_tok_f16_dtp(q, stream);
+    const ScanPlan plan = plan_scan(p);
+    if (!plan.slice) return launch(p, plan, stream);
+    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
+        const zigma_scan_params_t q = batch_slice(p, b0, plan.slice);
+        const int rc = launch(q, plan_scan(q), stream);
+        if (rc != ZIGMA_OK) return rc;
     }
-    if (p.flags & ZIGMA_SCAN_ACCUMULATE) return ZIGMA_ERR_UNSUPPORTED;       // (only the in-kernel dt_proj form above adds to out_z)
-    if (!p.u || !p.delta || !p.A || !p.B || !p.C) return ZIGMA_ERR_NULL;
-    if (p.z && !p.out_z) return ZIGMA_ERR_NULL;
-    if (!p.z && !p.out) return ZIGMA_ERR_NULL;
-
-    if (p.reset_period < 0 || p.reset_period % 16 != 0 || (p.reset_period > 0 && p.x)) return ZIGMA_ERR_SHAPE;
-    if (p.reset_period > 0 && !tok_eligible(p)) return ZIGMA_ERR_STRIDE;   // only the token-major kernel restarts sequences
-    if ((p.flags & ZIGMA_SCAN_Z_PREACTIVATED) && !(tok_eligible(p) && p.io_dtype != ZIGMA_F32)) return ZIGMA_ERR_UNSUPPORTED;
-    if (tok_eligible(p) && p.batch > 65535) {
-        // the first-generation token-major kernel carries the batch in gridDim.y: larger batches (video temporal layers:
-        // batch x tokens-per-frame rows) run in slices.  checkpoints are per (batch, slab): sliced alike.
-        const size_t es = p.io_dtype == ZIGMA_F32 ? 4 : 2;
-        const int chunk_len = p.chunk_len > 0 ? p.chunk_len : 2048;
-        const int64_t n_chunks = (p.seqlen + chunk_len - 1) / chunk_len, n_tiles = (p.seqlen + 15) / 16;
-        for (int b0 = 0; b0 < p.batch; b0 += 65535) {
-            zigma_scan_params_t q = p;
-            q.batch = p.batch - b0 < 65535 ? p.batch - b0 : 65535;
-            auto adv = [&](const void *ptr, int64_t stride_elems, size_t esz) -> const void * {
-                return ptr ? reinterpret_cast<const char *>(ptr) + static_cast<int64_t>(b0) * stride_elems * static_cast<int64_t>(esz) : nullptr;
-            };
-            q.u = adv(p.u, p.u_batch_stride, es);
-            q.delta = adv(p.delta, p.delta_batch_stride, es);
-            q.z = adv(p.z, p.z_batch_stride, es);
-            q.out = const_cast<void *>(adv(p.out, p.out_batch_stride, es));
-            q.out_z = const_cast<void *>(adv(p.out_z, p.out_z_batch_stride, es));
-            q.B = adv(p.B, p.B_batch_stride, es);
-            q.C = adv(p.C, p.C_batch_stride, es);
-            q.x = const_cast<void *>(adv(p.x, static_cast<int64_t>(p.dim) * n_chunks * 2 * p.dstate, 4));
-            q.checkpoints = reinterpret_cast<float *>(const_cast<void *>(
-                adv(p.checkpoints, static_cast<int64_t>(p.dim / 64) * n_tiles * p.dstate * 64, 4)));
-            const int rc = zigma_selective_scan_fwd(&q, stream_);
-            if (rc != ZIGMA_OK) return rc;
-        }
-        return ZIGMA_OK;
-    }
-    if (tok_eligible(p)) {
-        switch (p.io_dtype) {
-            case ZIGMA_BF16: return launch_scan_tok_bf16(p, stream);
-            case ZIGMA_F16: return launch_scan_tok_f16(p, stream);
-            case ZIGMA_F32: return launch_scan_tok_f32(p, stream);
-            default: return ZIGMA_ERR_DTYPE;
-        }
-    }
-    ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, {
-        ZIGMA_DISPATCH_DTYPE(p.bc_dtype, BCT, { return launch_generic<IO, BCT>(p, stream); })
-    })
-    return ZIGMA_ERR_DTYPE;
+    return ZIGMA_OK;
 }

@@ -61,8 +61,8 @@ def split_chunk_len(batch, d_inner, seqlen, reset_period=0):
 
 
 def split_limits_ok(batch, d_inner, seqlen, chunk_len):
-    """The C side's limits of the sequence split (tok2_split_eligible, csrc/scan_tok2.inc): < 768 workgroups, whole-tile chunks, 2 <= n_chunks
-    <= 65535.  Every chunk split_chunk_len returns under the default knobs passes; SPLIT_MAX_WGS >= 768 (a probe setting) can break that."""
+    """The C side's limits of the sequence split (tok2_split_ok() of plan_scan(), csrc/scan_plan.h): < 768 workgroups, whole-tile chunks,
+    2 <= n_chunks <= 65535.  Every chunk split_chunk_len returns under the default knobs passes; SPLIT_MAX_WGS >= 768 (a probe setting) can break that."""
     return chunk_len > 0 and chunk_len % 16 == 0 and batch * (d_inner // 64) < 768 and 2 <= -(-seqlen // chunk_len) <= 65535
 
 
@@ -270,8 +270,8 @@ def conv_x_proj(x_half, conv_w, conv_b, x_proj_weight, perm=None, _flags=0):
 
 
 def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z=None):
-    """limits of the in-kernel dt_proj of scan_tok2_kernel (zigma_scan_params_t.dt_x), mirroring tok2_dtp_ok() / tok2_layout_ok() /
-    tok_eligible() of csrc/: bf16 / fp16, whole-sequence mode of the hot kernel (dstate == 16, seqlen % 16 == 0, d_inner % 64 == 0; reset_period a
+    """limits of the in-kernel dt_proj of scan_tok2_kernel (zigma_scan_params_t.dt_x), mirroring the whole-sequence dt_proj form of plan_scan()
+    (csrc/scan_plan.h: tok_layout_ok(), tok2_layout_ok(), tok2_dt_operands_ok()): bf16 / fp16, whole-sequence mode of the hot kernel (dstate == 16, seqlen % 16 == 0, d_inner % 64 == 0; reset_period a
     multiple of 16 — the video temporal layers, round 6), 32 <= dt_rank <= 64 and % 8 == 0, x_dbl rows >= 64 wide on 16-byte boundaries, channel-contiguous u / z, and every
     in-sample offset (seqlen * row stride, in bytes of up to 4-byte elements) below 2^31 / 4.  A caller that gets False keeps the
     dt_proj kernel (or F.linear) + the ordinary scan call, which serves every shape the reference does."""
@@ -427,7 +427,8 @@ def differentiable(*tensors):
 
 
 def z_preactivated_eligible(batch, seqlen, d_state):
-    """scan-side limits of a gate in_proj pre-activated (ZIGMA_SCAN_Z_PREACTIVATED): the hot kernel's inference form, 16 states, whole tiles, one grid"""
+    """scan-side limits of a gate in_proj pre-activated (ZIGMA_SCAN_Z_PREACTIVATED): the hot kernel's inference form, 16 states, whole tiles, one grid
+    (plan_scan() of csrc/scan_plan.h: tok2_layout_ok() without `out`, no batch slices)"""
     return d_state == 16 and seqlen % 16 == 0 and batch <= 65535 and not torch.is_grad_enabled()
 
 
