@@ -212,7 +212,7 @@ typedef struct zigma_norm_params {
 int zigma_add_norm_fwd(const zigma_norm_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * dt_proj + bias + softplus on the matrix cores (bf16 in / fp32 accumulate / bf16 out).
+ * dt_proj + bias + softplus on the matrix cores (bf16 or fp16 in / fp32 accumulate / same type out).
  * Replaces the skinny GEMM  delta = delta_proj_weight @ x_dbl[:, :dt_rank].T  of the reference
  * (dis_mamba/mamba_ssm/ops/selective_scan_interface.py:323, K = dt_rank) together with the
  * softplus(delta + delta_bias) its scan kernel applies first (selective_scan_fwd_kernel.cuh:153-156):
@@ -221,7 +221,7 @@ int zigma_add_norm_fwd(const zigma_norm_params_t *p, void *stream);
  *
  * x: (m, >=k) rows of pitch x_row_stride (the first k columns of x_dbl);  w: (n, k) = dt_proj.weight;
  * bias: float32 (n) or NULL;  out: (m, n).  The selective scan is then called with delta_softplus = 0 and
- * delta_bias = NULL.  Limits: dtype bf16, k <= 48 and a multiple of 8, n % 64 == 0, x/w rows 16-byte aligned.
+ * delta_bias = NULL.  Limits: dtype bf16 or fp16 (x, w, out alike), k <= 48 and a multiple of 8, n % 64 == 0, x/w rows 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_dtproj_params {
     int64_t m;              /* tokens (batch * seqlen) */
@@ -395,7 +395,7 @@ int zigma_scale_reduce_bwd(const zigma_glue_bwd_params_t *p, void *stream);
  * Replaces the scaled_dot_product_attention / xformers call of CrossAttention.forward (reference model_zigma.py:113-127;
  * ZigMa: 8 heads x 64, 77 text tokens).  q, out: (batch, seqlen, heads*head_dim) rows; k, v: (batch, n_ctx, heads*head_dim)
  * rows (any row / batch pitch: e.g. slices of one batched K/V projection); head h = columns [h*head_dim, (h+1)*head_dim).
- * Limits: bf16, head_dim 64, n_ctx <= 128, rows 16-byte aligned.
+ * Limits: bf16 or fp16 (q, k, v, out alike), head_dim 64, n_ctx <= 128, rows 16-byte aligned.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_xattn_params {
     int32_t batch, seqlen, n_ctx, heads, head_dim;
@@ -441,8 +441,8 @@ int zigma_cross_attn_bwd(const zigma_xattn_bwd_params_t *p, void *stream);
 /* ------------------------------------------------------------------------------------------
  * x_proj: out[m, n] = sum_k x[m, k] * w[n, k]  for the skinny projection of the Mamba block (n = dt_rank + 2 d_state).
  * Replaces F.linear(conv1d_out, x_proj_weight) (reference dis_mamba/mamba_ssm/ops/selective_scan_interface.py:318-322).
- * x: (m, k) rows (the conv output u, token-major); w: (n, k) = x_proj.weight; out: (m, n).  bf16 in, fp32 accumulate,
- * bf16 out.  Limits: n <= 96, k % 256 == 0, x / w rows 16-byte aligned.  Below 16 384 rows (and k <= 1536) the library splits K over the
+ * x: (m, k) rows (the conv output u, token-major); w: (n, k) = x_proj.weight; out: (m, n).  bf16 or fp16 in, fp32 accumulate,
+ * same type out.  Limits: n <= 96, k % 256 == 0, x / w rows 16-byte aligned.  Below 16 384 rows (and k <= 1536) the library splits K over the
  * waves of 32-row workgroups and adds the partial tiles in a fixed order (round 5); from 16 384 rows on a workgroup streams 256 rows.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_xproj_params {
@@ -463,7 +463,7 @@ int zigma_x_proj_fwd(const zigma_xproj_params_t *p, void *stream);
  *   out[b*L + k, n] = sum_c u[b, k, c] * w[n, c]
  * Replaces causal_conv1d_fn(..., activation="silu") + F.linear(conv1d_out, x_proj_weight) of MambaInnerFn.forward
  * (reference selective_scan_interface.py:307-322) with the gather of mamba_simple.py:362-370 in the loads.  u (needed by
- * the scan) is written once and not read back.  bf16 throughout, fp32 accumulation; u is rounded to bf16 BEFORE the
+ * the scan) is written once and not read back.  bf16 or fp16 throughout (one dtype), fp32 accumulation; u is rounded to it BEFORE the
  * projection, as in the reference.  x: (batch, seqlen, dim) channel-contiguous rows; conv_weight: (dim, 4) contiguous;
  * conv_bias: (dim); w: (n, dim) rows; u: (batch, seqlen, dim) in scan order; out: (batch * seqlen, n) rows.
  * Limits: width 4, bias required, seqlen % 32 == 0, batch * seqlen % 256 == 0, dim % 64 == 0, n <= 96 and n % 8 == 0, 16-byte
@@ -485,13 +485,13 @@ typedef struct zigma_conv_xproj_params {
 int zigma_conv_x_proj_fwd(const zigma_conv_xproj_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Dense projection on the matrix cores:  out = x @ w^T (+ bias) (+ SiLU on a column range), bf16 in / fp32 accumulate / bf16 out.
+ * Dense projection on the matrix cores:  out = x @ w^T (+ bias) (+ SiLU on a column range), bf16 or fp16 in / fp32 accumulate / same type out.
  * Replaces the cuBLAS GEMMs behind F.linear at Mamba.in_proj (reference mamba_simple.py:290-294), out_proj
  * (selective_scan_interface.py:365) and CrossAttention.to_q / to_out (model_zigma.py:104-135).
- * x: (m, k) rows; w: (n, k) rows (nn.Linear layout); out: (m, n) rows; bias: bf16 (n) or NULL.
+ * x: (m, k) rows; w: (n, k) rows (nn.Linear layout); out: (m, n) rows; bias: (n) in the operand dtype or NULL.
  * silu_from_col: output columns >= this value leave as silu(value) (in_proj writes silu(z) for the gate half, consumed by
  * the scan under ZIGMA_SCAN_Z_PREACTIVATED); pass n for a plain projection.  Must be a multiple of 32.
- * Limits: bf16; k % 64 == 0; n % 128 == 0; x / w rows 16-byte aligned, out rows 8-byte aligned.
+ * Limits: bf16 or fp16 (every operand of a call in the one dtype); k % 64 == 0; n % 128 == 0; x / w rows 16-byte aligned, out rows 8-byte aligned.
  * ZIGMA_LINEAR_WS (flags): the weight-stationary kernel (csrc/linear_ws.hip — a panel of w lives in the registers of a workgroup, only
  * the rows of x stream; the in_proj of the default path).  Same result bit for bit.  Limits, else ZIGMA_ERR_UNSUPPORTED: no bias /
  * residual; k = 512 or 640 with 256-feature panels (pw = 256), or — since round 5 — k = 1280 or 1536 with 128-feature panels (pw = 128:
@@ -516,8 +516,8 @@ typedef struct zigma_linear_params {
     const void *bias;        /* or NULL */
     void *out;
     /* optional gated residual in the epilogue (ABI 4) — CrossAttention's `hidden + gate_msa * to_out(...)` (model_zigma.py:447-449):
-     *   out[m, :] = residual[m, :] + gate[m / rows_per_batch, :] * bf16(x @ w^T + bias)[m, :]
-     * residual: (m, n) bf16 rows of pitch res_row_stride; gate: (m / rows_per_batch, n) bf16 rows of pitch gate_batch_stride;
+     *   out[m, :] = residual[m, :] + gate[m / rows_per_batch, :] * r16(x @ w^T + bias)[m, :]     (r16: rounded to the operand dtype)
+     * residual: (m, n) rows of pitch res_row_stride; gate: (m / rows_per_batch, n) rows of pitch gate_batch_stride, both in the operand dtype;
      * rows_per_batch % 256 == 0.  residual == NULL: plain projection. */
     const void *residual, *gate;
     int64_t res_row_stride, gate_batch_stride;

@@ -5,14 +5,14 @@ for the shapes ZigMa produces (8 heads x 64, 77 text tokens).  `cross_attn` is t
 autograd form for the training path: forward and backward are both hand-written HIP kernels (zigma_cross_attn_bwd recomputes the
 probabilities: with 77 keys they are 80 MB per layer, recomputing them on the matrix cores is cheaper than storing them and than any
 flash machinery) — torch's fused SDPA is an AOT-Triton kernel on ROCm, which the north star rules out.
-Operands outside the kernels' limits (bf16, head_dim 64, n_ctx <= 128, 16-byte aligned rows) take the same math in plain torch ops.
+Operands outside the kernels' limits (forward: bf16 or fp16, backward: bf16; head_dim 64, n_ctx <= 128, 16-byte aligned rows) take the same math in plain torch ops.
 """
 import torch
 
 from . import _lib
 
 def cross_attn_eligible(q, k, v, heads):
-    if not (q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == q.dtype and v.dtype == q.dtype):
+    if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
         return False
     if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != heads * 64 or k.shape[2] != heads * 64:
         return False
@@ -22,11 +22,16 @@ def cross_attn_eligible(q, k, v, heads):
     return ok(q) and ok(k) and ok(v)
 
 
+def cross_attn_bwd_eligible(q, k, v, heads):
+    """limits of zigma_cross_attn_bwd: the forward's, bf16 only (the backward kernel has no fp16 form)"""
+    return q.dtype == torch.bfloat16 and cross_attn_eligible(q, k, v, heads)
+
+
 def cross_attn(q, k, v, heads, scale=None):
     """q: (B, L, H*64); k, v: (B, n_ctx, H*64) (row-strided views are fine) -> (B, L, H*64)."""
     dev = _lib.require_device(q, k, v)
     if not cross_attn_eligible(q, k, v, heads):
-        raise RuntimeError("cross_attn: needs bf16 (B, L, H*64) / (B, n_ctx <= 128, H*64) operands with 16-byte aligned rows")
+        raise RuntimeError("cross_attn: needs bf16 or fp16 (B, L, H*64) / (B, n_ctx <= 128, H*64) operands with 16-byte aligned rows")
     Bsz, L, C = q.shape
     out = torch.empty(Bsz, L, C, device=q.device, dtype=q.dtype)
     P = _lib.XAttnParams()
@@ -104,7 +109,7 @@ def cross_attn_bwd(q, k, v, dout, heads, scale=None):
     """gradients of cross_attn(q, k, v) w.r.t. q, k, v given dout (zigma_cross_attn_bwd: the probabilities are recomputed, nothing of
     the forward is needed).  Returns (dq, dk, dv) in the operand dtype; dk / dv are accumulated in fp32."""
     dev = _lib.require_device(q, k, v, dout)
-    if not (cross_attn_eligible(q, k, v, heads) and cross_attn_eligible(dout, k, v, heads) and dout.shape == q.shape):
+    if not (cross_attn_bwd_eligible(q, k, v, heads) and cross_attn_bwd_eligible(dout, k, v, heads) and dout.shape == q.shape):
         raise RuntimeError("cross_attn_bwd: needs bf16 (B, L, H*64) / (B, n_ctx <= 128, H*64) operands with 16-byte aligned rows")
     Bsz, L, C = q.shape
     NC = k.shape[1]

@@ -49,6 +49,28 @@ def check_no_scratch(remarks, src):
     return seen
 
 
+GENERATED_F16_INC = os.path.join(CSRC, "linear4w_body_f16.inc")
+
+
+def ensure_generated(verbose=True):
+    """csrc/linear4w_body_f16.inc — the fp16 bodies of linear4w_kernel's generated main loop (csrc/gen/linear4w_gen.py, cfg f16=True) — is a build
+    product, not a committed file: its 19 400 lines are the committed bf16 text of linear4w_body.inc with four mnemonics substituted one for one
+    (tests/test_linear4w_gen_f16.py checks exactly that).  (Re)written here when missing or not what the generator emits; takes about a second."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("zigma_linear4w_gen", os.path.join(CSRC, "gen", "linear4w_gen.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    tmp = GENERATED_F16_INC + ".tmp"
+    gen.emit_inc_f16(tmp)
+    if os.path.exists(GENERATED_F16_INC) and open(GENERATED_F16_INC).read() == open(tmp).read():
+        os.remove(tmp)
+        return GENERATED_F16_INC
+    os.replace(tmp, GENERATED_F16_INC)
+    if verbose:
+        print(f"generated {GENERATED_F16_INC}", flush=True)
+    return GENERATED_F16_INC
+
+
 def _digest(paths, extra=()):
     h = hashlib.sha256()
     for pth in sorted(paths):
@@ -68,6 +90,7 @@ def build(force=False, verbose=True, sources=None, lib=None, extra_flags=()):
     obj_dir = OBJ if lib == LIB else OBJ + "_" + os.path.splitext(os.path.basename(lib))[0]      # (A/B libraries of tools/ keep their own objects)
     os.makedirs(obj_dir, exist_ok=True)
     os.makedirs(os.path.dirname(lib), exist_ok=True)
+    ensure_generated(verbose)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))]
     headers.append(os.path.join(ROOT, "include", "zigma_hip.h"))
     stamp = lib + ".srchash"

@@ -22,7 +22,7 @@
 //   than it — 138.7 vs 71.3 + 64.4 us; archived as tools/experiments/conv_x_proj_dt_r02.hip.)
 // Measured at the headline shape (B=64, L=1024, d_inner=1280, n=72): 72 us against 131 us for conv_tok + x_proj_mfma
 // (tools/conv_xproj_ab.py); loads + MFMA alone 35 us, + conv 64 us, + stores 64 us (probe flags).
-// bf16 only; width 4; bias required; seqlen % 32 == 0; d_inner % 64 == 0; n <= 96, n % 8 == 0.
+// bf16 or fp16 (template parameter T: the dot products of the conv, the packs, the MFMA); width 4; bias required; seqlen % 32 == 0; d_inner % 64 == 0; n <= 96, n % 8 == 0.
 #include "zigma_common.h"
 
 namespace zigma {
@@ -40,14 +40,14 @@ constexpr int cx_w_off(int nw) { return nw * kCxXBytes; }
 constexpr int cx_c_off(int nw) { return cx_w_off(nw) + 96 * 128; }
 constexpr int cx_stage(int nw) { return cx_c_off(nw) + 1024; }      // 8 waves: 54272 B, 4 waves: 33792 B
 
-__device__ __forceinline__ float bf_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bf_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-__device__ __forceinline__ float dot2(unsigned a, unsigned b, float c) {
+// c + a.lo * b.lo + a.hi * b.hi on packed pairs: v_dot2c_f32_bf16 / v_dot2_f32_f16
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+template <typename T> __device__ __forceinline__ float dot2(unsigned a, unsigned b, float c);
+template <> __device__ __forceinline__ float dot2<BF16>(unsigned a, unsigned b, float c) {
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), c, false);
 }
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {        // one v_cvt_pk_bf16_f32 (round to nearest even)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
+template <> __device__ __forceinline__ float dot2<F16>(unsigned a, unsigned b, float c) {
+    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c, false);
 }
 // LDS reads are inline assembly on purpose: hipcc makes a ds_read it can see wait for EVERY direct-to-LDS load in flight
 // (s_waitcnt vmcnt(0)), the younger stages included, which would serialise the pipeline.  Landing is tracked by hand (counted
@@ -84,7 +84,7 @@ __device__ __forceinline__ void wait_vm_n(int n) {
     }
 }
 
-template <int NST, int NW>
+template <int NST, int NW, typename T>
 __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_xproj_params_t p) {
     constexpr int kCxWaves = NW, kCxWOff = cx_w_off(NW), kCxCOff = cx_c_off(NW), kCxStage = cx_stage(NW), NWI = (12 + NW - 1) / NW;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NST * kCxStage];
@@ -213,18 +213,18 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
                 const unsigned lo23 = __builtin_amdgcn_perm(xs[3][r], xs[2][r], 0x05040100u);
                 const unsigned hi01 = __builtin_amdgcn_perm(xs[1][r], xs[0][r], 0x07060302u);
                 const unsigned hi23 = __builtin_amdgcn_perm(xs[3][r], xs[2][r], 0x07060302u);
-                float a_lo = dot2(lo01, k.Wc[r].x, bf_lo(bs[r]));
-                a_lo = dot2(lo23, k.Wc[r].y, a_lo);
-                float a_hi = dot2(hi01, k.Wc[r].z, bf_hi(bs[r]));
-                a_hi = dot2(hi23, k.Wc[r].w, a_hi);
-                ur[r] = pack_bf2(silu(a_lo), silu(a_hi));
+                float a_lo = dot2<T>(lo01, k.Wc[r].x, lo16<T>(bs[r]));
+                a_lo = dot2<T>(lo23, k.Wc[r].y, a_lo);
+                float a_hi = dot2<T>(hi01, k.Wc[r].z, hi16<T>(bs[r]));
+                a_hi = dot2<T>(hi23, k.Wc[r].w, a_hi);
+                ur[r] = pack2_pk<T>(silu(a_lo), silu(a_hi));
             }
             const u32x4 u8 = {ur[0], ur[1], ur[2], ur[3]};
             uq[ks] = u8;
-            const bf16x8 a = __builtin_bit_cast(bf16x8, u8);
+            const frag8_t<T> a = __builtin_bit_cast(frag8_t<T>, u8);
 #pragma unroll
             for (int nb = 0; nb < 3; ++nb)
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, k.Bf[nb]), a, acc[nb], 0, 0, 0);
+                acc[nb] = mfma_32x32x16<T>(__builtin_bit_cast(frag8_t<T>, k.Bf[nb]), a, acc[nb]);
         }
         // u of this stage (32 positions x 64 channels per wave) leaves as FULL 128-byte lines: a lane holds 16-byte pieces of its own
         // row only (two lanes = 32 contiguous bytes per store instruction and row — measured: the partial-line stores cost more than
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-            const u32x2 pk = {pack_bf2(acc[nb][q * 4], acc[nb][q * 4 + 1]), pack_bf2(acc[nb][q * 4 + 2], acc[nb][q * 4 + 3])};
+            const u32x2 pk = {pack2_pk<T>(acc[nb][q * 4], acc[nb][q * 4 + 1]), pack2_pk<T>(acc[nb][q * 4 + 2], acc[nb][q * 4 + 3])};
             asm volatile("ds_write_b64 %0, %1" ::"v"(tile + j * kPitch + nb * 64 + q * 16 + kh * 8), "v"(pk) : "memory");
         }
     {
@@ -283,7 +283,7 @@ extern "C" int zigma_conv_x_proj_fwd(const zigma_conv_xproj_params_t *pp, void *
     if (p.flags & ~15) return ZIGMA_ERR_UNSUPPORTED;
     if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
     if (!p.x || !p.conv_weight || !p.conv_bias || !p.w || !p.u || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
+    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
     if (p.n > 96 || p.n % 8 != 0 || p.dim % kCxBK != 0 || p.seqlen % kCxTok != 0) return ZIGMA_ERR_SHAPE;
     if (p.out_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0) return ZIGMA_ERR_STRIDE;
     const int64_t m = static_cast<int64_t>(p.batch) * p.seqlen;
@@ -297,7 +297,7 @@ extern "C" int zigma_conv_x_proj_fwd(const zigma_conv_xproj_params_t *pp, void *
     // while the other waits for its loads (measured 72 us; 8 waves in lockstep 75 us; a third stage does not pay, the second
     // workgroup does its job).  flags: 1 = three stages, 2 = eight-wave workgroups; probes (wrong results): 4 = no u stores,
     // 8 = no conv arithmetic.
-#define ZIGMA_CX(S_, W_) hipLaunchKernelGGL((conv_x_proj_kernel<S_, W_>), grid, block, 0, stream, p);
+#define ZIGMA_CX(S_, W_) ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((conv_x_proj_kernel<S_, W_, T>), grid, block, 0, stream, p))
     if (p.flags & 2) {
         const dim3 grid(static_cast<unsigned>(m / (kCxTok * 8))), block(64 * 8);
         if (p.flags & 1) { ZIGMA_CX(3, 8) } else { ZIGMA_CX(2, 8) }

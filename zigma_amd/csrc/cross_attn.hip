@@ -12,12 +12,11 @@
 //   O^T = V^T P^T : A = V^T rows from LDS, B = P rows (bf16) from the per-wave LDS tile
 //   O^T / rowsum -> per-wave LDS tile (8-byte pieces) -> 16-byte stores, 128 contiguous bytes per token
 // HBM-bound by construction: reads Q once, writes O once (2 x 67 MB at B=64, L=1024); K/V come from L2.
-// bf16 only (MFMA operand type), head_dim 64, n_ctx <= 128.
+// bf16 or fp16 (template parameter T: both MFMAs, the P and O packs; P = exp2(.) <= 1 is in fp16's range), head_dim 64, n_ctx <= 128.
 #include "zigma_common.h"
 
 namespace zigma {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kXaD = 64;                 // head dim
@@ -27,14 +26,9 @@ constexpr int kXaKPitch = (kXaD + 8) * 2;   // bytes per K row in LDS (16 B skew
 // 16-token tiles per wave = how many query tokens share one staging of K_h / V_h^T (20 KB): 8 (512 tokens per workgroup) where the
 // sequence has them — 35.5 us against 38.0 with 4 and 40.2 with 16 at the headline shape (tools/attn_probe.py) —, 4 for short ones
 
-typedef float xa_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 xa_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack_bf16(float lo, float hi) {        // one v_cvt_pk_bf16_f32 (round to nearest even, like from_float<BF16>)
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(xa_f32x2{lo, hi}, xa_bf16x2));
-}
 
 // NKB 16-key blocks: n_ctx <= 16 * NKB; MASK_ALL = false: n_ctx > 16 (NKB - 1), padded keys only in the last block
-template <int NKB, bool MASK_ALL>
+template <int NKB, bool MASK_ALL, typename T>
 __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_xattn_params_t p, const int kXaTiles) {
     constexpr int KP = 16 * NKB;                         // keys covered by S
     constexpr int KS = (KP + 31) / 32, KP2 = 32 * KS;    // k-steps / padded keys of the P V product
@@ -82,20 +76,20 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
     const float sc = p.scale * kLog2e;
     unsigned char *pt = s_p[wave];
     const int tile0 = blockIdx.x * kXaTiles * kXaWaves + wave;      // this wave's tiles: tile0, tile0 + 4, ...
-    auto load_q = [&](int t0, bf16x8 (&qa)[2]) {                    // lane -> token t0 + i16, dims 32 ks + 8 g ..
+    auto load_q = [&](int t0, frag8_t<T> (&qa)[2]) {                    // lane -> token t0 + i16, dims 32 ks + 8 g ..
         int tq = t0 + i16;
         tq = tq < L ? tq : L - 1;
         const uint16_t *qrow = qb + static_cast<int64_t>(tq) * p.q_row_stride;
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) qa[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(qrow + ks * 32 + g * 8));
+        for (int ks = 0; ks < 2; ++ks) qa[ks] = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(qrow + ks * 32 + g * 8));
     };
-    bf16x8 qn[2];
+    frag8_t<T> qn[2];
     if (tile0 * kXaTok < L) load_q(tile0 * kXaTok, qn);
 #pragma unroll 1
     for (int it = 0; it < kXaTiles; ++it) {
         const int t0 = (tile0 + it * kXaWaves) * kXaTok;
         if (t0 >= L) break;                                         // wave-uniform; no workgroup barriers below
-        const bf16x8 qa[2] = {qn[0], qn[1]};
+        const frag8_t<T> qa[2] = {qn[0], qn[1]};
         if (it + 1 < kXaTiles && t0 + kXaWaves * kXaTok < L) load_q(t0 + kXaWaves * kXaTok, qn);
         // ---- S^T = K Q^T : lane -> token column i16, key rows 16 nb + 4 g + r -----------------------------------------
         f32x4 s[NKB];
@@ -103,9 +97,8 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
         for (int ks = 0; ks < 2; ++ks) {                 // (k-step outermost: consecutive MFMAs on different accumulators; the first on a literal zero)
 #pragma unroll
             for (int nb = 0; nb < NKB; ++nb) {
-                const bf16x8 kf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXaKPitch + ks * 64 + g * 16));
-                s[nb] = ks == 0 ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qa[ks], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qa[ks], s[nb], 0, 0, 0);
+                const frag8_t<T> kf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXaKPitch + ks * 64 + g * 16));
+                s[nb] = ks == 0 ? mfma_16x16x32<T>(kf, qa[ks], f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(kf, qa[ks], s[nb]);
             }
         }
         // ---- softmax over the keys of this lane's token: 4 NKB values in the lane, the rest in lanes i16 + 16 g' ----------
@@ -128,7 +121,7 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
             float e[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) { e[r] = fast_exp2(__builtin_fmaf(s[nb][r], sc, msc)); sum += e[r]; }   // exp2(-inf) = 0 for padded keys
-            *reinterpret_cast<uint2 *>(pt + i16 * VPitch + (nb * 16 + 4 * g) * 2) = make_uint2(pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]));
+            *reinterpret_cast<uint2 *>(pt + i16 * VPitch + (nb * 16 + 4 * g) * 2) = make_uint2(pack2_pk<T>(e[0], e[1]), pack2_pk<T>(e[2], e[3]));
         }
         if (KP2 > KP) *reinterpret_cast<uint2 *>(pt + i16 * VPitch + (KP + 4 * g) * 2) = make_uint2(0u, 0u);
         sum += __shfl_xor(sum, 16, 64);
@@ -140,12 +133,11 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
         f32x4 o[4];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const bf16x8 pf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(pt + i16 * VPitch + ks * 64 + g * 16));
+            const frag8_t<T> pf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(pt + i16 * VPitch + ks * 64 + g * 16));
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
-                const bf16x8 vf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_vt + (db * 16 + i16) * VPitch + ks * 64 + g * 16));
-                o[db] = ks == 0 ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[db], 0, 0, 0);
+                const frag8_t<T> vf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(s_vt + (db * 16 + i16) * VPitch + ks * 64 + g * 16));
+                o[db] = ks == 0 ? mfma_16x16x32<T>(vf, pf, f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(vf, pf, o[db]);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -154,7 +146,7 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
 #pragma unroll
         for (int db = 0; db < 4; ++db)
             *reinterpret_cast<uint2 *>(pt + i16 * OPitch + (db * 16 + 4 * g) * 2) =
-                make_uint2(pack_bf16(o[db][0] * inv, o[db][1] * inv), pack_bf16(o[db][2] * inv, o[db][3] * inv));
+                make_uint2(pack2_pk<T>(o[db][0] * inv, o[db][1] * inv), pack2_pk<T>(o[db][2] * inv, o[db][3] * inv));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -185,7 +177,7 @@ extern "C" int zigma_cross_attn_fwd(const zigma_xattn_params_t *pp, void *stream
     if (!(p.scale > 0.f) || !(p.scale < 3.0e38f)) return ZIGMA_ERR_UNSUPPORTED;
     if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
     if (!p.q || !p.k || !p.v || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
+    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
     if (p.head_dim != kXaD || p.n_ctx > 128 || p.batch > 65535 || p.heads > 65535) return ZIGMA_ERR_SHAPE;
     auto mis = [](const void *q, int64_t rs, int64_t bs) { return reinterpret_cast<uintptr_t>(q) % 16 != 0 || rs % 8 != 0 || bs % 8 != 0; };
     if (mis(p.q, p.q_row_stride, p.q_batch_stride) || mis(p.k, p.k_row_stride, p.k_batch_stride) ||
@@ -195,13 +187,12 @@ extern "C" int zigma_cross_attn_fwd(const zigma_xattn_params_t *pp, void *stream
     const int tok_per_wg = kXaTok * kXaWaves * tiles;
     dim3 grid((p.seqlen + tok_per_wg - 1) / tok_per_wg, p.heads, p.batch), block(64 * kXaWaves);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (p.n_ctx <= 80) {
-        if (p.n_ctx > 64) hipLaunchKernelGGL((cross_attn_kernel<5, false>), grid, block, 0, stream, p, tiles);
-        else hipLaunchKernelGGL((cross_attn_kernel<5, true>), grid, block, 0, stream, p, tiles);
-    } else {
-        if (p.n_ctx > 112) hipLaunchKernelGGL((cross_attn_kernel<8, false>), grid, block, 0, stream, p, tiles);
-        else hipLaunchKernelGGL((cross_attn_kernel<8, true>), grid, block, 0, stream, p, tiles);
-    }
+#define ZIGMA_XA(N_, M_) hipLaunchKernelGGL((cross_attn_kernel<N_, M_, T>), grid, block, 0, stream, p, tiles)
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, {
+        if (p.n_ctx <= 80) { if (p.n_ctx > 64) ZIGMA_XA(5, false); else ZIGMA_XA(5, true); }
+        else { if (p.n_ctx > 112) ZIGMA_XA(8, false); else ZIGMA_XA(8, true); }
+    })
+#undef ZIGMA_XA
     set_last_kernel("cross_attn_mfma");
     return check_launch();
 }

@@ -6,7 +6,7 @@
 // WRITE-bound streaming kernel (one pass over the (M, Di) output, 168 MB at B=64), so the transcendental work
 // rides for free under the stores — and it no longer sits in the VALU-bound scan kernel.
 //
-//   out[m, d] = softplus20( sum_r x[m, r] * w[d, r] + bias[d] )        (bf16 in, fp32 accumulate, bf16 out)
+//   out[m, d] = softplus20( sum_r x[m, r] * w[d, r] + bias[d] )        (bf16 or fp16 in, fp32 accumulate, same type out)
 //
 // One wave = 32 tokens x 64 channels: v_mfma_f32_32x32x16_bf16, 3 k-steps (K padded to 48 with zero fragments),
 // two accumulators.  The B fragments of the two accumulators hold the EVEN and the ODD channels of the 64-channel
@@ -18,7 +18,6 @@
 
 namespace zigma {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kDtTokPerWave = 32, kDtChPerBlock = 64, kDtWaves = 4;
@@ -27,6 +26,7 @@ constexpr int kDtTokPerWave = 32, kDtChPerBlock = 64, kDtWaves = 4;
 #endif
 constexpr int kDtIters = ZIGMA_DT_ITERS;
 
+template <typename T>
 __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(const zigma_dtproj_params_t p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_tile[kDtWaves * kDtTokPerWave * 144];
     const int lane = threadIdx.x & 63;
@@ -41,13 +41,13 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
 
     // 8 consecutive k of one row; k % 8 == 0 (dispatcher), so a fragment is either whole or beyond K (= zero): the
     // address is clamped and the value selected — no divergent branches around the loads
-    auto frag = [&](const uint16_t *row, int k0) -> bf16x8 {
+    auto frag = [&](const uint16_t *row, int k0) -> frag8_t<T> {
         const bool live = k0 < p.k;
         const uint4 v = *reinterpret_cast<const uint4 *>(row + (live ? k0 : 0));
-        return __builtin_bit_cast(bf16x8, live ? v : make_uint4(0, 0, 0, 0));
+        return __builtin_bit_cast(frag8_t<T>, live ? v : make_uint4(0, 0, 0, 0));
     };
     // B fragments (weights) of this block's channels: even / odd channel per lane, 3 k-steps, loaded once
-    bf16x8 be[3], bo[3];
+    frag8_t<T> be[3], bo[3];
     const uint16_t *we = ww + static_cast<int64_t>(d0 + 2 * j) * p.w_row_stride;
     const uint16_t *wo = we + p.w_row_stride;
 #pragma unroll
@@ -60,14 +60,14 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
     const int64_t m_blk = static_cast<int64_t>(blockIdx.y) * (kDtTokPerWave * kDtWaves * kDtIters);
     // A fragments of tile `it`: the next tile's are requested before this tile's softplus / stores (their L2 latency otherwise
     // sits between every two tiles of a wave)
-    auto a_frags = [&](int it, bf16x8 (&a)[3]) {
+    auto a_frags = [&](int it, frag8_t<T> (&a)[3]) {
         int64_t mr = m_blk + (static_cast<int64_t>(it) * kDtWaves + wave) * kDtTokPerWave + j;
         mr = mr < p.m ? mr : p.m - 1;                            // rows beyond m: clamped loads, never stored
         const uint16_t *xr = xw + mr * p.x_row_stride;
 #pragma unroll
         for (int s = 0; s < 3; ++s) a[s] = frag(xr, s * 16 + kh * 8);
     };
-    bf16x8 a_cur[3], a_nxt[3];
+    frag8_t<T> a_cur[3], a_nxt[3];
     a_frags(0, a_cur);
 #pragma unroll 1
     for (int it = 0; it < kDtIters; ++it) {
@@ -77,8 +77,14 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
         f32x16 ce = {}, co = {};
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
-            ce = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[s], be[s], ce, 0, 0, 0);
-            co = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[s], bo[s], co, 0, 0, 0);
+            // (the builtins spelled out: through the mfma_32x32x16<T> wrapper hipcc allocates this loop's registers differently)
+            if constexpr (T::id == ZIGMA_F16) {
+                ce = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[s], be[s], ce, 0, 0, 0);
+                co = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_cur[s], bo[s], co, 0, 0, 0);
+            } else {
+                ce = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[s], be[s], ce, 0, 0, 0);
+                co = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_cur[s], bo[s], co, 0, 0, 0);
+            }
         }
         // C/D layout: column = lane & 31 (channel pair j), row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (token)
         const bool full = m0 + kDtTokPerWave <= p.m;            // wave-uniform: whole tile inside -> no per-store predicate
@@ -91,8 +97,7 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
                 const int dm = (r & 3) + 8 * (r >> 2) + 4 * kh;
                 float ve = ce[r] + b_e, vo = co[r] + b_o;
                 if (p.softplus) { ve = softplus20_r16(ve); vo = softplus20_r16(vo); }
-                *reinterpret_cast<uint32_t *>(tile + dm * 144 + j * 4) =
-                    static_cast<uint32_t>(from_float<BF16>(ve)) | (static_cast<uint32_t>(from_float<BF16>(vo)) << 16);
+                *reinterpret_cast<uint32_t *>(tile + dm * 144 + j * 4) = pack2<T>(ve, vo);
             }
             uint16_t *orow8 = ow + (m0 + (lane >> 3)) * p.out_row_stride + d0 + (lane & 7) * 8;
 #pragma unroll
@@ -106,7 +111,7 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
             const int dm = (r & 3) + 8 * (r >> 2);
             float ve = ce[r] + b_e, vo = co[r] + b_o;
             if (p.softplus) { ve = softplus20_r16(ve); vo = softplus20_r16(vo); }
-            const uint32_t pk = static_cast<uint32_t>(from_float<BF16>(ve)) | (static_cast<uint32_t>(from_float<BF16>(vo)) << 16);
+            const uint32_t pk = pack2<T>(ve, vo);
             if (full || m0 + 4 * kh + dm < p.m) *reinterpret_cast<uint32_t *>(orow + dm * p.out_row_stride) = pk;
         }
         }
@@ -127,7 +132,7 @@ extern "C" int zigma_dt_proj_softplus_fwd(const zigma_dtproj_params_t *pp, void 
     if (p.flags & ~1) return ZIGMA_ERR_UNSUPPORTED;         // 1: four-byte stores as the accumulators lie (A/B probe)
     if (p.m == 0 || p.n == 0) return ZIGMA_OK;
     if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
+    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
     if (p.k > 48 || p.k % 8 != 0 || p.n % kDtChPerBlock != 0) return ZIGMA_ERR_SHAPE;
     // 16-byte fragment loads, 4-byte packed stores
     if (p.x_row_stride % 8 != 0 || p.w_row_stride % 8 != 0 || p.out_row_stride % 2 != 0 ||
@@ -136,7 +141,7 @@ extern "C" int zigma_dt_proj_softplus_fwd(const zigma_dtproj_params_t *pp, void 
         return ZIGMA_ERR_STRIDE;
     const int64_t tok_per_block = kDtTokPerWave * kDtWaves * kDtIters;
     dim3 grid(p.n / kDtChPerBlock, static_cast<unsigned>((p.m + tok_per_block - 1) / tok_per_block)), block(64 * kDtWaves);
-    hipLaunchKernelGGL(dt_proj_softplus_kernel, grid, block, 0, static_cast<hipStream_t>(stream_), p);
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(dt_proj_softplus_kernel<T>, grid, block, 0, static_cast<hipStream_t>(stream_), p))
     set_last_kernel("dt_proj_softplus_mfma");
     return check_launch();
 }

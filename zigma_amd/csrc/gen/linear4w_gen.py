@@ -4,6 +4,7 @@ ZigMa block (reference call sites mamba_simple.py:290-294, selective_scan_interf
 as ONE inline-asm statement per kernel variant, for gfx950.
 
     python zigma_amd/csrc/gen/linear4w_gen.py --emit      # writes csrc/linear4w_body.inc (committed; the build does not run this)
+    python zigma_amd/csrc/gen/linear4w_gen.py --emit-f16  # writes csrc/linear4w_body_f16.inc: the same bodies for fp16 operands (cfg f16=True); not committed, zigma_amd/build.py does this
     python zigma_amd/csrc/gen/linear4w_gen.py --check     # runs the generated text through the simulator below
 
 Why generated assembly.  The arrangement: ONE wave per SIMD — a 4-wave workgroup per CU, 512 registers per
@@ -114,7 +115,27 @@ def acc(nb, mb):
 STORE_POLICY = " nt" if os.environ.get("L4W_STORE_NT", "1") == "1" else ""
 RES_AHEAD = os.environ.get("L4W_RES_AHEAD", "1") == "1"      # residual rows of the next block pair requested in front of this pair's stores
 OPTS = set()       # probe variants (timing only, results wrong): "nomfma", "noreads", "noglds", "nostore", "laxvm", "noepi"
-CFG = dict(narrow=False, res=False, bias=False)     # what the body being generated supports (see VARIANTS)
+CFG = dict(narrow=False, res=False, bias=False, f16=False)     # what the body being generated supports (see VARIANTS); f16: fp16 I/O
+
+
+# The I/O type of a body.  fp16 substitutes one instruction for one (so the placement between the MFMAs carries over): the MFMA
+# and the packed conversion by mnemonic, the bf16 unpack pair (shift / mask) by v_cvt_f32_f16 and its SDWA form on the high half.
+def mfma_op():
+    return "v_mfma_f32_32x32x16_f16" if CFG.get("f16") else "v_mfma_f32_32x32x16_bf16"
+
+
+def cvt_pk_op():
+    return "v_cvt_pk_f16_f32" if CFG.get("f16") else "v_cvt_pk_bf16_f32"
+
+
+def unpack16(e, lo, hi, src):
+    """the two 16-bit halves of v[src] as fp32 -> v[lo], v[hi]"""
+    if CFG.get("f16"):
+        e.ins(f"v_cvt_f32_f16 {v(lo)}, {v(src)}")
+        e.ins(f"v_cvt_f32_f16_sdwa {v(hi)}, {v(src)} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1")
+    else:
+        e.ins(f"v_lshlrev_b32 {v(lo)}, 16, {v(src)}")
+        e.ins(f"v_and_b32 {v(hi)}, 0xffff0000, {v(src)}")
 
 
 class Emit:
@@ -231,7 +252,7 @@ class Emit:
         if "nomfma" in OPTS:
             return
         src = "0" if zero else a(c, 16)
-        self.ins(f"v_mfma_f32_32x32x16_bf16 {a(c, 16)}, {v(fa, 4)}, {v(fb, 4)}, {src}")
+        self.ins(f"{mfma_op()} {a(c, 16)}, {v(fa, 4)}, {v(fb, 4)}, {src}")
         self.mfma_at[c] = self.n_inst - 1
 
 
@@ -389,8 +410,7 @@ def tile_operand_finish(e, nbw):
     if CFG["res"]:
         for nbp in range(nbw // 2):
             for d in range(4):
-                e.ins(f"v_lshlrev_b32 {v(RM.G + 8 * nbp + 2 * d)}, 16, {v(RM.GRAW + 4 * nbp + d)}")
-                e.ins(f"v_and_b32 {v(RM.G + 8 * nbp + 2 * d + 1)}, 0xffff0000, {v(RM.GRAW + 4 * nbp + d)}")
+                unpack16(e, RM.G + 8 * nbp + 2 * d, RM.G + 8 * nbp + 2 * d + 1, RM.GRAW + 4 * nbp + d)
 
 
 def bias_mfmas(e, nbw):
@@ -469,13 +489,12 @@ def epilogue_rows(e, nbp, mb, res16=None):
             for d in range(4):
                 if CFG["res"]:
                     gq = RM.G + 8 * nbp + 2 * d
-                    e.ins(f"v_lshlrev_b32 {v(t0)}, 16, {v(res + d)}")
-                    e.ins(f"v_and_b32 {v(t1)}, 0xffff0000, {v(res + d)}")
+                    unpack16(e, t0, t1, res + d)
                     e.ins(f"v_fma_f32 {v(t0)}, {v(gq)}, {v(row + 2 * d)}, {v(t0)}")
                     e.ins(f"v_fma_f32 {v(t1)}, {v(gq + 1)}, {v(row + 2 * d + 1)}, {v(t1)}")
-                    e.ins(f"v_cvt_pk_bf16_f32 {v(pk + d)}, {v(t0)}, {v(t1)}")
+                    e.ins(f"{cvt_pk_op()} {v(pk + d)}, {v(t0)}, {v(t1)}")
                 else:
-                    e.ins(f"v_cvt_pk_bf16_f32 {v(pk + d)}, {v(row + 2 * d)}, {v(row + 2 * d + 1)}")
+                    e.ins(f"{cvt_pk_op()} {v(pk + d)}, {v(row + 2 * d)}, {v(row + 2 * d + 1)}")
         return [run, lambda: e.store(pk, RM.S_SO + mb * 4 + g, nbp * 128)]
     ops = load(0) + load(1)
     for g in range(4):
@@ -686,7 +705,7 @@ def clobbers():
 def generate(cfg=None):
     """-> (asm text with %N operands and %= label ids, T = vector-memory ops a LAST step issues behind its direct-to-LDS batch)"""
     global CFG
-    CFG = dict(narrow=False, res=False, bias=False)
+    CFG = dict(narrow=False, res=False, bias=False, f16=False)
     CFG.update(cfg or {})
     out = []
 
@@ -773,14 +792,30 @@ def emit_inc(path):
             fh.write("    " + ", ".join(f'"{c}"' for c in cl[i:i + 16]) + (", \\\n" if i + 16 < len(cl) else "\n"))
 
 
+def emit_inc_f16(path):
+    """the fp16 bodies of the four kernel variants (no probe variants); operand and clobber lists are those of linear4w_body.inc"""
+    with open(path, "w") as fh:
+        fh.write("// GENERATED by zigma_amd/csrc/gen/linear4w_gen.py --emit-f16 — a build product (zigma_amd/build.py writes it), do not edit or commit.\n")
+        fh.write("// The main loop of linear4w_kernel for fp16 operands: linear4w_body.inc with the f16 MFMA / conversions substituted one for one.\n")
+        for name, cfg in VARIANTS.items():
+            lines, _ = generate(dict(cfg, f16=True))
+            fh.write(f"#define ZIGMA_LINEAR4W_F16_BODY{name} \\\n")
+            for ln in lines:
+                fh.write(f'    "{ln}\\n" \\\n')
+            fh.write("    \"\"\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--emit", action="store_true")
+    ap.add_argument("--emit-f16", action="store_true")
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--stats", action="store_true")
     args = ap.parse_args()
     if args.emit:
         emit_inc(os.path.join(os.path.dirname(HERE), "linear4w_body.inc"))
+    if args.emit_f16:
+        emit_inc_f16(os.path.join(os.path.dirname(HERE), "linear4w_body_f16.inc"))
     if args.stats:
         for name, cfg in VARIANTS.items():
             lines, T = generate(cfg)

@@ -1,7 +1,7 @@
 """Simulator / checker for the generated body of linear4w_kernel (see linear4w_gen.py).  TEST INFRASTRUCTURE.
 
 Executes the SAME text the assembler gets, for the 4 waves of one workgroup, with numpy as the 64 lanes:
-  * functional: SGPR / VGPR / AGPR files, SCC, M0, LDS bytes, global memory, MFMA 32x32x16 bf16, the packed conversion;
+  * functional: SGPR / VGPR / AGPR files, SCC, M0, LDS bytes, global memory, MFMA 32x32x16 bf16 / f16, the packed conversions, the f16 widening pair;
   * synchronisation discipline (what a correct run on hardware relies on, not what happens to work):
       - a register written by an LDS read / vector load is unusable until an s_waitcnt covers it (both counters retire in order);
       - an LDS granule filled by a direct-to-LDS load is readable by the issuing wave after its covering vmcnt wait, by the other
@@ -26,6 +26,15 @@ def f32_to_bf16(x):
     u = x.astype(np.float32).view(np.uint32).astype(np.uint64)
     r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32)
     return (r & 0xFFFF).astype(np.uint32)
+
+
+def f16_to_f32(u16):
+    return u16.astype(np.uint16).view(np.float16).astype(np.float32)
+
+
+def f32_to_f16(x):
+    """round to nearest even (numpy's float16 conversion), as bits"""
+    return x.astype(np.float32).astype(np.float16).view(np.uint16).astype(np.uint32)
 
 
 class SimError(Exception):
@@ -222,8 +231,18 @@ class Wave:
         elif op == "v_cvt_pk_bf16_f32":
             lo, hi = self.rv(args[1]).view(np.float32), self.rv(args[2]).view(np.float32)
             self.wv(args[0], f32_to_bf16(lo) | (f32_to_bf16(hi) << 16))
+        elif op == "v_cvt_pk_f16_f32":
+            lo, hi = self.rv(args[1]).view(np.float32), self.rv(args[2]).view(np.float32)
+            self.wv(args[0], f32_to_f16(lo) | (f32_to_f16(hi) << 16))
+        elif op == "v_cvt_f32_f16":                      # low half of the source
+            self.wv(args[0], f16_to_f32(self.rv(args[1]) & 0xFFFF).view(np.uint32))
+        elif op == "v_cvt_f32_f16_sdwa":                 # high half (the generator emits only src0_sel:WORD_1, whole-dword destination)
+            assert "src0_sel:WORD_1" in text and "dst_sel:DWORD" in text, text
+            self.wv(args[0], f16_to_f32(self.rv(args[1]) >> 16).view(np.uint32))
         elif op == "v_mfma_f32_32x32x16_bf16":
             self.mfma(args, text)
+        elif op == "v_mfma_f32_32x32x16_f16":
+            self.mfma(args, text, to_f32=f16_to_f32)
         # ---- LDS ----------------------------------------------------------------------------------------
         elif op == "ds_read_b128":
             d = self.rng(args[0])
@@ -368,7 +387,7 @@ class Wave:
         self.sh["last_read"].setdefault(g, {})[self.wid] = self.interval
         return g
 
-    def mfma(self, args, text):
+    def mfma(self, args, text, to_f32=bf16_to_f32):
         d, fa, fb = self.rng(args[0]), self.rng(args[1]), self.rng(args[2])
         assert d[0] == "a" and d[2] == 16 and fa[2] == 4 and fb[2] == 4
         self.chk_v(fa[1], 4, text)
@@ -376,7 +395,7 @@ class Wave:
 
         def frag(base):          # (64 lanes, 8 bf16) -> matrix [row = l % 32][k = 8 (l // 32) + e]
             raw = np.stack([self.V[base + k] for k in range(4)], 1)      # (64, 4) u32
-            lo, hi = bf16_to_f32((raw & 0xFFFF).astype(np.uint16)), bf16_to_f32((raw >> 16).astype(np.uint16))
+            lo, hi = to_f32((raw & 0xFFFF).astype(np.uint16)), to_f32((raw >> 16).astype(np.uint16))
             e8 = np.stack([lo, hi], 2).reshape(64, 8)
             M = np.zeros((32, 16), np.float32)
             M[:, 0:8], M[:, 8:16] = e8[:32], e8[32:]
@@ -457,7 +476,7 @@ def run_workgroup(lines, operands_for_wave, mem, order=(0, 1, 2, 3)):
 # ------------------------------------------------------------------------------------------------------------------
 # a problem instance, exactly as csrc/linear4w.hip sets the operands up
 # ------------------------------------------------------------------------------------------------------------------
-def lane_operands(wave, w_pitch, x_pitch, o_pitch, lds_base=0):
+def lane_operands(wave, w_pitch, x_pitch, o_pitch, lds_base=0, f16=False):
     lane = np.arange(64)
     j, kh = lane & 31, lane >> 5
     wn, wm = wave & 1, wave >> 1
@@ -476,7 +495,7 @@ def lane_operands(wave, w_pitch, x_pitch, o_pitch, lds_base=0):
         scrr=lds_base + 2 * 65536 + wave * 8192 + t8 * 256 + ((u ^ t8) << 5),
         stoff=t8 * o_pitch + u * 16,
         bias_voff=np.where(lane < 32, j * 2, 0x7FFF0000),
-        ones0=np.where(lane < 32, 0x3F80, 0),
+        ones0=np.where(lane < 32, 0x3C00 if f16 else 0x3F80, 0),             # 1.0 in the operand type
     )
 
 
@@ -486,16 +505,17 @@ def simulate(M, N, K, n_wg=8, wg=0, seed=0, order=(0, 1, 2, 3), gen=None, cfg=No
     import linear4w_gen as G
     cfg = dict(cfg or {})
     lines, _ = gen or G.generate(cfg)
-    res_on, bias_on = bool(cfg.get("res")), bool(cfg.get("bias"))
+    res_on, bias_on, f16 = bool(cfg.get("res")), bool(cfg.get("bias")), bool(cfg.get("f16"))
+    to_bits, to_f32 = (f32_to_f16, f16_to_f32) if f16 else (f32_to_bf16, bf16_to_f32)
     rng = np.random.default_rng(seed)
-    rb = lambda a: f32_to_bf16(a.astype(np.float32)).astype(np.uint16)
+    rb = lambda a: to_bits(a.astype(np.float32)).astype(np.uint16)
     x = rb(rng.standard_normal((M, K)))
     w = rb(rng.standard_normal((N, K)) * K ** -0.5)
     nb_ = M // rows_per_batch
     res = rb(rng.standard_normal((M, N)))
     gate = rb(rng.standard_normal((nb_, N)))
     bias = rb(rng.standard_normal(N) * 0.5)
-    out = np.full((M, N), 0x7FC0, np.uint16)            # NaN pattern: untouched outputs show
+    out = np.full((M, N), 0x7E00 if f16 else 0x7FC0, np.uint16)            # NaN pattern: untouched outputs show
     mem = Memory()
     WB, XB, OB, RB, GB, BB = 0x10000000, 0x20000000, 0x40000000, 0x60000000, 0x70000000, 0x78000000
     mem.add(WB, w.view(np.uint8).reshape(-1))
@@ -523,7 +543,7 @@ def simulate(M, N, K, n_wg=8, wg=0, seed=0, order=(0, 1, 2, 3), gen=None, cfg=No
               rpb_shift=int(np.log2(rows_per_batch)), bias_lo=BB & 0xFFFFFFFF, bias_hi=BB >> 32)
 
     def operands_for_wave(wv):
-        lo = lane_operands(wv, K * 2, K * 2, N * 2)
+        lo = lane_operands(wv, K * 2, K * 2, N * 2, f16=f16)
         toks, preset = [], {}
         nv, ns = 0, 0
         for c, name in G.OPERANDS:
@@ -545,7 +565,7 @@ def simulate(M, N, K, n_wg=8, wg=0, seed=0, order=(0, 1, 2, 3), gen=None, cfg=No
         return toks, preset
 
     waves, shared = run_workgroup(lines, operands_for_wave, mem, order)
-    f = lambda a: bf16_to_f32(a).astype(np.float64)
+    f = lambda a: to_f32(a).astype(np.float64)
     val = f(x) @ f(w).T
     if bias_on:
         val = val + f(bias)[None, :]
@@ -564,7 +584,7 @@ def simulate(M, N, K, n_wg=8, wg=0, seed=0, order=(0, 1, 2, 3), gen=None, cfg=No
     dup = [a for a, c in shared["stored"].items() if c != 1]
     if dup:
         raise SimError(f"{len(dup)} output pieces stored more than once")
-    return bf16_to_f32(out), owned, ref, waves, n_mfma
+    return to_f32(out), owned, ref, waves, n_mfma
 
 
 def check(M, N, K, n_wg=8, wg=0, order=(0, 1, 2, 3), seed=0, gen=None, cfg=None, rows_per_batch=256):
@@ -578,7 +598,7 @@ def check(M, N, K, n_wg=8, wg=0, order=(0, 1, 2, 3), seed=0, gen=None, cfg=None,
         raise SimError("outputs outside this workgroup's tiles were written")
     got, want = out[owned].astype(np.float64), ref[owned]
     err = np.linalg.norm(got - want) / np.linalg.norm(want)
-    if not err < 3e-3:
+    if not err < (3e-3 / 8 if (cfg or {}).get("f16") else 3e-3):          # fp16: three more mantissa bits
         raise SimError(f"rel err {err:.3e}")
     for wv in waves:
         if wv.stats["mfma"] != n_mfma:

@@ -1,4 +1,5 @@
-// Dense projections of the ZigMa block on the CDNA4 matrix cores: out = x @ W^T (+ bias) (+ SiLU on a column range), bf16.
+// Dense projections of the ZigMa block on the CDNA4 matrix cores: out = x @ W^T (+ bias) (+ SiLU on a column range), bf16 or fp16
+// (the I/O type is a template parameter: the MFMA, the unpacking of bias / residual / gate and the output pack follow it).
 // C ABI: zigma_linear_fwd.
 //
 // Replaces the cuBLAS GEMMs behind F.linear at the reference's call sites Mamba.in_proj (mamba_simple.py:290-294),
@@ -44,7 +45,7 @@ constexpr int kLinBM = 256, kLinBK = 64;
 // RES: out = residual + gate * bf16(value) (CrossAttention's `hidden + gate_msa * to_out(...)`, reference model_zigma.py:447-449; the
 // projection result is rounded to bf16 first, as the reference's bf16 tensor is): the residual rows are fetched with the store
 // pattern (16 bytes per lane, 8 tokens x 128 B per instruction), `gate8` = this lane's 8 gate values (bf16).
-template <int MB, int NB, bool RES = false>
+template <int MB, int NB, bool RES = false, typename T = BF16>
 __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], unsigned char *scr, const uint16_t *s_bias,
                                                 const rsrc_t o_rs, const int64_t o_pitch, const int n_wave0, const int silu_from_col,
                                                 const int lane, const rsrc_t r_rs, const int64_t r_pitch, const uint4 gate8) {
@@ -78,10 +79,10 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]));
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    v[q * 4 + 0] += __uint_as_float(bq[q].x << 16);
-                    v[q * 4 + 1] += __uint_as_float(bq[q].x & 0xffff0000u);
-                    v[q * 4 + 2] += __uint_as_float(bq[q].y << 16);
-                    v[q * 4 + 3] += __uint_as_float(bq[q].y & 0xffff0000u);
+                    v[q * 4 + 0] += lo16<T>(bq[q].x);
+                    v[q * 4 + 1] += hi16<T>(bq[q].x);
+                    v[q * 4 + 2] += lo16<T>(bq[q].y);
+                    v[q * 4 + 3] += hi16<T>(bq[q].y);
                 }
             }
             if (n0 >= silu_from_col) {                                                         // (silu_from_col % 32 == 0)
@@ -91,8 +92,8 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 uint2 pk;
-                pk.x = static_cast<uint32_t>(from_float<BF16>(v[q * 4])) | (static_cast<uint32_t>(from_float<BF16>(v[q * 4 + 1])) << 16);
-                pk.y = static_cast<uint32_t>(from_float<BF16>(v[q * 4 + 2])) | (static_cast<uint32_t>(from_float<BF16>(v[q * 4 + 3])) << 16);
+                pk.x = pack2<T>(v[q * 4], v[q * 4 + 1]);
+                pk.y = pack2<T>(v[q * 4 + 2], v[q * 4 + 3]);
                 // (inline asm: a ds_write the compiler can see makes it drain vmcnt — i.e. the whole load ring — first,
                 // because an LDS-DMA in flight might target the same bytes; it cannot: the scratch is outside the ring)
                 typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -113,10 +114,9 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = __builtin_fmaf(__uint_as_float(gq[e] << 16), __uint_as_float(row[i][e] << 16), __uint_as_float(res[i][e] << 16));
-                    const float hi = __builtin_fmaf(__uint_as_float(gq[e] & 0xffff0000u), __uint_as_float(row[i][e] & 0xffff0000u),
-                                                    __uint_as_float(res[i][e] & 0xffff0000u));
-                    row[i][e] = static_cast<uint32_t>(from_float<BF16>(lo)) | (static_cast<uint32_t>(from_float<BF16>(hi)) << 16);
+                    const float lo = __builtin_fmaf(lo16<T>(gq[e]), lo16<T>(row[i][e]), lo16<T>(res[i][e]));
+                    const float hi = __builtin_fmaf(hi16<T>(gq[e]), hi16<T>(row[i][e]), hi16<T>(res[i][e]));
+                    row[i][e] = pack2<T>(lo, hi);
                 }
         }
 #pragma unroll
@@ -146,7 +146,7 @@ __device__ __forceinline__ void wait_vm(int n) {
 // was issued after the batch this k-step needs": the younger load batch (NST == 3) and, during the first NST - 1 k-steps
 // after an epilogue, that epilogue's stores — the store acknowledgements are never waited for on the critical path
 // (__syncthreads() would drain them: measured ~2 us per tile).
-template <int WN_, int NST, bool HAS_BIAS, bool RES = false>
+template <int WN_, int NST, bool HAS_BIAS, bool RES = false, typename T = BF16>
 __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_params_t p, const int tiles_m, const int tiles_n) {
     constexpr int BM = kLinBM, BN = 64 * WN_, WM_ = 8 / WN_, MB = BM / WM_ / 32, NB = 2;
     constexpr int ROWS = BN + BM, STAGE = ROWS * 128;            // bytes per stage: W rows first, then token rows
@@ -271,15 +271,15 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
             }
             const unsigned char *sb = smem + (g % NST) * STAGE;
             // fragments one k-substep ahead of the MFMAs that use them (the LDS latency hides under the previous 8 MFMAs)
-            bf16x8 a[2][NB], b[2][MB];
-            auto frags = [&](int ks, bf16x8 (&fa)[NB], bf16x8 (&fb)[MB]) {
+            frag8_t<T> a[2][NB], b[2][MB];
+            auto frags = [&](int ks, frag8_t<T> (&fa)[NB], frag8_t<T> (&fb)[MB]) {
                 const int off = ((((ks << 1) | kh) ^ sw) << 4);
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb)
-                    fa[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(sb + a_row0 + nb * 32 * 128 + off));
+                    fa[nb] = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(sb + a_row0 + nb * 32 * 128 + off));
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb)
-                    fb[mb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(sb + b_row0 + mb * 32 * 128 + off));
+                    fb[mb] = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(sb + b_row0 + mb * 32 * 128 + off));
             };
             if (dbg & 0x100) continue;
             frags(0, a[0], b[0]);
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
                 for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
                     for (int mb = 0; mb < MB; ++mb)
-                        acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks & 1][nb], b[ks & 1][mb], acc[nb][mb], 0, 0, 0);
+                        acc[nb][mb] = mfma_32x32x16<T>(a[ks & 1][nb], b[ks & 1][mb], acc[nb][mb]);
             }
             // Pin the order hipcc would otherwise collapse to [all reads of a sub-step -> wait -> its MFMAs]: the NB + MB reads of
             // sub-step ks + 1 are issued one by one between the first MFMAs of sub-step ks (masks: 0x100 DS read, 0x008 MFMA).
@@ -335,11 +335,11 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
                                               rows_here > 0 ? (rows_here < BM / WM_ ? rows_here : BM / WM_) * r_pitch - n_w * 2 : 0);
                 const int64_t bsm = m_tile / p.rows_per_batch;
                 const uint4 gate8 = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(p.gate) + bsm * p.gate_batch_stride + n_w + (lane & 7) * 8);
-                linear_epilogue<MB, NB, true>(acc, smem + ((g - 1) % NST) * STAGE + wave * 4096,
+                linear_epilogue<MB, NB, true, T>(acc, smem + ((g - 1) % NST) * STAGE + wave * 4096,
                                               HAS_BIAS ? reinterpret_cast<const uint16_t *>(smem + NST * STAGE) : nullptr, o_rs, o_pitch, n_w,
                                               p.silu_from_col, lane, r_rs, r_pitch, gate8);
             } else {
-                linear_epilogue<MB, NB>(acc, smem + ((g - 1) % NST) * STAGE + wave * 4096,
+                linear_epilogue<MB, NB, false, T>(acc, smem + ((g - 1) % NST) * STAGE + wave * 4096,
                                         HAS_BIAS ? reinterpret_cast<const uint16_t *>(smem + NST * STAGE) : nullptr, o_rs, o_pitch, nt * BN + wn * 64,
                                         p.silu_from_col, lane, o_rs, 0, uint4{});      // (no residual: the last three are not read)
             }
@@ -369,7 +369,7 @@ extern "C" int zigma_linear_fwd(const zigma_linear_params_t *pp, void *stream_) 
     if (p.flags & ~0xf7ff00) return ZIGMA_ERR_UNSUPPORTED;     // 0x4000: the weight-stationary kernel; 0x8000: the few-token kernel; 0x100 ... 0x1000: timing / A-B probes (tools/linear_probe.py); 0x2000: the 8-wave kernel; 0x10000 .. 0x50000: probes of the 4-wave kernel (probe builds only)
     if (p.m == 0) return ZIGMA_OK;
     if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
+    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
     if (p.k % kLinBK != 0 || p.n % 128 != 0 || p.m % 8 != 0) return ZIGMA_ERR_SHAPE;
     if (p.m * p.x_row_stride * 2 > 0x7fffffff || static_cast<int64_t>(p.n) * p.w_row_stride * 2 > 0x7fffffff ||
         256 * p.out_row_stride * 2 > 0x7fffffff)
@@ -396,14 +396,13 @@ extern "C" int zigma_linear_fwd(const zigma_linear_params_t *pp, void *stream_) 
     if (n_tiles > 0x7fffffff) return ZIGMA_ERR_SHAPE;
     int grid = 256;                                  // one persistent workgroup per CU; multiples of 8 keep the XCD map
     if (n_tiles < grid) grid = static_cast<int>((n_tiles + 7) / 8 * 8);
-#define ZIGMA_LIN(W_, S_, B_) hipLaunchKernelGGL((linear_tn_kernel<W_, S_, B_>), dim3(grid), dim3(512), 0, stream, p, tiles_m, tiles_n)
-    if (wide) { if (p.bias) ZIGMA_LIN(4, 2, true); else ZIGMA_LIN(4, 2, false); }
-    else if (p.flags & 0x800) { if (p.bias) ZIGMA_LIN(2, 2, true); else ZIGMA_LIN(2, 2, false); }      // 0x800: two stages (probe)
-    else if (p.residual) {
-        if (p.bias) hipLaunchKernelGGL((linear_tn_kernel<2, 3, true, true>), dim3(grid), dim3(512), 0, stream, p, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((linear_tn_kernel<2, 3, false, true>), dim3(grid), dim3(512), 0, stream, p, tiles_m, tiles_n);
-    }
-    else { if (p.bias) ZIGMA_LIN(2, 3, true); else ZIGMA_LIN(2, 3, false); }
+#define ZIGMA_LIN(W_, S_, B_, R_) hipLaunchKernelGGL((linear_tn_kernel<W_, S_, B_, R_, T>), dim3(grid), dim3(512), 0, stream, p, tiles_m, tiles_n)
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, {
+        if (wide) { if (p.bias) ZIGMA_LIN(4, 2, true, false); else ZIGMA_LIN(4, 2, false, false); }
+        else if (p.flags & 0x800) { if (p.bias) ZIGMA_LIN(2, 2, true, false); else ZIGMA_LIN(2, 2, false, false); }      // 0x800: two stages (probe)
+        else if (p.residual) { if (p.bias) ZIGMA_LIN(2, 3, true, true); else ZIGMA_LIN(2, 3, false, true); }
+        else { if (p.bias) ZIGMA_LIN(2, 3, true, false); else ZIGMA_LIN(2, 3, false, false); }
+    })
 #undef ZIGMA_LIN
     set_last_kernel(wide ? "linear_tn_256x256" : "linear_tn_256x128");
     return check_launch();

@@ -1,4 +1,4 @@
-// linear4w: dense projections out = x @ W^T (bf16 in, fp32 accumulate, bf16 out) with ONE wave per SIMD — in_proj, out_proj
+// linear4w: dense projections out = x @ W^T (bf16 or fp16 in, fp32 accumulate, same type out) with ONE wave per SIMD — in_proj, out_proj
 // (mamba_simple.py:290-294, selective_scan_interface.py:365) and to_q / to_out (model_zigma.py:104-135) of the ZigMa block,
 // reference F.linear; with the block's gated branch add `residual + gate * (x W^T + bias)` (model_zigma.py:441-449) in the epilogue.
 //
@@ -17,6 +17,7 @@
 // elements), samples of 2^i >= 128 rows; a bias only together with the gated residual (to_out), n <= 8192.
 #include "zigma_common.h"
 #include "linear4w_body.inc"
+#include "linear4w_body_f16.inc"      // the same loops for fp16 operands (generator cfg f16=True; written by zigma_amd/build.py, not committed): bodies only
 
 namespace zigma {
 
@@ -24,7 +25,8 @@ typedef __attribute__((address_space(3))) unsigned char *lds4w_ptr_t;
 
 // EPI: 0 = 256-wide tiles only, no epilogue operands (in_proj, to_q); 1 = + narrow tiles; 2 = + gated residual; 3 = + bias.
 // VARIANT > 0: timing probes of tools/linear4w_probe.py (only in a library built with -DZIGMA_LINEAR4W_PROBES, EPI 0)
-template <int EPI, int VARIANT>
+// T: the I/O type (BF16 / F16) picks the generated body and the 1.0 of the bias product; everything else is type-blind
+template <int EPI, int VARIANT, typename T = BF16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int n_wide, const int n_tiles) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[163840];
@@ -61,7 +63,7 @@ void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int
     const unsigned scrw_base = lds_base + 2 * 65536 + wave * 8192 + j * 256 + kh * 16, j7 = j & 7;
     const unsigned scrr = lds_base + 2 * 65536 + wave * 8192 + t8 * 256 + ((u ^ t8) << 5);
     const unsigned stoff = t8 * o_pitch + u * 16;
-    const unsigned bias_voff = lane < 32 ? j * 2 : 0x7fff0000u, ones0 = lane < 32 ? 0x3f80u : 0u;
+    const unsigned bias_voff = lane < 32 ? j * 2 : 0x7fff0000u, ones0 = lane < 32 ? (T::id == ZIGMA_F16 ? 0x3c00u : 0x3f80u) : 0u;
     const void *w_ptr = p.w, *x_ptr = p.x;
     void *out_ptr = p.out;
     const uint64_t res_a = reinterpret_cast<uint64_t>(p.residual), gate_a = reinterpret_cast<uint64_t>(p.gate), bias_a = reinterpret_cast<uint64_t>(p.bias);
@@ -77,7 +79,14 @@ void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int
                                            out_ptr, w_pitch, x_pitch, o_pitch, dims, my_tiles, steps, tile0, wave_lds, res_lo, res_hi,        \
                                            gate_lo, gate_hi, gate_bstride, rpb_shift, bias_lo, bias_hi)                                       \
                  : ZIGMA_LINEAR4W_CLOBBERS)
-    if constexpr (EPI == 1) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_BODY_N); }
+    if constexpr (T::id == ZIGMA_F16) {
+        static_assert(VARIANT == 0, "the timing probes exist for bf16 only");
+        if constexpr (EPI == 1) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_F16_BODY_N); }
+        else if constexpr (EPI == 2) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_F16_BODY_NR); }
+        else if constexpr (EPI == 3) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_F16_BODY_NRB); }
+        else { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_F16_BODY); }
+    }
+    else if constexpr (EPI == 1) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_BODY_N); }
     else if constexpr (EPI == 2) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_BODY_NR); }
     else if constexpr (EPI == 3) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_BODY_NRB); }
     else if constexpr (VARIANT == 0) { ZIGMA_L4W_ASM(ZIGMA_LINEAR4W_BODY); }
@@ -128,6 +137,16 @@ int launch_linear4w(const zigma_linear_params_t &p, hipStream_t stream) {
     const int n_tiles = static_cast<int>((p.m / 256) * tiles_n);
     const dim3 grid(256), block(256);
 #define ZIGMA_L4W(E_, V_) hipLaunchKernelGGL((linear4w_kernel<E_, V_>), grid, block, 0, stream, p, tiles_n, n_wide, n_tiles)
+#define ZIGMA_L4W_F16(E_) hipLaunchKernelGGL((linear4w_kernel<E_, 0, F16>), grid, block, 0, stream, p, tiles_n, n_wide, n_tiles)
+    if (p.dtype == ZIGMA_F16) {
+        if ((p.flags >> 16) & 7) return ZIGMA_ERR_UNSUPPORTED;              // (probe variants: bf16 only)
+        switch (linear4w_variant(p)) {
+            case 1: ZIGMA_L4W_F16(1); break;
+            case 2: ZIGMA_L4W_F16(2); break;
+            case 3: ZIGMA_L4W_F16(3); break;
+            default: ZIGMA_L4W_F16(0);
+        }
+    } else
     switch (linear4w_variant(p)) {
         case 1: ZIGMA_L4W(1, 0); break;
         case 2: ZIGMA_L4W(2, 0); break;
@@ -146,6 +165,7 @@ int launch_linear4w(const zigma_linear_params_t &p, hipStream_t stream) {
                 default: ZIGMA_L4W(0, 0);
             }
     }
+#undef ZIGMA_L4W_F16
 #undef ZIGMA_L4W
     set_last_kernel(p.n % 256 ? "linear4w_256x256+128" : "linear4w_256x256");
     return check_launch();

@@ -15,7 +15,7 @@
 //   per k-step behind a counted s_waitcnt vmcnt.
 //   Epilogue: accumulators -> bf16 -> the wave's LDS tile (32 tokens x 32 NBLK features, 16-byte padded pitch) -> 16-byte stores along
 //   the token rows.
-// Limits: bf16, no activation (bias and the gated residual: template flag EPI), k % 64 == 0 and k >= 128, m % 128 == 0, n % (32 NBLK) == 0 for NBLK = 5, 6 or 4 (tried in that order).
+// Limits: bf16 or fp16 (template parameter T), no activation (bias and the gated residual: template flag EPI), k % 64 == 0 and k >= 128, m % 128 == 0, n % (32 NBLK) == 0 for NBLK = 5, 6 or 4 (tried in that order).
 #include "scan_helpers.h"
 
 namespace zigma {
@@ -32,7 +32,7 @@ template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_wai
 
 // EPI: + bias (fp32, before the single rounding) and / or the block's gated branch add out = residual + gate[sample] * bf16(x W^T + bias) (reference
 // model_zigma.py:441-449) — the arithmetic and rounding points of linear_tn_kernel's epilogue (csrc/linear.hip), so the two agree bit for bit.
-template <int NBLK, bool EPI = false>
+template <int NBLK, bool EPI = false, typename T = BF16>
 __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_params_t p, const int tiles_n) {
     constexpr int BN = 32 * NBLK, ROWS = BN + kBM, STAGE = ROWS * 128;        // bytes per stage: W rows first, then token rows
     constexpr int NLD = ROWS / 32;                                            // direct-to-LDS loads per wave and stage (8 rows each, 4 waves)
@@ -88,13 +88,13 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
         const unsigned char *sb = smem + (kt % kNST) * STAGE;
         // fragments one k-substep ahead of the MFMAs that use them, and the direct-to-LDS pieces of k-step kt + 3 spread between the MFMAs of the
         // first three sub-steps: with one wave per SIMD nothing else covers an LDS round trip or the ~55 cycles a piece takes to issue
-        bf16x8 fa[2][NBLK], fb[2];
-        auto frags = [&](int ks, bf16x8 (&a)[NBLK], bf16x8 &b) {
+        frag8_t<T> fa[2][NBLK], fb[2];
+        auto frags = [&](int ks, frag8_t<T> (&a)[NBLK], frag8_t<T> &b) {
             const int off = ((((ks << 1) | kh) ^ sw) << 4);
-            b = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(sb + b_row0 + off));
+            b = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(sb + b_row0 + off));
 #pragma unroll
             for (int nb = 0; nb < NBLK; ++nb)
-                a[nb] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(sb + a_row0 + nb * 32 * 128 + off));
+                a[nb] = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(sb + a_row0 + nb * 32 * 128 + off));
         };
         frags(0, fa[0], fb[0]);
 #pragma unroll
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
             for (int i = ks * PPS; i < (ks + 1) * PPS && i < NLD && ks < 3; ++i) issue_piece(kt + kNST - 1, i);
 #pragma unroll
             for (int nb = 0; nb < NBLK; ++nb)
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ks & 1][nb], fb[ks & 1], acc[nb], 0, 0, 0);
+                acc[nb] = mfma_32x32x16<T>(fa[ks & 1][nb], fb[ks & 1], acc[nb]);
         }
         // pin the order (masks: 0x100 DS read, 0x008 MFMA): behind every MFMA of sub-steps 0 .. 2 one fragment read of the next sub-step (two
         // behind the first); the direct-to-LDS pieces stay where the source puts them, between the sub-steps
@@ -136,14 +136,14 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
             float v[4] = {acc[nb][q * 4], acc[nb][q * 4 + 1], acc[nb][q * 4 + 2], acc[nb][q * 4 + 3]};
             if (EPI && biasp) {
                 const uint2 bq = *reinterpret_cast<const uint2 *>(biasp + nt * BN + nb * 32 + q * 8 + kh * 4);
-                v[0] += __uint_as_float(bq.x << 16);
-                v[1] += __uint_as_float(bq.x & 0xffff0000u);
-                v[2] += __uint_as_float(bq.y << 16);
-                v[3] += __uint_as_float(bq.y & 0xffff0000u);
+                v[0] += lo16<T>(bq.x);
+                v[1] += hi16<T>(bq.x);
+                v[2] += lo16<T>(bq.y);
+                v[3] += hi16<T>(bq.y);
             }
             uint2 pk;
-            pk.x = static_cast<uint32_t>(from_float<BF16>(v[0])) | (static_cast<uint32_t>(from_float<BF16>(v[1])) << 16);
-            pk.y = static_cast<uint32_t>(from_float<BF16>(v[2])) | (static_cast<uint32_t>(from_float<BF16>(v[3])) << 16);
+            pk.x = pack2<T>(v[0], v[1]);
+            pk.y = pack2<T>(v[2], v[3]);
             *reinterpret_cast<uint2 *>(scr + j * PITCH + (nb * 32 + q * 8 + kh * 4) * 2) = pk;
         }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -173,9 +173,9 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
                 unsigned oo[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = __builtin_fmaf(__uint_as_float(gg[e] << 16), __uint_as_float(vv[e] << 16), __uint_as_float(rr[e] << 16));
-                    const float hi = __builtin_fmaf(__uint_as_float(gg[e] & 0xffff0000u), __uint_as_float(vv[e] & 0xffff0000u), __uint_as_float(rr[e] & 0xffff0000u));
-                    oo[e] = static_cast<uint32_t>(from_float<BF16>(lo)) | (static_cast<uint32_t>(from_float<BF16>(hi)) << 16);
+                    const float lo = __builtin_fmaf(lo16<T>(gg[e]), lo16<T>(vv[e]), lo16<T>(rr[e]));
+                    const float hi = __builtin_fmaf(hi16<T>(gg[e]), hi16<T>(vv[e]), hi16<T>(rr[e]));
+                    oo[e] = pack2<T>(lo, hi);
                 }
                 v = make_uint4(oo[0], oo[1], oo[2], oo[3]);
             }
@@ -210,9 +210,9 @@ int launch_linear_sm(const zigma_linear_params_t &p, hipStream_t stream) {
     const int tiles_n = p.n / (32 * nblk);
     const dim3 grid(static_cast<unsigned>((p.m / 128) * tiles_n)), block(256);
     const bool epi = p.bias || p.residual;
-#define ZIGMA_LSM(N_) do { if (epi) hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, true>), grid, block, 0, stream, p, tiles_n); \
-                           else hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, false>), grid, block, 0, stream, p, tiles_n); } while (0)
-    if (nblk == 5) ZIGMA_LSM(5); else if (nblk == 6) ZIGMA_LSM(6); else ZIGMA_LSM(4);
+#define ZIGMA_LSM(N_) do { if (epi) hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, true, T>), grid, block, 0, stream, p, tiles_n); \
+                           else hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, false, T>), grid, block, 0, stream, p, tiles_n); } while (0)
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, { if (nblk == 5) ZIGMA_LSM(5); else if (nblk == 6) ZIGMA_LSM(6); else ZIGMA_LSM(4); })
 #undef ZIGMA_LSM
     set_last_kernel(nblk == 5 ? "linear_sm_128x160" : nblk == 6 ? "linear_sm_128x192" : "linear_sm_128x128");
     return check_launch();

@@ -15,7 +15,7 @@
 //   Tokens: slices of 64 tokens x 128 k (16 KB, global_load_lds_dwordx4, 16-byte slots XOR-swizzled by the row on the source side)
 //   through a ring of eight; ONE counted vmcnt + barrier per two slices; B fragments by ds_read_b128, one k-group ahead.
 //   Epilogue per tile: accumulators -> bf16 -> the wave's LDS tile -> 16-byte stores (64 FB contiguous bytes per token and wave).
-// Limits: bf16, no bias / residual, SiLU only on whole 128-column groups from silu_from_col on; k = 512 or 640 with n % 256 == 0, or (FB = 1) k = 1280 / 1536
+// Limits: bf16 or fp16 (template parameter T: the MFMA mnemonic and the output pack), no bias / residual, SiLU only on whole 128-column groups from silu_from_col on; k = 512 or 640 with n % 256 == 0, or (FB = 1) k = 1280 / 1536
 // with n % 128 == 0; m % 512 == 0.
 // FB is a template parameter: the 128-feature form (FB = 1: one MFMA per fragment read, k up to 1280 — out_proj / to_out shapes) was
 // instantiated, is bit-identical too and does NOT beat the tiled kernel: out_proj shape 102 vs 97 us, to_out shape 48 vs 45 us, its
@@ -45,9 +45,6 @@ constexpr int kRing = 8;
 constexpr int kScrOff = kRing * kSlice;   // 131072: 4 waves x 8 KB of epilogue tiles (two token blocks)
 constexpr int kLds = kScrOff + 4 * 8192;  // 163840
 
-__device__ __forceinline__ unsigned pack_bf2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
-}
 // every LDS access and every direct-to-LDS load is inline assembly: hipcc must not see them (it would drain vmcnt before each read)
 template <int OFF>
 __device__ __forceinline__ void lds_rd(u32x4 &d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
@@ -66,15 +63,26 @@ __device__ __forceinline__ void wait_lgkm_n(const int n) {           // n folds 
 __device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // D += W . T^T for one 32 x 32 block; FIRST: the accumulator starts at zero (inline constant as srcC)
-template <bool FIRST>
+// (T picks the mnemonic: v_mfma_f32_32x32x16_bf16 / _f16 — same operands, same lane maps, same rate)
+template <bool FIRST, typename T>
 __device__ __forceinline__ void mfma_wa(f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in AGPRs
-    if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(acc) : "a"(w), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(b));
+    if constexpr (T::id == ZIGMA_F16) {
+        if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "a"(w), "v"(b));
+        else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(b));
+    } else {
+        if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(acc) : "a"(w), "v"(b));
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(b));
+    }
 }
-template <bool FIRST>
+template <bool FIRST, typename T>
 __device__ __forceinline__ void mfma_wv(f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in VGPRs
-    if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(acc) : "v"(w), "v"(b));
-    else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(w), "v"(b));
+    if constexpr (T::id == ZIGMA_F16) {
+        if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "v"(w), "v"(b));
+        else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(w), "v"(b));
+    } else {
+        if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&a"(acc) : "v"(w), "v"(b));
+        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(w), "v"(b));
+    }
 }
 
 template <int KG, int FB>
@@ -85,10 +93,10 @@ struct WFrags {        // fragment f = FB kg + fb; 256 AGPRs = two accumulator s
 };
 
 // (f and first fold to constants in the unrolled loop: one instruction survives)
-template <int KG, int FB>
+template <int KG, int FB, typename T>
 __device__ __forceinline__ void mfma_f(f32x16 &acc, const WFrags<KG, FB> &w, const int f, const bool first, const u32x4 &b) {
-    if (f < WFrags<KG, FB>::NA) { if (first) mfma_wa<true>(acc, w.a[f], b); else mfma_wa<false>(acc, w.a[f], b); }
-    else { if (first) mfma_wv<true>(acc, w.v[f - WFrags<KG, FB>::NA], b); else mfma_wv<false>(acc, w.v[f - WFrags<KG, FB>::NA], b); }
+    if (f < WFrags<KG, FB>::NA) { if (first) mfma_wa<true, T>(acc, w.a[f], b); else mfma_wa<false, T>(acc, w.a[f], b); }
+    else { if (first) mfma_wv<true, T>(acc, w.v[f - WFrags<KG, FB>::NA], b); else mfma_wv<false, T>(acc, w.v[f - WFrags<KG, FB>::NA], b); }
 }
 
 // PROBE (tools/linear_ws_probe.py; probe builds only): 0 = the kernel, 1 = no epilogue, 2 = default-policy stores instead of nt,
@@ -97,7 +105,7 @@ __device__ __forceinline__ void mfma_f(f32x16 &acc, const WFrags<KG, FB> &w, con
 // SL (round 5): output columns >= p.silu_from_col (a multiple of 64 FB, so a wave is all-or-nothing) leave as silu(.) — in_proj writing the
 // PRE-ACTIVATED gate half for the scan (ZIGMA_SCAN_Z_PREACTIVATED).  The 20 instructions per write chunk (4 values: -log2e *, v_exp, 1 +,
 // v_rcp, * x) are spread over the MFMA gaps 1 .. 3 of the chunk's k-group, the LDS write moves from gap 1 to gap 3.
-template <int KG, int FB, int PROBE, bool SL = false>
+template <int KG, int FB, int PROBE, bool SL = false, typename T = BF16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void linear_ws_kernel(const zigma_linear_params_t p, const int panels, const int ranges, const int tiles_per_xcd) {
     constexpr int NS = KG / 8;                           // slices per tile
@@ -204,7 +212,7 @@ void linear_ws_kernel(const zigma_linear_params_t p, const int panels, const int
     };
     auto wr_chunk_wr = [&](const int c, const float (&d)[4], const unsigned sw) {
         const int tb = (c >> 2) / FB, fb = (c >> 2) % FB, q4 = c & 3;
-        const u32x2 pk = {pack_bf2(d[0], d[1]), pack_bf2(d[2], d[3])};
+        const u32x2 pk = {pack2_pk<T>(d[0], d[1]), pack2_pk<T>(d[2], d[3])};
         const unsigned addr = sw + (static_cast<unsigned>((fb * 4 + q4) << 4) ^ sw_w);
         if (tb == 0) lds_wr8<0>(addr, pk); else lds_wr8<32 * RB>(addr, pk);
     };
@@ -276,7 +284,7 @@ void linear_ws_kernel(const zigma_linear_params_t p, const int panels, const int
 #pragma unroll
                 for (int mi = 0; mi < NB; ++mi) {
                     const int tb = mi / FB, fb = mi % FB;
-                    mfma_f<KG, FB>(acc[PAR][mi], w, FB * qg + fb, first, bf[q & 1][tb]);
+                    mfma_f<KG, FB, T>(acc[PAR][mi], w, FB * qg + fb, first, bf[q & 1][tb]);
                     if (mi == 0) {                       // ---- gap 0
                         if (PROBE != 4) frag_reads();
                         if (rd_prev) {
@@ -383,19 +391,21 @@ int launch_linear_ws(const zigma_linear_params_t &p, hipStream_t stream) {
     const int probe = (p.flags >> 16) & 7;
     const dim3 grid(256), block(256);
     const bool sl = p.silu_from_col < p.n;
-#define ZIGMA_LWS(KG_, FB_, P_) do { if (sl) hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, true>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); \
-                                     else hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, false>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); } while (0)
+#define ZIGMA_LWS(KG_, FB_, P_) do { if (sl) hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, true, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); \
+                                     else hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); } while (0)
 #ifdef ZIGMA_LINEAR4W_PROBES
 #define ZIGMA_LWS_K(KG_, FB_) { if (probe == 1) ZIGMA_LWS(KG_, FB_, 1); else if (probe == 2) ZIGMA_LWS(KG_, FB_, 2); else if (probe == 3) ZIGMA_LWS(KG_, FB_, 3); else if (probe == 4) ZIGMA_LWS(KG_, FB_, 4); else ZIGMA_LWS(KG_, FB_, 0); }
 #else
 #define ZIGMA_LWS_K(KG_, FB_) { if (probe) return ZIGMA_ERR_UNSUPPORTED; ZIGMA_LWS(KG_, FB_, 0); }
 #endif
-    if (p.k == 640) ZIGMA_LWS_K(40, 2) else if (p.k == 512) ZIGMA_LWS_K(32, 2)
-    else {      // one 32-feature block per wave (128-feature panels): k = 1280 / 1536
-        if (probe || sl) return ZIGMA_ERR_UNSUPPORTED;
-        if (p.k == 1280) hipLaunchKernelGGL((lws::linear_ws_kernel<80, 1, 0, false>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
-        else hipLaunchKernelGGL((lws::linear_ws_kernel<96, 1, 0, false>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
-    }
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, {
+        if (p.k == 640) ZIGMA_LWS_K(40, 2) else if (p.k == 512) ZIGMA_LWS_K(32, 2)
+        else {      // one 32-feature block per wave (128-feature panels): k = 1280 / 1536
+            if (probe || sl) return ZIGMA_ERR_UNSUPPORTED;
+            if (p.k == 1280) hipLaunchKernelGGL((lws::linear_ws_kernel<80, 1, 0, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
+            else hipLaunchKernelGGL((lws::linear_ws_kernel<96, 1, 0, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
+        }
+    })
 #undef ZIGMA_LWS_K
 #undef ZIGMA_LWS
     set_last_kernel(sl ? "linear_ws_silu" : pw == 128 ? "linear_ws_128" : "linear_ws");

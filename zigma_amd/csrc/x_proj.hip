@@ -8,7 +8,7 @@
 //   (shared by the 8 waves); every wave streams ITS 32 token rows of u straight from HBM as MFMA A fragments
 //   (v_mfma_f32_32x32x16_bf16: lane -> token row, 8 consecutive channels; 4 k-steps deep in flight) and keeps the
 //   32 x 96 accumulator in registers; output rows leave as bf16.
-// bf16 only; n <= 96; k % 256 == 0; rows 16-byte aligned.
+// bf16 or fp16 (template parameter T: the MFMA and the output rounding); n <= 96; k % 256 == 0; rows 16-byte aligned.
 #include "zigma_common.h"
 
 namespace zigma {
@@ -19,6 +19,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kXpWaves = 8, kXpTok = 32, kXpChunk = 256, kXpRows = 96, kXpDepth = 4;
 constexpr int kXpPitch = kXpChunk * 2 + 16;          // bytes per staged weight row (16 B skew)
 
+template <typename T>
 __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj_params_t p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_w[kXpRows * kXpPitch];   // 50.7 KB
     const int tid = threadIdx.x, lane = tid & 63;
@@ -53,12 +54,12 @@ __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj
 #pragma unroll
         for (int ks = 0; ks < kXpChunk / 16; ++ks) {
             const int s = c0 / 16 + ks;
-            const bf16x8 a = __builtin_bit_cast(bf16x8, aq[ks % kXpDepth]);
+            const frag8_t<T> a = __builtin_bit_cast(frag8_t<T>, aq[ks % kXpDepth]);
             if (s + kXpDepth < n_steps) aq[ks % kXpDepth] = *reinterpret_cast<const uint4 *>(xrow + (s + kXpDepth) * 16);
 #pragma unroll
             for (int nb = 0; nb < 3; ++nb) {
-                const bf16x8 b = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_w + (nb * 32 + j) * kXpPitch + ks * 32 + kh * 16));
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[nb], 0, 0, 0);
+                const frag8_t<T> b = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(s_w + (nb * 32 + j) * kXpPitch + ks * 32 + kh * 16));
+                acc[nb] = mfma_32x32x16<T>(a, b, acc[nb]);
             }
         }
     }
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            if (n < p.n && m < p.m) ow[m * p.out_row_stride + n] = from_float<BF16>(acc[nb][r]);
+            if (n < p.n && m < p.m) ow[m * p.out_row_stride + n] = from_float<T>(acc[nb][r]);
         }
     }
 }
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj
 // the eight partial 32 x 96 tiles are added through LDS in wave order (a fixed summation order: results do not depend on timing).
 constexpr int kXsWaves = 8, kXsMaxSteps = 12;
 
+template <typename T>
 __global__ __launch_bounds__(64 * kXsWaves) void x_proj_splitk_kernel(const zigma_xproj_params_t p) {
     __shared__ __attribute__((aligned(16))) float s_part[kXsWaves][3][16][64];     // 96 KB: [wave][feature block][accumulator register][lane]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -119,10 +121,10 @@ __global__ __launch_bounds__(64 * kXsWaves) void x_proj_splitk_kernel(const zigm
                 for (int nb = 0; nb < 3; ++nb)
                     bq[(s + 1) & 1][nb] = live[nb] ? *reinterpret_cast<const uint4 *>(wrow[nb] + (s + 1) * 16) : make_uint4(0, 0, 0, 0);
             }
-            const bf16x8 a = __builtin_bit_cast(bf16x8, aq[s]);
+            const frag8_t<T> a = __builtin_bit_cast(frag8_t<T>, aq[s]);
 #pragma unroll
             for (int nb = 0; nb < 3; ++nb)
-                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, bq[s & 1][nb]), acc[nb], 0, 0, 0);
+                acc[nb] = mfma_32x32x16<T>(a, __builtin_bit_cast(frag8_t<T>, bq[s & 1][nb]), acc[nb]);
         }
     }
 #pragma unroll
@@ -139,7 +141,7 @@ __global__ __launch_bounds__(64 * kXsWaves) void x_proj_splitk_kernel(const zigm
         for (int w = 0; w < kXsWaves; ++w) v += s_part[w][nb][r][l];
         const int n = nb * 32 + (l & 31);
         const int64_t m = m0 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
-        if (n < p.n && m < p.m) ow[m * p.out_row_stride + n] = from_float<BF16>(v);
+        if (n < p.n && m < p.m) ow[m * p.out_row_stride + n] = from_float<T>(v);
     }
 }
 
@@ -155,21 +157,21 @@ extern "C" int zigma_x_proj_fwd(const zigma_xproj_params_t *pp, void *stream_) {
     if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
     if (p.m == 0) return ZIGMA_OK;
     if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
+    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
     if (p.n > kXpRows || p.k % kXpChunk != 0 || p.k / 16 < kXpDepth) return ZIGMA_ERR_SHAPE;
     if (p.x_row_stride % 8 != 0 || p.w_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.x) % 16 != 0 ||
         reinterpret_cast<uintptr_t>(p.w) % 16 != 0)
         return ZIGMA_ERR_STRIDE;
     // few tokens: K split over the waves of 32-token workgroups (the streaming form would leave most CUs idle)
     if (p.m < 16384 && p.k % (16 * kXsWaves) == 0 && p.k / (16 * kXsWaves) <= kXsMaxSteps) {
-        hipLaunchKernelGGL(x_proj_splitk_kernel, dim3(static_cast<unsigned>((p.m + kXpTok - 1) / kXpTok)), dim3(64 * kXsWaves), 0,
-                           static_cast<hipStream_t>(stream_), p);
+        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_splitk_kernel<T>, dim3(static_cast<unsigned>((p.m + kXpTok - 1) / kXpTok)), dim3(64 * kXsWaves), 0,
+                                                          static_cast<hipStream_t>(stream_), p))
         set_last_kernel("x_proj_splitk");
         return check_launch();
     }
     const int64_t tok_per_wg = kXpTok * kXpWaves;
-    hipLaunchKernelGGL(x_proj_kernel, dim3(static_cast<unsigned>((p.m + tok_per_wg - 1) / tok_per_wg)), dim3(64 * kXpWaves), 0,
-                       static_cast<hipStream_t>(stream_), p);
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_kernel<T>, dim3(static_cast<unsigned>((p.m + tok_per_wg - 1) / tok_per_wg)), dim3(64 * kXpWaves), 0,
+                                                      static_cast<hipStream_t>(stream_), p))
     set_last_kernel("x_proj_mfma");
     return check_launch();
 }

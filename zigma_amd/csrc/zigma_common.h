@@ -54,6 +54,55 @@ template <typename T> __device__ __forceinline__ void st(void *base, int64_t idx
     reinterpret_cast<typename T::raw *>(base)[idx] = from_float<T>(v);
 }
 
+// ---- 16-bit pairs and MFMA fragments by I/O type (the matrix-core kernels serve BF16 and F16) -------
+// Two 16-bit values travel in one dword.  bf16 widens by bit ops, f16 by the hardware converter (v_cvt_f32_f16 and its
+// WORD_1 form); both narrow with round-to-nearest-even, so every kernel family rounds at the same points to the same bits.
+template <typename T> __device__ __forceinline__ float lo16(uint32_t v);
+template <typename T> __device__ __forceinline__ float hi16(uint32_t v);
+template <> __device__ __forceinline__ float lo16<BF16>(uint32_t v) { return __uint_as_float(v << 16); }
+template <> __device__ __forceinline__ float hi16<BF16>(uint32_t v) { return __uint_as_float(v & 0xffff0000u); }
+template <> __device__ __forceinline__ float lo16<F16>(uint32_t v) { return to_float<F16>(static_cast<uint16_t>(v & 0xffffu)); }
+template <> __device__ __forceinline__ float hi16<F16>(uint32_t v) { return to_float<F16>(static_cast<uint16_t>(v >> 16)); }
+
+template <typename T> __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+    return static_cast<uint32_t>(from_float<T>(lo)) | (static_cast<uint32_t>(from_float<T>(hi)) << 16);
+}
+// the same as one packed conversion (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32)
+template <typename T> __device__ __forceinline__ uint32_t pack2_pk(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pack2_pk<BF16>(float lo, float hi) {
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v2f{lo, hi}, bf16x2_t));
+}
+template <> __device__ __forceinline__ uint32_t pack2_pk<F16>(float lo, float hi) {
+    typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v2f{lo, hi}, f16x2_t));
+}
+
+typedef __bf16 mfma_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 mfma_f16x8 __attribute__((ext_vector_type(8)));
+typedef float mfma_f32x16 __attribute__((ext_vector_type(16)));
+typedef float mfma_f32x4 __attribute__((ext_vector_type(4)));
+template <typename T> struct Frag8;
+template <> struct Frag8<BF16> { typedef mfma_bf16x8 type; };
+template <> struct Frag8<F16> { typedef mfma_f16x8 type; };
+template <typename T> using frag8_t = typename Frag8<T>::type;      // 8 elements of a row: one 16-byte MFMA operand
+
+// v_mfma_f32_32x32x16_{bf16,f16} / v_mfma_f32_16x16x32_{bf16,f16}: same rate, same operand and accumulator lane maps
+template <typename T> __device__ __forceinline__ mfma_f32x16 mfma_32x32x16(frag8_t<T> a, frag8_t<T> b, mfma_f32x16 c);
+template <> __device__ __forceinline__ mfma_f32x16 mfma_32x32x16<BF16>(mfma_bf16x8 a, mfma_bf16x8 b, mfma_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+template <> __device__ __forceinline__ mfma_f32x16 mfma_32x32x16<F16>(mfma_f16x8 a, mfma_f16x8 b, mfma_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+template <typename T> __device__ __forceinline__ mfma_f32x4 mfma_16x16x32(frag8_t<T> a, frag8_t<T> b, mfma_f32x4 c);
+template <> __device__ __forceinline__ mfma_f32x4 mfma_16x16x32<BF16>(mfma_bf16x8 a, mfma_bf16x8 b, mfma_f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+template <> __device__ __forceinline__ mfma_f32x4 mfma_16x16x32<F16>(mfma_f16x8 a, mfma_f16x8 b, mfma_f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
 // ---- math (reference numerics: selective_scan_fwd_kernel.cuh:153-156,216,293) ------------------
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
@@ -99,6 +148,14 @@ void set_last_kernel(const char *name);
 #define ZIGMA_DISPATCH_DTYPE(DT, T, ...)                                   \
     switch (DT) {                                                          \
         case ZIGMA_F32: { using T = ::zigma::F32; __VA_ARGS__; break; }    \
+        case ZIGMA_F16: { using T = ::zigma::F16; __VA_ARGS__; break; }    \
+        case ZIGMA_BF16: { using T = ::zigma::BF16; __VA_ARGS__; break; }  \
+        default: return ZIGMA_ERR_DTYPE;                                   \
+    }
+
+// the matrix-core kernels: the two 16-bit types only
+#define ZIGMA_DISPATCH_16BIT(DT, T, ...)                                   \
+    switch (DT) {                                                          \
         case ZIGMA_F16: { using T = ::zigma::F16; __VA_ARGS__; break; }    \
         case ZIGMA_BF16: { using T = ::zigma::BF16; __VA_ARGS__; break; }  \
         default: return ZIGMA_ERR_DTYPE;                                   \

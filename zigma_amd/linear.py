@@ -8,17 +8,20 @@ from . import _lib
 from . import routing
 
 
+MFMA_DTYPES = (torch.bfloat16, torch.float16)      # the I/O types of the matrix-core kernels; all operands of a call share one
+
+
 def linear_eligible(x, weight, bias=None):
-    """LIMITS of zigma_linear_fwd's tiled kernels on these tensors (no policy — which projection runs where is zigma_amd/routing.py): bf16 on the
-    device, k % 64 == 0, n % 128 == 0, tokens % 8 == 0, aligned contiguous rows, no autograd"""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16):
+    """LIMITS of zigma_linear_fwd's tiled kernels on these tensors (no policy — which projection runs where is zigma_amd/routing.py): bf16 or fp16
+    (x, weight and bias in ONE of them) on the device, k % 64 == 0, n % 128 == 0, tokens % 8 == 0, aligned contiguous rows, no autograd"""
+    if not (x.is_cuda and x.dtype in MFMA_DTYPES and weight.dtype == x.dtype):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         return False
     n, k = weight.shape
     if k % 64 or n % 128 or x.shape[-1] != k or x.stride(-1) != 1 or weight.stride(1) != 1:
         return False
-    if bias is not None and (bias.dtype != torch.bfloat16 or bias.stride(0) != 1 or n > 4096 or bias.data_ptr() % 4):
+    if bias is not None and (bias.dtype != x.dtype or bias.stride(0) != 1 or n > 4096 or bias.data_ptr() % 4):
         return False                                     # (the kernel stages the bias vector in 8 KB of LDS)
     m = x.numel() // k
     if m % 8 or m == 0:
@@ -66,7 +69,7 @@ _TENSOR_LIMITS["ws128"] = _TENSOR_LIMITS["ws"]
 
 def linear(x, weight, bias=None, silu_from_col=None, out=None, _probe_flags=0, residual=None, gate=None, weight_stationary=False, few_tokens=False):
     """out = x @ weight.T (+ bias); output columns >= silu_from_col (a multiple of 32) leave as silu(.).
-    residual (same shape as the result) + gate (batch, n): out = residual + gate[b] * bf16(x @ weight.T + bias) in the kernel's
+    residual (same shape as the result) + gate (batch, n): out = residual + gate[b] * r16(x @ weight.T + bias) (r16: rounded to the I/O type) in the kernel's
     epilogue (the gated branch add of the reference's Block, model_zigma.py:447-449); x must then be (batch, rows, k) with
     rows % 256 == 0.  weight_stationary: the csrc/linear_ws.hip kernel (linear_ws_eligible shapes only; fails otherwise); few_tokens: the
     csrc/linear_sm.hip kernel (linear_sm_eligible shapes only)."""
@@ -98,9 +101,9 @@ def residual_rows_ok(residual):
 
 
 def gated_residual_eligible(x, residual, gate):
-    """limits of the gated-residual epilogue: (B, rows % 256 == 0, k) input, bf16 residual rows 16-byte aligned in one pitch,
-    gate rows 16-byte aligned"""
-    return (x.dim() == 3 and x.shape[1] % 256 == 0 and residual.dtype == x.dtype and gate.dtype == x.dtype and residual_rows_ok(residual)
+    """limits of the gated-residual epilogue: (B, rows % 256 == 0, k) bf16 or fp16 input, residual rows of the same dtype 16-byte aligned in
+    one pitch, gate rows of the same dtype 16-byte aligned"""
+    return (x.dtype in MFMA_DTYPES and x.dim() == 3 and x.shape[1] % 256 == 0 and residual.dtype == x.dtype and gate.dtype == x.dtype and residual_rows_ok(residual)
             and residual.stride(-1) == 1 and residual.stride(1) % 8 == 0 and residual.data_ptr() % 16 == 0
             and gate.dim() == 2 and gate.stride(1) == 1 and gate.stride(0) % 8 == 0 and gate.data_ptr() % 16 == 0
             and 256 * residual.stride(1) * 2 < 2 ** 31)
@@ -109,11 +112,11 @@ def gated_residual_eligible(x, residual, gate):
 def plan(role, x, weight, bias=None, residual=None, gate=None):
     """The ONE decision which kernel serves a projection (routing.ROLES) on these tensors: the first route of the table (routing.candidates) whose
     kernel's shape and tensor limits the call meets; a route the tensors refuse is logged in routing.REFUSED and the walk goes on.  Calls no own kernel
-    can take (fp32 / fp16 models, CPU tensors, autograd) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
+    can take (fp32 models, mixed dtypes, CPU tensors, autograd) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
     epilogue (the route fuses, residual / gate are given and meet the epilogue's limits, no autograd)."""
     n, k = weight.shape
     if not linear_eligible(x, weight, bias):
-        return routing.Route("library", False, "not-bf16-inference")
+        return routing.Route("library", False, "not-16bit-inference")
     tokens = x.numel() // k
     for r in routing.candidates(role, tokens, n, k):
         if _TENSOR_LIMITS[r.kernel](x, bias):

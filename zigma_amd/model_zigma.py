@@ -29,7 +29,7 @@ import torch.nn.functional as F
 import torch.utils.checkpoint
 from torch import Tensor
 
-from .attention import attention_math, cross_attn, cross_attn_eligible, cross_attn_train
+from .attention import attention_math, cross_attn, cross_attn_bwd_eligible, cross_attn_eligible, cross_attn_train
 from . import embed as _embed
 from .layernorm import RMSNorm, block_norm, glue_bwd_eligible, layer_norm_fn, rms_norm_fn, scale_reduce_bwd
 from .linear import plan, project, run
@@ -140,13 +140,14 @@ class CrossAttention(nn.Module):
         H = self.heads
         k, v = kv[:2] if kv is not None else (self.to_k(text), self.to_v(text))
         q = project("to_q", x, self.to_q.weight, self.to_q.bias)
-        if cross_attn_eligible(q, k, v, H):
+        needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
+        if cross_attn_eligible(q, k, v, H) and (not needs_grad or cross_attn_bwd_eligible(q, k, v, H)):
             # HIP kernel: attention core in one pass (K/V of the head in LDS); under autograd its differentiable form (backward =
             # library GEMMs + ATen elementwise ops).  No fused SDPA anywhere: on ROCm that is an AOT-Triton kernel.
-            if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+            if needs_grad:
                 return self._proj_out(cross_attn_train(q, k, v, H, self.scale), residual, gate)
             return self._proj_out(cross_attn(q, k, v, H, self.scale), residual, gate)
-        # operands the kernel does not take (fp32 / fp16 models, CPU tensors, long contexts): the same math in torch ops
+        # operands the kernels do not take (fp32 models, fp16 under autograd — the backward kernel is bf16-only —, CPU tensors, long contexts): the same math in torch ops
         return self._proj_out(attention_math(q, k.reshape(Bsz, k.shape[1], -1), v.reshape(Bsz, v.shape[1], -1), H, self.scale), residual, gate)
 
 

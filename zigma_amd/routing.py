@@ -147,7 +147,7 @@ def _disabled():
 
 
 def candidates(role, tokens, n, k):
-    """the routes the table offers a bf16 inference call of `role` with `tokens` rows, n output and k input features, best first; the last is the library"""
+    """the routes the table offers a bf16 / fp16 inference call of `role` with `tokens` rows, n output and k input features, best first; the last is the library"""
     if role not in ROLES:
         raise ValueError(f"routing: unknown role {role!r}")
     if POLICY == "off":

@@ -206,11 +206,11 @@ def scan_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
 
 
 def x_proj_eligible(u, weight):
-    """limits of zigma_x_proj_fwd: bf16, n <= 96, k % 256 == 0, 16-byte aligned contiguous rows.  From 16 384 tokens on a workgroup streams
+    """limits of zigma_x_proj_fwd: bf16 or fp16 (u and weight alike), n <= 96, k % 256 == 0, 16-byte aligned contiguous rows.  From 16 384 tokens on a workgroup streams
     256 token rows over the whole K; below, K is split over the waves of 32-token workgroups (x_proj_splitk_kernel, round 5: the streaming
     form was 32 workgroups and 31 us at 8192 tokens against 21 for the library), which needs k <= 1536."""
     tokens = u.numel() // u.shape[-1]
-    return (u.is_cuda and u.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and u.is_contiguous()
+    return (u.is_cuda and u.dtype in (torch.bfloat16, torch.float16) and weight.dtype == u.dtype and u.is_contiguous()
             and (tokens >= 16384 or (tokens >= 256 and weight.shape[1] <= 1536))
             and weight.shape[0] <= 96 and weight.shape[1] % 256 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
             and u.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
@@ -232,14 +232,14 @@ def x_proj(u, weight):
 
 
 def conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_weight, perm, reset_period=0):
-    """limits of zigma_conv_x_proj_fwd: bf16, width-4 taps as contiguous (d_inner, 4), a bias, seqlen % 32 == 0,
+    """limits of zigma_conv_x_proj_fwd: bf16 or fp16 (all four operands alike), width-4 taps as contiguous (d_inner, 4), a bias, seqlen % 32 == 0,
     batch * seqlen % 256 == 0 and >= 16384 positions (a workgroup walks 256 positions over the whole d_inner: fewer than ~64
     workgroups leave the chip idle), d_inner % 64 == 0, n <= 96, 16-byte aligned rows, one sequence per batch row."""
     if conv_b is None or reset_period or not x_half.is_cuda:
         return False
     Bsz, L, Di = x_half.shape
-    return (x_half.dtype == torch.bfloat16 and conv_w.dtype == torch.bfloat16 and conv_b.dtype == torch.bfloat16
-            and x_proj_weight.dtype == torch.bfloat16 and conv_w.shape == (Di, 4) and conv_w.is_contiguous() and conv_b.is_contiguous()
+    return (x_half.dtype in (torch.bfloat16, torch.float16) and conv_w.dtype == x_half.dtype and conv_b.dtype == x_half.dtype
+            and x_proj_weight.dtype == x_half.dtype and conv_w.shape == (Di, 4) and conv_w.is_contiguous() and conv_b.is_contiguous()
             and L % 32 == 0 and (Bsz * L) % 256 == 0 and Bsz * L >= CONV_X_PROJ_MIN_POSITIONS and Di % 64 == 0
             and x_proj_weight.shape[0] <= 96 and x_proj_weight.shape[0] % 8 == 0
             and x_half.stride(2) == 1 and x_half.stride(1) % 8 == 0 and x_half.stride(0) % 8 == 0
@@ -250,7 +250,7 @@ def conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_weight, perm, reset_peri
 
 def conv_x_proj(x_half, conv_w, conv_b, x_proj_weight, perm=None, _flags=0):
     """u = silu(causal_conv1d(x_half[:, perm])) and x_dbl = u @ x_proj_weight.T in one pass over x (zigma_conv_x_proj_fwd).
-    x_half: (B, L, d_inner) bf16 view with contiguous channels (the first half of the in_proj output, as is); conv_w: (d_inner, 4);
+    x_half: (B, L, d_inner) bf16 / fp16 view with contiguous channels (the first half of the in_proj output, as is); conv_w: (d_inner, 4);
     returns u (B, L, d_inner) in SCAN order and x_dbl (B, L, n).  Replaces causal_conv1d_fn + F.linear of reference
     selective_scan_interface.py:307-322."""
     dev = _lib.require_device(x_half, conv_w, conv_b, x_proj_weight, perm)
@@ -291,8 +291,8 @@ def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z
 
 
 def dt_proj_eligible(x_dbl, dt_rank, weight):
-    """bf16 token-major x_dbl rows / weight rows on 16-byte boundaries, d_inner a multiple of 64, dt_rank <= 48, % 8 == 0."""
-    return (x_dbl.is_cuda and x_dbl.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and dt_rank <= 48
+    """bf16 or fp16 (x_dbl and weight alike) token-major x_dbl rows / weight rows on 16-byte boundaries, d_inner a multiple of 64, dt_rank <= 48, % 8 == 0."""
+    return (x_dbl.is_cuda and x_dbl.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x_dbl.dtype and dt_rank <= 48
             and dt_rank % 8 == 0
             and weight.shape[0] % 64 == 0 and x_dbl.stride(-1) == 1 and weight.stride(1) == 1
             and x_dbl.stride(-2) % 8 == 0 and weight.stride(0) % 8 == 0
@@ -301,8 +301,8 @@ def dt_proj_eligible(x_dbl, dt_rank, weight):
 
 def dt_proj_softplus(x_dbl, dt_rank, weight, bias=None, softplus=True):
     """delta' = softplus(x_dbl[..., :dt_rank] @ weight.T + bias) on the matrix cores (zigma_dt_proj_softplus_fwd).
-    x_dbl: (..., >= dt_rank) bf16 rows; weight: (d_inner, dt_rank) bf16; bias: float32 (d_inner) or None.
-    Returns (..., d_inner) bf16.  Fuses reference selective_scan_interface.py:323 with the softplus(delta + bias)
+    x_dbl: (..., >= dt_rank) bf16 / fp16 rows; weight: (d_inner, dt_rank) in the same dtype; bias: float32 (d_inner) or None.
+    Returns (..., d_inner) in that dtype.  Fuses reference selective_scan_interface.py:323 with the softplus(delta + bias)
     at the top of its scan kernel; the scan is then called with delta_softplus=False, delta_bias=None."""
     dev = _lib.require_device(x_dbl, weight, bias)
     lead = x_dbl.shape[:-1]
