@@ -661,6 +661,43 @@ def test_linear_train_fn_fp16(M, K, N_, monkeypatch):
     assert torch.equal(got[2], w.grad)
 
 
+def test_model_gradients_fp16_close_to_fp32_reference():
+    """The fp16 twin of tests/test_gpu_backward.py::test_model_gradients_bf16_close_to_fp32_reference (same fixture, same limits: fp16 carries
+    three more mantissa bits than bf16): fp16 parameters / activations under autograd reach the three backward kernels in their F16 instantiations
+    — asserted from the call trace — and the gradients stay within the bf16 limits of the reference's fp32 autograd gradients."""
+    from zigma_amd import _lib
+    from zigma_amd.model_zigma import ZigMa
+    name = "zigma_uncond_zigzag8"
+    g, gg = load_golden(name + ".npz"), load_golden("bwd_model_" + name + ".npz")
+    cfg = ast.literal_eval(str(g["cfg"]))
+    m = ZigMa(device=DEV, dtype=H, **cfg).eval()
+    m.load_state_dict({k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd.")}, strict=True)
+    x = T(g["x"]).requires_grad_(True)
+    _lib.TRACE = []
+    try:
+        out = m(x, T(g["t"]), None)
+        (out * T(gg["wgt"])).sum().backward()
+    finally:
+        trace, _lib.TRACE = _lib.TRACE, None
+    for fn, field in (("zigma_selective_scan_bwd", "io_dtype"), ("zigma_causal_conv1d_bwd", "io_dtype"), ("zigma_add_norm_bwd", "x_dtype")):
+        seen = [getattr(P, field) for f, _, P in trace if f == fn]
+        assert seen and all(d == _lib.F16 for d in seen), (fn, seen)
+    assert torch.isfinite(out).all() and torch.isfinite(x.grad).all()
+    e = rel_err(N(x.grad), gg["gx"])
+    worst = 1.0
+    for k, p in m.named_parameters():
+        if "g." + k not in gg or p.grad is None:
+            continue
+        assert torch.isfinite(p.grad).all(), k
+        a, b = N(p.grad).ravel().astype(np.float64), gg["g." + k].ravel().astype(np.float64)
+        if np.linalg.norm(b) < 1e-6:
+            continue
+        worst = min(worst, float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-30)))
+    print(f"fp16 model gradients vs fp32 reference: input gradient {e:.3e}, worst cosine {worst:.4f}")
+    assert e < 8e-2, e
+    assert worst > 0.95, worst
+
+
 # ---------------------------------------------------------------------------------------------------
 # 7. refusals stay refusals
 # ---------------------------------------------------------------------------------------------------
