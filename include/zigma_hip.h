@@ -36,7 +36,8 @@ extern "C" {
                                * 7: reset_period in the two backward blocks (zigma_scan_bwd_params_t reuses its padding, zigma_conv_bwd_params_t grew)
                                * 8: zigma_patch_embed_fwd, zigma_timestep_embed_fwd, zigma_final_layer_fwd, zigma_skinny_linear_fwd added
                                * 9: zigma_scan_params_t grew: dt_x / dt_w (dt_proj + softplus inside the scan kernel)
-                               * 10: zigma_calib_launch (bench.py's box calibration) added; new ZIGMA_LINEAR_* kernel selectors of round 6 */
+                               * 10: zigma_calib_launch (bench.py's box calibration) added; new ZIGMA_LINEAR_* kernel selectors of round 6
+                               * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -525,6 +526,34 @@ typedef struct zigma_linear_params {
 } zigma_linear_params_t;
 
 int zigma_linear_fwd(const zigma_linear_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Weight gradient of a dense projection:  out[n][k] = sum_m dy[m][n] * x[m][k]  (dW = dY^T X), bf16 or fp16 in / fp32 accumulate.
+ * Replaces the GEMM that autograd's linear backward runs for the weight of F.linear at the call sites of zigma_linear_fwd and at
+ * x_proj / dt_proj (reference selective_scan_interface.py:318-323).  dy: (m, n) rows of pitch dy_row_stride; x: (m, k) rows of pitch
+ * x_row_stride (column views of wider rows pass as they are); out: (n, k) rows of pitch out_row_stride, of the operand type or float32.
+ * The tokens are split into `slabs` slabs (0 = the library's choice from the shape); the fp32 slab partials go through the caller's
+ * `workspace` of zigma_linear_wgrad_workspace_bytes() bytes (0 when one slab serves; private layout) and are added in ascending slab order,
+ * rounded once: no atomics, the result is bit-reproducible.  Nothing outside out[:n, :k] is written.
+ * Limits: m >= 1; n, k multiples of 8 up to 8192; row strides multiples of 8 elements; dy, x, out, workspace 16-byte aligned, out rows a
+ * multiple of 16 bytes apart.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_linear_wgrad_params {
+    int64_t m;               /* tokens: the contraction length */
+    int32_t n, k;            /* columns of dy, columns of x */
+    int32_t dtype;           /* zigma_dtype_t of dy and x: ZIGMA_BF16 or ZIGMA_F16 */
+    int32_t out_dtype;       /* `dtype` or ZIGMA_F32 */
+    int32_t slabs;           /* 0: chosen by the library; > 0: forced (tests, probes) */
+    int32_t flags;           /* reserved, must be 0 */
+    int64_t dy_row_stride, x_row_stride, out_row_stride;
+    const void *dy, *x;
+    void *out;
+    void *workspace;
+    int64_t workspace_bytes;
+} zigma_linear_wgrad_params_t;
+
+int64_t zigma_linear_wgrad_workspace_bytes(const zigma_linear_wgrad_params_t *p);
+int zigma_linear_wgrad(const zigma_linear_wgrad_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The small per-forward operators around the blocks (bf16 models; each replaces a chain of library GEMM + ATen elementwise launches):

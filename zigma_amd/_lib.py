@@ -167,7 +167,13 @@ class LinearParams(C.Structure):
                 + [("residual", vp), ("gate", vp), ("res_row_stride", i64), ("gate_batch_stride", i64), ("rows_per_batch", i32), ("pad2_", i32)])
 
 
-EXPORTS = ("zigma_linear_fwd", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
+class LinearWgradParams(C.Structure):
+    _fields_ = ([("m", i64), ("n", i32), ("k", i32), ("dtype", i32), ("out_dtype", i32), ("slabs", i32), ("flags", i32)]
+                + [(n, i64) for n in ("dy_row_stride", "x_row_stride", "out_row_stride")] + [(n, vp) for n in ("dy", "x", "out", "workspace")]
+                + [("workspace_bytes", i64)])
+
+
+EXPORTS = ("zigma_linear_fwd", "zigma_linear_wgrad", "zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
            "zigma_selective_scan_bwd_workspace_bytes", "zigma_causal_conv1d_bwd",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
@@ -191,13 +197,15 @@ def lib():
                          ("zigma_selective_scan_bwd", ScanBwdParams), ("zigma_causal_conv1d_bwd", ConvBwdParams),
                          ("zigma_add_norm_bwd", NormBwdParams), ("zigma_cross_attn_fwd", XAttnParams), ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_patch_embed_fwd", PatchEmbedParams),
                          ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_skinny_linear_fwd", SkinnyParams), ("zigma_x_proj_fwd", XProjParams),
-                         ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams)):
+                         ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
+                         ("zigma_linear_wgrad", LinearWgradParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st), vp]
             fn.restype = C.c_int
         for name, st in (("zigma_selective_scan_bwd_workspace_bytes", ScanBwdParams),
                          ("zigma_causal_conv1d_bwd_workspace_bytes", ConvBwdParams),
-                         ("zigma_add_norm_bwd_workspace_bytes", NormBwdParams)):
+                         ("zigma_add_norm_bwd_workspace_bytes", NormBwdParams),
+                         ("zigma_linear_wgrad_workspace_bytes", LinearWgradParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st)]
             fn.restype = C.c_int64

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libzigma_hip.so")
 SOURCES = ["api.hip", "selective_scan.hip", "scan_tok_bf16.hip", "scan_tok_f16.hip", "scan_tok_f32.hip",
-           "causal_conv1d.hip", "add_norm.hip", "dt_proj.hip", "scan_bwd.hip", "conv_bwd.hip", "norm_bwd.hip", "cross_attn.hip", "cross_attn_bwd.hip", "x_proj.hip", "linear.hip", "linear4w.hip", "linear_ws.hip", "linear_sm.hip", "conv_x_proj.hip", "glue_bwd.hip", "embed.hip", "skinny_linear.hip", "calib.hip"]
+           "causal_conv1d.hip", "add_norm.hip", "dt_proj.hip", "scan_bwd.hip", "conv_bwd.hip", "norm_bwd.hip", "cross_attn.hip", "cross_attn_bwd.hip", "x_proj.hip", "linear.hip", "linear4w.hip", "linear_ws.hip", "linear_sm.hip", "conv_x_proj.hip", "glue_bwd.hip", "embed.hip", "skinny_linear.hip", "calib.hip", "wgrad.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-fno-slp-vectorize",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
@@ -26,8 +26,10 @@ _VGPR_MFMA = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 # a live-range split of the destination registers between the load and the tile's fence would silently lose a row.  The two TUs that instantiate
 # the kernel are compiled with the resource-usage remarks on, and the build FAILS if any instantiation uses scratch memory or spills a register.
 _RES = ["-Rpass-analysis=kernel-resource-usage"]
-SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES}
-NO_SCRATCH_KERNELS = ("scan_tok2_kernel",)
+# wgrad_kernel (csrc/wgrad.hip) holds its accumulators and one prefetched step in registers at 3 - 4 workgroups per CU: scratch would cost it the stream rate, so
+# the same check guards its instantiations.
+SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES}
+NO_SCRATCH_KERNELS = ("scan_tok2_kernel", "wgrad_kernel", "wgrad_reduce_kernel")
 
 
 def check_no_scratch(remarks, src):
@@ -44,7 +46,7 @@ def check_no_scratch(remarks, src):
         if m and name and int(m.group(2)) != 0:
             bad.append((name, m.group(1), int(m.group(2))))
     if bad or not seen:
-        raise RuntimeError(f"{src}: scan_tok2_kernel must not spill (inline-asm d16_hi row loads are invisible to the register allocator): "
+        raise RuntimeError(f"{src}: {' / '.join(NO_SCRATCH_KERNELS)} must not spill or use scratch (scan_tok2_kernel: inline-asm d16_hi row loads are invisible to the register allocator): "
                            f"{bad if bad else 'no instantiation found in the remarks'}")
     return seen
 
@@ -124,7 +126,7 @@ def build(force=False, verbose=True, sources=None, lib=None, extra_flags=()):
             r = subprocess.run(cmd, check=True, capture_output=True, text=True)
             n = check_no_scratch(r.stderr, cmd[-3])
             if verbose:
-                print(f"  {os.path.basename(cmd[-3])}: {n} scan_tok2_kernel instantiations, no scratch, no spills", flush=True)
+                print(f"  {os.path.basename(cmd[-3])}: {n} checked kernel instantiations, no scratch, no spills", flush=True)
         else:
             run(cmd)
         open(o_stamp, "w").write(o_want)

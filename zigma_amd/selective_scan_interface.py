@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 from . import _knobs, _lib
 from .causal_conv1d_interface import causal_conv1d_raw, conv_bwd_tok
-from .wgrad import wgrad
+from .wgrad import plan_wgrad, wgrad
 
 
 SPLIT_SMALL_BATCH = True             # tools/latency_probe.py flips this to measure the effect of the small-batch sequence split
@@ -531,7 +531,10 @@ class MambaInnerTokFn(torch.autograd.Function):
         ctx.ck = None
         dd2 = ddelta.reshape(-1, Di)
         dx_dbl[:, :, :R] = (dd2 @ dt_proj_w).reshape(Bsz, L, R)                  # d(x_dbl[:, :R]) = ddelta @ W_dt
-        d_dt_w = wgrad(dd2, x_dbl.reshape(-1, R + 2 * N)[:, :R].contiguous())       # (Di, R)  token-slab GEMMs (zigma_amd/wgrad.py)
+        x_dt = x_dbl.reshape(-1, R + 2 * N)[:, :R]
+        if plan_wgrad(dd2, x_dt) != "own":                                          # (the own kernel takes the 72-pitch column view as it is)
+            x_dt = x_dt.contiguous()
+        d_dt_w = wgrad(dd2, x_dt)                                                   # (Di, R)  zigma_linear_wgrad or token-slab GEMMs (zigma_amd/wgrad.py)
         dxd = dx_dbl.to(xz.dtype).reshape(-1, R + 2 * N)
         du = torch.addmm(du.reshape(-1, Di), dxd, x_proj_w).reshape(Bsz, L, Di)    # x_dbl = u @ W_x^T
         d_x_w = wgrad(dxd, u.reshape(-1, Di))                                      # (R + 2N, Di)

@@ -6,13 +6,22 @@ CUs and run at 0.03 ... 0.5 PFLOP/s (tools/wgrad_split_probe.py: in_proj 450 us,
 into S slabs as a BATCHED GEMM (the slab index is the library's batch dimension) the same products fill the chip; the S partial
 results (bf16, like a GEMM output) are added in fp32: in_proj 332 us, out_proj 303 -> 149, to_q 259 -> 76, to_out 271 -> 66,
 x_proj 227 -> 72, dt_proj 205 -> 64 us — 17 ms of a 122 ms training step.  `LinearTrainFn` is F.linear with that backward; since round 4 its forward product and dX run on the hand-written projection kernels
-(zigma_linear_fwd) where one serves the shape — the "train" rows of zigma_amd/routing.py (routing.POLICY="off": the library for both)."""
+(zigma_linear_fwd) where one serves the shape — the "train" rows of zigma_amd/routing.py (routing.POLICY="off": the library for both).
+
+The same products have an own entry point, zigma_linear_wgrad (csrc/wgrad.hip: split-K over token slabs, MFMA operands by transposed LDS reads, fp32 partials
+added in slab order, row-strided operands): wgrad_own() launches it, plan_wgrad() decides per product between it and the slab bmm (PLAN_TABLE; knob OWN_WGRAD)."""
+import ctypes
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
+from . import _knobs, _lib
 from .linear import plan, run
 
 SPLIT_WGRAD = True        # False: one GEMM (A/B in tools/train_probe.py)
+OWN_WGRAD = True          # True: PLAN_TABLE decides between zigma_linear_wgrad and the slab bmm;  False: never the own kernel (the A/B partner);
+#                           "all": the own kernel wherever its tensor-level limits hold (tools/wgrad_split_probe.py measures the table's rows with it)
 
 
 _BMM_OUT_DTYPE = {}      # (device type, index, dtype) -> bool
@@ -73,8 +82,104 @@ def _slabs(m, n, k):
     return s
 
 
+# ---- the own split-K kernel (csrc/wgrad.hip, zigma_linear_wgrad) ------------------------------------------------------------------------------
+INF = 1 << 40
+WgradRow = namedtuple("WgradRow", "id n k tokens path why")
+# n / k / tokens: (lo, hi) inclusive; the first matching row wins.  n = columns of dY = rows of dW, k = columns of X.
+# `why` carries the measurement that decided the row (tools/wgrad_split_probe.py --own-ab, profiles/wgrad_own_vs_bmm.jsonl).
+PLAN_TABLE = (
+    WgradRow("few_tokens", (8, 8192), (8, 8192), (1, 255), "bmm",
+             "not measured: below 256 tokens one GEMM of the library is a single small launch and the kernel has at most four 64-token steps per workgroup to hide its prologue under"),
+    WgradRow("skinny_n", (8, 128), (8, 8192), (256, INF), "bmm",
+             "x_proj (72 x 1280): one 128-row tile covers n, X streams exactly once (168 MB at 65 536 tokens; the slab bmm: 72 us, round 4).  own vs bmm NOT MEASURED on the MI355X yet "
+             "(tools/wgrad_split_probe.py --own-ab): the row stays on the measured path until it is"),
+    WgradRow("skinny_k", (136, 8192), (8, 64), (256, INF), "bmm",
+             "dt_proj (1280 x 40): one 64-column tile covers k, dY streams exactly once and the 72-pitch view of x_dbl needs no copy (the slab bmm: 64 us + the copy, round 4).  own vs bmm "
+             "NOT MEASURED on the MI355X yet: the row stays on the measured path until it is"),
+    WgradRow("dense", (136, 8192), (72, 8192), (256, INF), "bmm",
+             "in_proj / out_proj / to_q / to_out (slab bmm: 332 / 149 / 76 / 66 us at 65 536 tokens, round 4): compute-bound; the kernel stages one 64-token step through registers behind two "
+             "barriers, the form that measured 4 x behind the library in round 3 (tools/experiments/wgrad_tr_r03.hip: in_proj 1260 vs 332 us).  own vs bmm of THIS kernel NOT MEASURED yet"),
+)
+
+
+def own_serves(dy2, x2):
+    """the tensor-level limits of zigma_linear_wgrad (include/zigma_hip.h), read from device, dtype, shape, strides and data_ptr only"""
+    if not (dy2.is_cuda and x2.is_cuda) or dy2.dtype not in (torch.bfloat16, torch.float16) or x2.dtype != dy2.dtype:
+        return False
+    if len(dy2.shape) != 2 or len(x2.shape) != 2 or dy2.shape[0] != x2.shape[0] or dy2.shape[0] < 1:
+        return False
+    for t in (dy2, x2):
+        w = t.shape[1]
+        if w < 8 or w % 8 or w > 8192 or t.stride(1) != 1 or t.stride(0) < w or t.stride(0) % 8 or t.data_ptr() % 16:
+            return False
+    return True
+
+
+def plan_row(dy2, x2):
+    """the PLAN_TABLE row a product falls on (None: the tensors are outside the kernel's limits, or the knob is off)"""
+    if OWN_WGRAD is False or torch.is_autocast_enabled() or not own_serves(dy2, x2):
+        return None
+    m, n, k = dy2.shape[0], dy2.shape[1], x2.shape[1]
+    for row in PLAN_TABLE:
+        if row.n[0] <= n <= row.n[1] and row.k[0] <= k <= row.k[1] and row.tokens[0] <= m <= row.tokens[1]:
+            return row
+    return None
+
+
+def plan_wgrad(dy2, x2):
+    """"own" (zigma_linear_wgrad) or "bmm" (the slab-wise library product below) for dW = dy2^T x2 — the ONE place that decides.  Two layers: the
+    tensor-level limits of the entry point, then PLAN_TABLE.  Independent of routing.POLICY (the own-vs-library tests of the forward kernels
+    compare w.grad bit for bit across its settings)."""
+    row = plan_row(dy2, x2)
+    if row is None:
+        return "bmm"
+    return "own" if OWN_WGRAD == "all" else row.path
+
+
+def wgrad_own(dy2, x2, out_dtype=None, slabs=0, out=None, workspace=None):
+    """dy2 (m, n), x2 (m, k) -> dy2^T x2 (n, k) by zigma_linear_wgrad: fp32 slab partials in a workspace, added in slab order, one rounding to
+    `out_dtype` (the operand dtype, or torch.float32).  Row-strided operands (column views) pass as they are.  slabs = 0: the library's choice.
+    out / workspace: caller-provided buffers (tests); the limits are the C side's — a refusal raises RuntimeError with its status."""
+    dev = _lib.require_device(dy2, x2, out, workspace)
+    if dy2.dim() != 2 or x2.dim() != 2 or dy2.shape[0] != x2.shape[0]:
+        raise RuntimeError("wgrad_own: dy2 (m, n) and x2 (m, k) with the same m")
+    if dy2.stride(1) != 1 or x2.stride(1) != 1:
+        raise RuntimeError("wgrad_own: the channel stride of both operands must be 1")
+    m, n = dy2.shape
+    k = x2.shape[1]
+    out_dtype = out_dtype or (out.dtype if out is not None else dy2.dtype)
+    P = _lib.LinearWgradParams()
+    P.m, P.n, P.k, P.slabs, P.flags = m, n, k, int(slabs), 0
+    # (a mixed pair has no representation in the block: it goes in as an unknown operand type and comes back as ZIGMA_ERR_DTYPE)
+    P.dtype = _lib.dtype_id(dy2) if x2.dtype == dy2.dtype else -1
+    P.out_dtype = _lib._DT.get(out_dtype, -1)
+    if out is None:
+        out = torch.empty(n, k, device=dev, dtype=out_dtype)
+    elif out.shape != (n, k) or out.stride(1) != 1 or out.dtype != out_dtype:
+        raise RuntimeError("wgrad_own: out must be (n, k) rows of out_dtype with channel stride 1")
+    P.dy_row_stride, P.x_row_stride, P.out_row_stride = dy2.stride(0), x2.stride(0), out.stride(0)
+    P.dy, P.x, P.out = _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(out)
+    if workspace is None:
+        ws = _lib.workspace("zigma_linear_wgrad", P, dev)
+    else:
+        ws = workspace
+        P.workspace, P.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    _lib.call("zigma_linear_wgrad", P, dev)
+    return out
+
+
+def wgrad_workspace_bytes(m, n, k, dtype=torch.bfloat16, slabs=0):
+    """bytes of workspace zigma_linear_wgrad asks for at this shape (0: one slab, the kernel writes the result itself)"""
+    P = _lib.LinearWgradParams()
+    P.m, P.n, P.k, P.slabs, P.dtype, P.out_dtype = m, n, k, int(slabs), _lib._DT[dtype], _lib._DT[dtype]
+    return int(_lib.lib().zigma_linear_wgrad_workspace_bytes(ctypes.byref(P)))
+
+
 def wgrad(dy2, x2):
-    """dy2 (m, n), x2 (m, k), same 16-bit dtype -> dy2^T x2 (n, k) in that dtype (fp32 sum of the slab products)"""
+    """dy2 (m, n), x2 (m, k), same 16-bit dtype -> dy2^T x2 (n, k) in that dtype: the own split-K kernel where plan_wgrad says so, else the fp32
+    sum of the library's slab products"""
+    if plan_wgrad(dy2, x2) == "own":
+        return wgrad_own(dy2, x2)
     m, n = dy2.shape
     k = x2.shape[1]
     s = _slabs(m, n, k) if (SPLIT_WGRAD and dy2.is_cuda and dy2.dtype in (torch.bfloat16, torch.float16)) else 1
@@ -122,3 +227,6 @@ def linear_train(x, weight, bias=None):
             and x.numel() // x.shape[-1] >= 4096 and torch.is_grad_enabled() and not torch.is_autocast_enabled()):
         return LinearTrainFn.apply(x, weight, bias)
     return F.linear(x, weight, bias)
+
+
+_knobs.apply(globals(), "wgrad")
