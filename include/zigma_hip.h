@@ -424,7 +424,7 @@ typedef struct zigma_xattn_bwd_params {
     int32_t batch, seqlen, n_ctx, heads, head_dim;
     int32_t dtype;
     int32_t flags;   /* reserved, must be 0 */
-    float scale;
+    float scale;     /* the forward's; must be finite and > 0 (else ZIGMA_ERR_UNSUPPORTED) */
     int32_t chunks;  /* zigma_cross_attn_bwd_chunks(seqlen) */
     int32_t pad_;
     int64_t q_batch_stride, q_row_stride;

@@ -291,6 +291,8 @@ extern "C" int zigma_cross_attn_bwd(const zigma_xattn_bwd_params_t *pp, void *st
     const zigma_xattn_bwd_params_t &p = *pp;
     if (p.batch < 0 || p.seqlen < 0 || p.heads < 1 || p.n_ctx < 1) return ZIGMA_ERR_SHAPE;
     if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
+    // the forward's domain (zigma_cross_attn_fwd takes a positive finite scale only): an inf or nan scale would come back as NaN gradients
+    if (!(p.scale > 0.f) || !(p.scale < 3.0e38f)) return ZIGMA_ERR_UNSUPPORTED;
     if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
     if (!p.q || !p.k || !p.v || !p.dout || !p.dq || !p.dk_part || !p.dv_part) return ZIGMA_ERR_NULL;
     if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
