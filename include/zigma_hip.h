@@ -37,7 +37,8 @@ extern "C" {
                                * 8: zigma_patch_embed_fwd, zigma_timestep_embed_fwd, zigma_final_layer_fwd, zigma_skinny_linear_fwd added
                                * 9: zigma_scan_params_t grew: dt_x / dt_w (dt_proj + softplus inside the scan kernel)
                                * 10: zigma_calib_launch (bench.py's box calibration) added; new ZIGMA_LINEAR_* kernel selectors of round 6
-                               * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added */
+                               * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added
+                               * (10, no block changed): zigma_linear_f32_split added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -554,6 +555,34 @@ typedef struct zigma_linear_wgrad_params {
 
 int64_t zigma_linear_wgrad_workspace_bytes(const zigma_linear_wgrad_params_t *p);
 int zigma_linear_wgrad(const zigma_linear_wgrad_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * fp32 projection on the bf16 matrix cores by splitting:  out = x @ W^T (+ bias), x / bias / out float32, W as two bf16 planes.
+ * split(a) of a finite fp32 a: hi = bf16_rne(a) (clamped to the largest finite bf16, never infinite), lo = bf16_rne(a - float(hi)); a
+ * non-finite a: hi = bf16(a), lo = 0.  The caller splits the (static) weight once into w_hi / w_lo; x is split inside the kernel on its way
+ * from global memory to LDS.
+ *   passes == 3 ("high", bf16 x 3):  out = sum_k (x_hi w_hi + x_lo w_hi + x_hi w_lo) + bias   (lo x lo is omitted)
+ *   passes == 1 ("medium"):          out = sum_k x_hi w_hi + bias                             (w_lo is not read, may be NULL)
+ * All products are v_mfma_f32_32x32x16_bf16 with fp32 accumulators: one for hi x hi, a second one for the two cross terms, added at the end.
+ * x: (m, k) rows of pitch x_row_stride; w_hi / w_lo: (n, k) rows of pitch w_*_row_stride; out: (m, n) rows of pitch out_row_stride (views of
+ * wider rows pass as they are); bias (n) or NULL.  Nothing outside out[:m, :n] is written; a partly filled last token tile is predicated.
+ * Errors, decided before anything touches the device: NULL block / x / w_hi / out (w_lo with passes == 3) -> ZIGMA_ERR_NULL; flags != 0 or
+ * passes not 1 or 3 -> ZIGMA_ERR_UNSUPPORTED; m < 0, m % 8, n % 128, k % 64, n or k < 1 or > 65536, a row stride below the width ->
+ * ZIGMA_ERR_SHAPE; pointers or rows not 16-byte aligned -> ZIGMA_ERR_STRIDE; m == 0 -> ZIGMA_OK without a launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_linear_split_params {
+    int64_t m;               /* tokens */
+    int32_t n, k;            /* output features (rows of W), input features */
+    int32_t passes;          /* 3: bf16 x 3 ("high");  1: hi x hi only ("medium") */
+    int32_t flags;           /* reserved, must be 0 */
+    int64_t x_row_stride, w_hi_row_stride, w_lo_row_stride, out_row_stride;   /* in elements */
+    const void *x;           /* float32 */
+    const void *w_hi, *w_lo; /* bf16 */
+    const void *bias;        /* float32 or NULL */
+    void *out;               /* float32 */
+} zigma_linear_split_params_t;
+
+int zigma_linear_f32_split(const zigma_linear_split_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The small per-forward operators around the blocks (bf16 models; each replaces a chain of library GEMM + ATen elementwise launches):

@@ -33,6 +33,9 @@ def main():
     ap.add_argument("--prediction", default="velocity")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--fp32-matmul", default="highest", choices=["highest", "high", "medium"],
+                    help="--dtype fp32 only: the block projections as three (high) or one (medium) bf16 matrix-core products instead of the "
+                         "library's fp32 GEMM (zigma_amd.set_float32_matmul_precision); a bf16 model does not read it")
     ap.add_argument("--class-label", type=int, default=None, help="class-conditional models: the label to sample")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--decode", default="none", choices=["none", "standin"],
@@ -41,6 +44,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
+    import zigma_amd
     from zigma_amd import sharded_sampling as ss
     from zigma_amd.graphs import GraphedForward
     from zigma_amd.model_zigma import ZigMa
@@ -53,6 +57,7 @@ def main():
     rank, world, _ = ss.init_from_env(backend="nccl", device=device)
     cfg = json.loads(args.config)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    zigma_amd.set_float32_matmul_precision(args.fp32_matmul)
     model = ZigMa(device=device, dtype=dtype, **cfg).eval()
     if args.ckpt:
         sd = torch.load(args.ckpt, map_location="cpu")

@@ -11,5 +11,8 @@ Layout (mirrors the reference's module names so call sites read the same):
     scan_paths                       zigzag_path, hilbert_path, reverse_permut_np (utils/utils_zigzag.py)
     transport                        create_transport, Sampler                   (transport/)
     extension_shims                  `selective_scan_cuda` / `causal_conv1d_cuda` module stand-ins
+    fp32_matmul                      set_float32_matmul_precision: fp32 projections as split bf16 products on the matrix cores (opt-in)
 """
 __version__ = "0.1.0"
+
+from .fp32_matmul import get_float32_matmul_precision, set_float32_matmul_precision  # noqa: E402,F401

@@ -5,6 +5,7 @@ runs with autograd off); linear_eligible itself refuses tensors that require gra
 import torch
 
 from . import _lib
+from . import fp32_matmul
 from . import routing
 
 
@@ -112,10 +113,15 @@ def gated_residual_eligible(x, residual, gate):
 def plan(role, x, weight, bias=None, residual=None, gate=None):
     """The ONE decision which kernel serves a projection (routing.ROLES) on these tensors: the first route of the table (routing.candidates) whose
     kernel's shape and tensor limits the call meets; a route the tensors refuse is logged in routing.REFUSED and the walk goes on.  Calls no own kernel
-    can take (fp32 models, mixed dtypes, CPU tensors, autograd) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
+    can take (mixed dtypes, CPU tensors, autograd, fp32 models unless fp32_matmul.PRECISION opts them into the bf16-split kernel) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
     epilogue (the route fuses, residual / gate are given and meet the epilogue's limits, no autograd)."""
     n, k = weight.shape
     if not linear_eligible(x, weight, bias):
+        # fp32 tensors of an inference call, opted in by fp32_matmul.PRECISION: the bf16-split kernel, for every role; its gated add stays where the
+        # library route leaves it (project's addcmul, or the next norm kernel)
+        mode = fp32_matmul.PRECISION
+        if mode != "highest" and x.dtype == torch.float32 and routing.POLICY != "off" and fp32_matmul.split_eligible(x, weight, bias):
+            return routing.Route(fp32_matmul.ROUTE_KERNEL[mode], False, "fp32." + mode)
         return routing.Route("library", False, "not-16bit-inference")
     tokens = x.numel() // k
     for r in routing.candidates(role, tokens, n, k):
@@ -132,6 +138,8 @@ def run(r, x, weight, bias=None, residual=None, gate=None, silu_from_col=None):
     if r.kernel == "library":
         from .wgrad import linear_train
         return linear_train(x, weight, bias)
+    if r.kernel in ("split3", "split1"):
+        return fp32_matmul.linear_split(x, weight, bias, mode="high" if r.kernel == "split3" else "medium")
     if r.kernel == "tiled_halves":
         n = weight.shape[0]
         y = torch.empty(*x.shape[:-1], n, device=x.device, dtype=x.dtype)

@@ -32,12 +32,15 @@ from . import _knobs
 Route = namedtuple("Route", "kernel fuse_add row")
 Row = namedtuple("Row", "id role k n tokens kernel fuse_add why")
 
-KERNELS = ("ws", "ws128", "sm", "tiled", "tiled_halves", "library")
+KERNELS = ("ws", "ws128", "sm", "tiled", "tiled_halves", "split3", "split1", "library")
 #   ws           csrc/linear_ws.hip, 256-feature weight panels resident in registers (k = 512 / 640)
 #   ws128        the same kernel's 128-feature-panel form (k = 1280 / 1536)
 #   sm           csrc/linear_sm.hip, one 128-token x n/4-feature tile per workgroup (few tokens)
 #   tiled        zigma_linear_fwd's default: the generated 4-wave kernel (csrc/linear4w.hip) from 256 tiles on, the 8-wave kernel (csrc/linear.hip) below
 #   tiled_halves two launches of `tiled`, one per half of the output columns
+#   split3       csrc/linear_split.hip, fp32 operands as three bf16 products (fp32_matmul.PRECISION = "high"); never a row of the table: linear.plan
+#                hands fp32 inference calls to it before the table is asked
+#   split1       the same kernel with one pass ("medium")
 #   library      F.linear
 
 POLICY = "auto"
@@ -185,4 +188,4 @@ def kernel_name(route_or_kernel, tokens=None, n=None, k=None):
             return "linear"
         nn = n // 2 if kern == "tiled_halves" else n
         return ("linear4w_256x256+128" if nn % 256 else "linear4w_256x256") if serves_4w(tokens, nn, k) else "linear_tn_"
-    return {"ws": "linear_ws", "ws128": "linear_ws_128", "sm": "linear_sm_", "library": "library"}[kern]
+    return {"ws": "linear_ws", "ws128": "linear_ws_128", "sm": "linear_sm_", "split3": "linear_split3_", "split1": "linear_split1_", "library": "library"}[kern]
