@@ -113,3 +113,182 @@ def install(monkeypatch):
     monkeypatch.setattr(ssi, "causal_conv1d_raw", conv_raw)
     monkeypatch.setattr(ssi, "scan_raw", scan_raw)
     monkeypatch.setattr(ln, "_norm_call", norm_call)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Stand-ins AT THE C ABI for the forward Mamba-inner entry points: _lib.call(name, parameter block, device) served on CPU tensors by float64
+# torch restatements that read and write through the block's pointers and strides, so that tests/test_gpu_fwd_fuzz.py (views, row tables,
+# NaN surroundings, staged checks) can be exercised without a GPU.  torch_scan_fwd is also the independent restatement the CPU test holds
+# the numpy reference of tests/fwd_fuzz_cases.py against.
+# ---------------------------------------------------------------------------------------------------
+import ctypes
+
+LAST_KERNEL = [""]
+
+
+def torch_scan_fwd(u, step, A, Bm, Cm, D, gate, zi, oi, *, reset=0, chunk=0, out_z0=None, kernel_decay=False):
+    """The token-major selective scan as an explicit float64 loop over (sequence, chunk, step) with restarts.  u, step (B, L, dim): scan order,
+    step = the step sizes the recurrence runs on; Bm, Cm (B, L, N); gate (B, L, dim) multiplier in TOKEN rows (read at row zi[k]) or None;
+    results are written at row oi[k].  kernel_decay: the decay taken the kernels' way, exp2(step * fl32(A * log2 e)) — the same number to 1e-7,
+    and exactly 0.5 for the known-answer cases' A.  Returns y (ungated, placed), y_gated (placed, + out_z0), ckpt (B, tile, dim, N): the state before every
+    16-step tile, x_prod / x_state (B, chunk, dim, N): running decay product and state at every chunk end."""
+    f64 = torch.float64
+    decay = (lambda d: torch.exp2(d * (A.float() * 1.4426950408889634).to(f64))) if kernel_decay else (lambda d: torch.exp(d * A.to(f64)))
+    u, step, A, Bm, Cm = (t.to(f64) for t in (u, step, A, Bm, Cm))
+    Bsz, L, dim = u.shape
+    N = A.shape[1]
+    y = torch.empty(Bsz, L, dim, dtype=f64)
+    ckpt = torch.zeros(Bsz, -(-L // 16), dim, N, dtype=f64)
+    n_chunks = -(-L // chunk) if chunk else 0
+    x_prod, x_state = torch.zeros(Bsz, n_chunks, dim, N, dtype=f64), torch.zeros(Bsz, n_chunks, dim, N, dtype=f64)
+    period = reset or L
+    for a in range(0, L, period):                                  # independent sequences
+        end = min(a + period, L)
+        h, cum = torch.zeros(Bsz, dim, N, dtype=f64), torch.zeros(Bsz, dim, dtype=f64)
+        for c0 in range(a, end, chunk or period):                  # chunks of one sequence: the state carries over
+            c1 = min(c0 + (chunk or period), end)
+            for l in range(c0, c1):
+                if l % 16 == 0:
+                    ckpt[:, l // 16] = h
+                d = step[:, l]
+                h = decay(d[..., None]) * h + (d * u[:, l])[..., None] * Bm[:, l, None, :]
+                cum = cum + d
+                y[:, l] = (h * Cm[:, l, None, :]).sum(-1)
+            if chunk:
+                x_prod[:, (c1 - 1) // chunk], x_state[:, (c1 - 1) // chunk] = decay(cum[..., None]), h
+    if D is not None:
+        y = y + u * D.to(f64)
+    place = lambda t: t if oi is None else torch.empty_like(t).index_copy_(1, oi.long(), t)
+    y_gated = None
+    if gate is not None:
+        g = gate.to(f64)
+        y_gated = place(y * (g if zi is None else g.index_select(1, zi.long())))
+        if out_z0 is not None:
+            y_gated = out_z0.to(f64) + y_gated
+    return dict(y=place(y), y_gated=y_gated, ckpt=ckpt, x_prod=x_prod, x_state=x_state)
+
+
+def _view(ptr, shape, strides, dtype):
+    """the tensor a parameter block describes: base pointer, shape and strides in elements"""
+    if not ptr:
+        return None
+    n = 1 + sum((s - 1) * st for s, st in zip(shape, strides))
+    es = torch.empty((), dtype=dtype).element_size()
+    buf = (ctypes.c_char * (n * es)).from_address(ptr)
+    return torch.frombuffer(buf, dtype=dtype, count=n).as_strided(tuple(shape), tuple(strides))
+
+
+def _io_dtype(i):
+    from zigma_amd import _lib
+    return {v: k for k, v in _lib._DT.items()}[i]
+
+
+def _scan_fwd(P, plan):
+    from zigma_amd import _lib
+    f32, dt = torch.float32, _io_dtype(P.io_dtype)
+    got = plan(P)
+    if got["status"] != 0:
+        raise RuntimeError(f"zigma_selective_scan_fwd: refused (status {got['status']})")
+    Bsz, dim, L, N = P.batch, P.dim, P.seqlen, P.dstate
+    act = lambda name: _view(getattr(P, name), (Bsz, L, dim), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "l", "d")], dt)
+    bc = lambda name: _view(getattr(P, name), (Bsz, L, N), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "l", "dstate")], dt)
+    A = _view(P.A, (dim, N), (P.A_d_stride, P.A_dstate_stride), f32)
+    D, bias = _view(P.D, (dim,), (1,), f32), _view(P.delta_bias, (dim,), (1,), f32)
+    u, z, delta = act("u"), act("z"), act("delta")
+    if P.dt_x:
+        R = P.dt_rank
+        x = _view(P.dt_x, (Bsz, L, R), (P.dt_x_batch_stride, P.dt_x_l_stride, 1), dt)
+        w = _view(P.dt_w, (dim, R), (P.dt_w_row_stride, 1), dt)
+        pre = x.double() @ w.double().T
+    else:
+        pre = delta.double()
+    if bias is not None:
+        pre = pre + bias.double()
+    step = _softplus(pre) if P.delta_softplus else pre
+    if P.dt_x and P.x:                      # the split's first pass writes the rounded step sizes; both passes run on them
+        delta.copy_(step.to(dt))
+        step = delta.double()
+    gate = None
+    if z is not None:
+        gate = z.double() if P.flags & _lib.SCAN_Z_PREACTIVATED else z.double() * torch.sigmoid(z.double())
+    zi, oi = _view(P.z_row_index, (L,), (1,), torch.int32), _view(P.out_row_index, (L,), (1,), torch.int32)
+    out, out_z = act("out"), act("out_z")
+    chunk = (P.chunk_len if P.chunk_len > 0 else 2048) if P.x else 0
+    r = torch_scan_fwd(u, step, A, bc("B"), bc("C"), D, gate, zi, oi, reset=P.reset_period, chunk=chunk,
+                       out_z0=out_z if P.flags & _lib.SCAN_ACCUMULATE else None, kernel_decay=True)
+    if out_z is not None:
+        out_z.copy_(r["y_gated"].to(dt))
+    if out is not None:
+        out.copy_(r["y"].to(dt))
+    if P.x:
+        xv = _view(P.x, (Bsz, dim, r["x_prod"].shape[1], 2 * N), _contig((Bsz, dim, r["x_prod"].shape[1], 2 * N)), f32)
+        xv[..., 0::2], xv[..., 1::2] = r["x_prod"].transpose(1, 2).float(), r["x_state"].transpose(1, 2).float()
+    if P.checkpoints and got["info1"]:
+        nt = -(-L // 16)
+        ck = _view(_addr(P.checkpoints), (Bsz, dim // 64, nt, N, 64), _contig((Bsz, dim // 64, nt, N, 64)), f32)
+        ck.copy_(r["ckpt"].reshape(Bsz, nt, dim // 64, 64, N).permute(0, 2, 1, 4, 3).float())
+    if P.info:
+        P.info[0], P.info[1] = got["family"], got["info1"]
+    return got["kernel"]
+
+
+def _addr(p):
+    return p if isinstance(p, int) else ctypes.cast(p, ctypes.c_void_p).value
+
+
+def _contig(shape):
+    return [int(np.prod(shape[i + 1:])) for i in range(len(shape))]
+
+
+def _softplus(x):
+    return torch.nn.functional.softplus(x)          # beta 1, threshold 20: the reference's
+
+
+def _conv_xproj_fwd(P):
+    dt = _io_dtype(P.dtype)
+    Bsz, L, dim, n = P.batch, P.seqlen, P.dim, P.n
+    x = _view(P.x, (Bsz, L, dim), (P.x_batch_stride, P.x_l_stride, 1), dt).double()
+    cw, cb = _view(P.conv_weight, (dim, 4), (4, 1), dt).double(), _view(P.conv_bias, (dim,), (1,), dt).double()
+    w = _view(P.w, (n, dim), (P.w_row_stride, 1), dt).double()
+    idx = _view(_addr(P.x_row_index), (L,), (1,), torch.int32)
+    if idx is not None:
+        x = x.index_select(1, idx.long())
+    xp = torch.nn.functional.pad(x, (0, 0, 3, 0))
+    pre = cb + sum(cw[:, t] * xp[:, t:t + L] for t in range(4))
+    u = _view(P.u, (Bsz, L, dim), (P.u_batch_stride, P.u_l_stride, 1), dt)
+    u.copy_((pre * torch.sigmoid(pre)).to(dt))
+    _view(P.out, (Bsz * L, n), (P.out_row_stride, 1), dt).copy_((u.double().reshape(Bsz * L, dim) @ w.T).to(dt))
+    return "conv_x_proj_mfma"
+
+
+def _x_proj_fwd(P):
+    dt = _io_dtype(P.dtype)
+    x, w = _view(P.x, (P.m, P.k), (P.x_row_stride, 1), dt), _view(P.w, (P.n, P.k), (P.w_row_stride, 1), dt)
+    _view(P.out, (P.m, P.n), (P.out_row_stride, 1), dt).copy_((x.double() @ w.double().T).to(dt))
+    return "x_proj_splitk" if P.m < 16384 and P.k % 128 == 0 and P.k // 128 <= 12 else "x_proj_mfma"
+
+
+def _dt_proj_fwd(P):
+    dt = _io_dtype(P.dtype)
+    x, w = _view(P.x, (P.m, P.k), (P.x_row_stride, 1), dt), _view(P.w, (P.n, P.k), (P.w_row_stride, 1), dt)
+    pre = x.double() @ w.double().T
+    if P.bias:
+        pre = pre + _view(P.bias, (P.n,), (1,), torch.float32).double()
+    _view(P.out, (P.m, P.n), (P.out_row_stride, 1), dt).copy_((_softplus(pre) if P.softplus else pre).to(dt))
+    return "dt_proj_softplus_mfma"
+
+
+def install_lib_call(monkeypatch, plan):
+    """route _lib.call to the stand-ins above.  plan: plan_scan() compiled with g++ (the scan_plan fixture of tests/test_host_cpu.py): names
+    the kernel, fills `info` and refuses what the library refuses"""
+    from zigma_amd import _lib
+    serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": _conv_xproj_fwd, "zigma_x_proj_fwd": _x_proj_fwd,
+             "zigma_dt_proj_softplus_fwd": _dt_proj_fwd}
+
+    def call(fn_name, params, device):
+        LAST_KERNEL[0] = serve[fn_name](params)
+        if _lib.TRACE is not None:
+            _lib.TRACE.append((fn_name, LAST_KERNEL[0], params))
+    monkeypatch.setattr(_lib, "call", call)
+    monkeypatch.setattr(_lib, "require_device", lambda *t: torch.device("cpu"))
+    monkeypatch.setattr(_lib, "last_kernel", lambda: LAST_KERNEL[0])

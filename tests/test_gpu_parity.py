@@ -444,7 +444,7 @@ def test_dt_proj_softplus_mfma_vs_oracle(M, Di, R, S):
 def test_scan_tok2_dt_proj_in_kernel_vs_oracle(Bsz, L, Di, R, use_perm, io):
     """ABI 9: dt_proj + bias + softplus inside scan_tok2_kernel (zigma_scan_params_t.dt_x / dt_w) against the numpy oracle's scan on
     delta' = x_dbl[:, :, :R] @ W_dt^T (reference selective_scan_interface.py:323 + softplus(delta + bias) of its kernel) evaluated in
-    fp32 on the same bf16 operands, and against the two-kernel path (dt_proj_softplus_kernel + scan) whose delta is a bf16 tensor."""
+    fp32 on the same 16-bit operands, and against the two-kernel path (dt_proj_softplus_kernel + scan) whose delta is a 16-bit tensor."""
     from zigma_amd import _lib
     from zigma_amd.selective_scan_interface import dt_in_scan_eligible, dt_proj_softplus, scan_raw
     Nst = 16
@@ -488,15 +488,13 @@ def test_scan_tok2_dt_proj_in_kernel_vs_oracle(Bsz, L, Di, R, use_perm, io):
     e = rel_err(got, bf(ref))
     assert np.isfinite(got).all() and e < 1e-3, e
     assert np.allclose(got, ref, rtol=3e-2, atol=5e-2)           # the reference's bf16 bounds (test_selective_scan.py:47)
-    # the path it replaces
-    if io != "bf16":
-        return                                                   # (zigma_dt_proj_softplus_fwd is a bf16 kernel)
+    # the path it replaces (zigma_dt_proj_softplus_fwd dispatches both 16-bit types)
     dl = dt_proj_softplus(xt, R, wt, T(db), True)
     y2 = torch.empty_like(y)
     scan_raw(ut.transpose(1, 2), dl.transpose(1, 2), T(A), Bv, Cv, T(D), zt.transpose(1, 2), None, False, out_z=y2.transpose(1, 2),
              z_row_index=pt, out_row_index=pt, want_out=False)
     e2 = rel_err(N(y), N(y2))
-    print(f"in-kernel dt_proj B={Bsz} L={L} Di={Di} R={R}: vs oracle {e:.2e}; vs dt_proj kernel + scan (bf16 delta) {e2:.2e}")
+    print(f"in-kernel dt_proj B={Bsz} L={L} Di={Di} R={R}: vs oracle {e:.2e}; vs dt_proj kernel + scan ({io} delta) {e2:.2e}")
     assert e2 < 5e-3, e2
 
 

@@ -323,7 +323,11 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
                 const float xv = dacc[i];
                 const float tv = xv * kLog2e;
                 float dv = xv > 20.f ? tv : fast_log2(1.f + fast_exp2(tv));          // dt' = dt * log2(e)
-                if constexpr (!LOG2U) dv = to_float<IO>(from_float<IO>(dv * kLn2));        // split first pass: the ROUNDED delta the second pass will read
+                // split first pass: the ROUNDED delta the second pass will read.  It is the tensor dt_proj_softplus_kernel used to write, so it takes
+                // that kernel's softplus: the direct log2(1 + t) above loses t against 1 (0 below t = 2^-24, 2^-24 / t relative above it), which a
+                // WRITTEN 16-bit delta shows as elements off the correctly rounded value (tests/test_gpu_fwd_fuzz.py: 2.1 % in bf16 with 4 of 192
+                // channels below -17)
+                if constexpr (!LOG2U) dv = to_float<IO>(from_float<IO>(softplus20_r16(xv)));
                 *reinterpret_cast<v2f *>(&s_dtdu[4 * kq + i][wave * 16 + n16][0]) = v2f{dv, dv * f32of(up[i])};
 #ifdef ZIGMA_DTP_DEBUG
                 if (p.checkpoints) {      // debug: (dt, u') of every element, [batch][step][dim][2]
