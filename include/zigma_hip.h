@@ -501,16 +501,18 @@ int zigma_conv_x_proj_fwd(const zigma_conv_xproj_params_t *p, void *stream);
  * multiple of 128 elements apart, out rows 16-byte aligned.  silu_from_col < n (round 5, pw = 256 only): a multiple of 128 — whole
  * 128-column groups leave as silu(.) of the fp32 accumulator.
  * ZIGMA_LINEAR_SM (flags; round 5): the few-token tiled kernel (csrc/linear_sm.hip: tiles of 128 rows x n / 4 columns, one per workgroup —
- * 8192 rows x 640 columns are exactly 256 tiles).  Same result bit for bit.  Limits, else ZIGMA_ERR_UNSUPPORTED: no bias / activation /
- * residual, k % 64 == 0 and k >= 128, m % 128 == 0 (n % 128 == 0: tiles of 160, 192 or 128 columns), out rows 16-byte aligned.
+ * 8192 rows x 640 columns are exactly 256 tiles).  Same result bit for bit; takes the bias (on an 8-byte boundary) and the gated residual.
+ * Limits, else ZIGMA_ERR_UNSUPPORTED: no activation (silu_from_col == n), k % 64 == 0 and k >= 128, m % 128 == 0 (n % 128 == 0: tiles of 160,
+ * 192 or 128 columns), out rows 16-byte aligned.
+ * Without a selector the library chooses between the 4-wave and the 8-wave tiled kernel.  Every refusal and choice: plan_linear(), csrc/linear_plan.h.
  * ------------------------------------------------------------------------------------------ */
 #define ZIGMA_LINEAR_WS 0x4000
 #define ZIGMA_LINEAR_SM 0x8000
 typedef struct zigma_linear_params {
     int64_t m;
     int32_t n, k;
-    int32_t dtype;           /* ZIGMA_BF16 */
-    int32_t flags;           /* 0, or ZIGMA_LINEAR_WS (other bits: probes of tools/, refused by the shipped library) */
+    int32_t dtype;           /* ZIGMA_BF16 or ZIGMA_F16 */
+    int32_t flags;           /* 0, ZIGMA_LINEAR_WS or ZIGMA_LINEAR_SM (other bits: probes of tools/; the shipped library answers them with the 8-wave kernel or refuses them) */
     int32_t silu_from_col;
     int32_t pad_;
     int64_t x_row_stride, w_row_stride, out_row_stride;

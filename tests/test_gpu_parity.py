@@ -1492,3 +1492,39 @@ def test_scan_dispatch_case_table(name):
         assert info == (0, 0) and after == before          # nothing reported
     else:
         assert info == want.info and after == want.kernel
+
+
+@pytest.mark.parametrize("name", sorted(__import__("linear_plan_cases").CASES))
+def test_linear_dispatch_case_table(name):
+    """every case of the dispatch table (tests/linear_plan_cases.py) through zigma_linear_fwd: status and last kernel (unchanged when nothing is served);
+    for a served case 64 sampled rows — the first, the last, both sides of the first 256-row boundary — against float64 on the same bf16 operands with
+    bias / SiLU range / gated residual applied, relative norm below 4e-3 as in test_every_routing_cell_vs_float64 (bf16 rounding of the product and of
+    the sum): a plan field mapped to the wrong instantiation computes something else"""
+    import ctypes
+    import linear_plan_cases
+    from zigma_amd import _lib
+    case, want = linear_plan_cases.CASES[name]
+
+    def launch(P):
+        before = _lib.last_kernel()
+        rc = _lib.lib().zigma_linear_fwd(ctypes.byref(P), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        return rc, before, _lib.last_kernel()
+    (rc, before, after), o = linear_plan_cases.call(case, DEV, launch)
+    assert rc == want.status
+    if want.kernel is None:
+        assert after == before              # nothing reported
+        return
+    assert after == want.kernel
+    m, n, k = case["shape"]
+    rows = torch.randint(0, m, (64,), generator=torch.Generator().manual_seed(m + n))
+    rows[:4] = torch.tensor([0, m - 1, min(255, m - 1), min(256, m - 1)])
+    rows = rows.to(DEV)
+    ref = o["x"].reshape(m, k)[rows].double() @ o["w"].double().T + (o["bias"].double() if o["bias"] is not None else 0)
+    if o["silu"] is not None:
+        ref[:, o["silu"]:] = torch.nn.functional.silu(ref[:, o["silu"]:])
+    if o["res"] is not None:
+        ref = o["res"].reshape(m, n)[rows].double() + o["gate"].double()[rows // o["rpb"]] * ref
+    err = float((o["out"].reshape(m, n)[rows].double() - ref).norm() / ref.norm())
+    print(f"{name}: {after} rel err {err:.3e}")
+    assert err < 4e-3, (name, after, err)

@@ -610,25 +610,35 @@ extern "C" int split_ok(const zigma_scan_params_t *p) { return tok2_split_ok(*p)
 """
 
 
-@pytest.fixture(scope="module")
-def scan_plan():
-    """plan_scan() of zigma_amd/csrc/scan_plan.h compiled on its own with g++ (no HIP): plan(params) -> status, family, info1, kernel;
-    split_ok(params)"""
-    from zigma_amd import _lib
+def _compile_plan(driver):
+    """a driver around one of the HIP-free plan headers of zigma_amd/csrc, compiled on its own with g++ and loaded"""
     with tempfile.TemporaryDirectory() as d:
         src, so = os.path.join(d, "plan.cpp"), os.path.join(d, "libplan.so")
-        open(src, "w").write(_PLAN_DRIVER)
+        open(src, "w").write(driver)
         subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"),
                         "-I", os.path.join(ROOT, "zigma_amd", "csrc"), src, "-o", so], check=True)
-        L = ctypes.CDLL(so)
-    L.plan.argtypes = [ctypes.POINTER(_lib.ScanParams), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
-    L.split_ok.argtypes = [ctypes.POINTER(_lib.ScanParams)]
-    names = ("status", "family", "info1")
+        return ctypes.CDLL(so)
+
+
+def _plan_caller(L, params_type, names):
+    """plan(P) -> dict of the driver's integer fields and the kernel string"""
+    L.plan.argtypes = [ctypes.POINTER(params_type), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
 
     def plan(P):
         f, k = (ctypes.c_int * len(names))(), ctypes.c_char_p()
         L.plan(ctypes.byref(P), f, ctypes.byref(k))
         return dict(zip(names, f), kernel=k.value.decode() if k.value else None)
+    return plan
+
+
+@pytest.fixture(scope="module")
+def scan_plan():
+    """plan_scan() of zigma_amd/csrc/scan_plan.h compiled on its own with g++ (no HIP): plan(params) -> status, family, info1, kernel;
+    split_ok(params)"""
+    from zigma_amd import _lib
+    L = _compile_plan(_PLAN_DRIVER)
+    L.split_ok.argtypes = [ctypes.POINTER(_lib.ScanParams)]
+    plan = _plan_caller(L, _lib.ScanParams, ("status", "family", "info1"))
     plan.split_ok = lambda P: bool(L.split_ok(ctypes.byref(P)))
     return plan
 
@@ -684,6 +694,7 @@ class _Dev:
         self.is_cuda, self.dtype, self.shape, self._ptr = True, dtype, shape, ptr
         self._strides = tuple(math.prod(shape[i + 1:]) for i in range(len(shape)))
     stride, dim, data_ptr = (lambda self, i: self._strides[i]), (lambda self: len(self.shape)), (lambda self: self._ptr)
+    numel, requires_grad = (lambda self: math.prod(self.shape)), False
 
 
 def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
@@ -789,14 +800,90 @@ def test_linear_train_fn_matches_autograd_and_slab_rule():
         assert s >= 1 and (s & (s - 1)) == 0 and (s == 1 or (m % s == 0 and m // s >= 256 and (m // s) % 8 == 0)), (m, n, k, s)
 
 
+_LINEAR_PLAN_DRIVER = r"""
+#include "linear_plan.h"
+using namespace zigma;
+extern "C" int plan(const zigma_linear_params_t *p, int *fields, const char **kernel) {
+    const LinearPlan s = plan_linear(*p);
+    fields[0] = s.status; fields[1] = s.family; fields[2] = s.pw; fields[3] = s.panels; fields[4] = s.ranges; fields[5] = s.tiles_per_xcd;
+    *kernel = s.kernel;
+    return s.status;
+}
+"""
+LIN_TN, LIN_4W, LIN_WS, LIN_SM = 1, 2, 3, 4         # enum LinearFamily
+
+
+@pytest.fixture(scope="module")
+def linear_plan():
+    """plan_linear() of zigma_amd/csrc/linear_plan.h compiled on its own with g++ (no HIP): plan(params) -> status, family, the weight-stationary
+    kernel's pw / panels / ranges / tiles_per_xcd, kernel"""
+    from zigma_amd import _lib
+    return _plan_caller(_compile_plan(_LINEAR_PLAN_DRIVER), _lib.LinearParams, ("status", "family", "pw", "panels", "ranges", "tiles_per_xcd"))
+
+
+def _linear_params(tokens, n, k, flags=0, x_pitch=None, bias=0):
+    """the parameter block zigma_amd.linear.linear builds for a plain bf16 projection of aligned operands into a fresh output"""
+    from zigma_amd import _lib
+    P = _lib.LinearParams()
+    P.m, P.n, P.k, P.dtype, P.flags, P.silu_from_col = tokens, n, k, _lib.BF16, flags, n
+    P.x_row_stride, P.w_row_stride, P.out_row_stride = x_pitch or k, k, n
+    P.x, P.w, P.out, P.bias = 1 << 30, 1 << 36, 1 << 40, bias or None
+    return P
+
+
+@pytest.mark.parametrize("name", sorted(__import__("linear_plan_cases").CASES))
+def test_linear_plan_case_table(name, linear_plan):
+    """plan_linear() (compiled) on the parameter block zigma_amd.linear.linear builds for every case of the table: status, last kernel"""
+    import linear_plan_cases
+    case, want = linear_plan_cases.CASES[name]
+    got, _ = linear_plan_cases.call(case, "cpu", linear_plan)
+    assert (got["status"], got["kernel"]) == tuple(want) and (got["family"] != 0) == (want.kernel is not None)
+
+
+def test_linear_mirrors_agree_with_the_plan(linear_plan):
+    """The Python side's limits of zigma_linear_fwd's kernel families against plan_linear() (compiled), on the edges of every rule: for each of ws / ws128 /
+    sm / tiled, linear_eligible and routing._SERVES[kern] and linear._TENSOR_LIMITS[kern] hold exactly where the plan serves the call flagged for that
+    family (and panel width); routing.kernel_name is a prefix of the plan's kernel on every served cell (all inside serves_4w's stated domain:
+    contiguous out, tokens * n * 2 < 2^32; a bias alone is passed on)."""
+    from zigma_amd import linear as zl, routing as zr
+    bf = torch.bfloat16
+    flags = {"ws": zl.LINEAR_WS_FLAG, "ws128": zl.LINEAR_WS_FLAG, "sm": zl.LINEAR_SM_FLAG, "tiled": 0}
+    served_by = {"ws": lambda pl: pl["family"] == LIN_WS and pl["pw"] == 256, "ws128": lambda pl: pl["family"] == LIN_WS and pl["pw"] == 128,
+                 "sm": lambda pl: pl["family"] == LIN_SM, "tiled": lambda pl: pl["family"] in (LIN_TN, LIN_4W)}
+    seen = {kern: set() for kern in flags}
+    for tokens in (8, 104, 128, 256, 512, 8192, 65536 + 8):
+        for n in (128, 384, 640, 4096, 8192, 8320):
+            for k in (64, 128, 192, 640, 768, 1280, 1536):
+                w = _Dev(bf, n, k, ptr=1 << 36)
+                for pitch in (k, k + 4, k + 8, k + 128):
+                    x = _Dev(bf, tokens, k, ptr=1 << 30)
+                    x._strides = (pitch, 1)
+                    for bias_ptr in (0, 1 << 42, (1 << 42) + 4, (1 << 42) + 2):      # absent, or on a 16- / 4- / 2-byte boundary
+                        bias = _Dev(bf, n, ptr=bias_ptr) if bias_ptr else None
+                        assert tokens * n * 2 < 1 << 32
+                        for kern, flag in flags.items():
+                            pl = linear_plan(_linear_params(tokens, n, k, flag, pitch, bias_ptr))
+                            served = pl["status"] == 0 and served_by[kern](pl)
+                            mirror = zl.linear_eligible(x, w, bias) and zr._SERVES[kern](tokens, n, k) and zl._TENSOR_LIMITS[kern](x, bias)
+                            assert mirror == served, (kern, tokens, n, k, pitch, bias_ptr, pl)
+                            seen[kern].add(served)
+                            if served:
+                                name = zr.kernel_name(kern, tokens, n, k, bias=bias is not None, residual=False)
+                                assert pl["kernel"].startswith(name), (kern, tokens, n, k, pitch, bias_ptr, pl, name)
+    assert all(v == {True, False} for v in seen.values()), seen
+
+
 @pytest.mark.parametrize("m,n", [(65536, 2560), (65536, 512), (32768, 2560), (4096, 8192), (5632, 1024), (512 * 43, 256), (16384, 1280)])
-def test_linear_ws_work_partition_covers_every_tile_once(m, n):
-    """The workgroup -> (panel, token range) assignment of csrc/linear_ws.hip restated: XCD x = blockIdx % 8 owns the x-th eighth of the 64-token
+def test_linear_ws_work_partition_covers_every_tile_once(m, n, linear_plan):
+    """The workgroup -> (panel, token range) assignment of csrc/linear_ws.hip on the panels / ranges / tiles_per_xcd plan_linear() (compiled) launches
+    it with: XCD x = blockIdx % 8 owns the x-th eighth of the 64-token
     tiles, slot = blockIdx / 8 -> panel = slot % panels, range = slot / panels, the range's tiles split as evenly as integers allow.  Every
     (panel, tile) pair must be computed by exactly one workgroup, ranges must be non-empty, and the per-workgroup tile counts of one launch
     may differ by at most one (the kernel's load balance)."""
-    panels, tiles_per_xcd = n // 256, m // 512
-    ranges = 32 // panels
+    from zigma_amd.linear import LINEAR_WS_FLAG
+    pl = linear_plan(_linear_params(m, n, 640, LINEAR_WS_FLAG))
+    assert pl["status"] == 0 and pl["kernel"] == "linear_ws"
+    panels, ranges, tiles_per_xcd = pl["panels"], pl["ranges"], pl["tiles_per_xcd"]
     assert tiles_per_xcd >= ranges
     seen, counts = {}, []
     for block in range(256):

@@ -25,6 +25,7 @@
 //   * epilogue in registers: + bias, SiLU on output columns >= silu_from_col (in_proj emits silu(z) for the gate half:
 //     the scan then multiplies instead of evaluating exp + rcp per element, ZIGMA_SCAN_Z_PREACTIVATED), bf16 pack.
 #include "scan_helpers.h"
+#include "linear_plan.h"
 
 namespace zigma {
 
@@ -347,63 +348,43 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
     }
 }
 
-// csrc/linear4w.hip: the one-wave-per-SIMD kernel for the wide, epilogue-free projections (in_proj, to_q)
-bool linear4w_eligible(const zigma_linear_params_t &p);
-int launch_linear4w(const zigma_linear_params_t &p, hipStream_t stream);
-// csrc/linear_ws.hip: weights stationary in registers, only the tokens stream (k <= 640, n % 256 == 0)
-bool linear_ws_eligible(const zigma_linear_params_t &p);
-int launch_linear_ws(const zigma_linear_params_t &p, hipStream_t stream);
-// csrc/linear_sm.hip: few tokens — tiles of 128 tokens x n / 4 features (n % 160 == 0 or n % 192 == 0), one per workgroup
-bool linear_sm_eligible(const zigma_linear_params_t &p);
-int launch_linear_sm(const zigma_linear_params_t &p, hipStream_t stream);
+// the launchers of the other three kernel families (csrc/linear4w.hip, linear_ws.hip, linear_sm.hip): like launch_linear_tn they only map a plan to instantiations
+int launch_linear4w(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream);
+int launch_linear_ws(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream);
+int launch_linear_sm(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream);
+
+static int launch_linear_tn(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream) {
+#define ZIGMA_LIN(W_, S_, B_, R_) hipLaunchKernelGGL((linear_tn_kernel<W_, S_, B_, R_, T>), dim3(plan.grid), dim3(512), 0, stream, p, plan.tiles_m, plan.tiles_n)
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, {
+        if (plan.wide) { if (plan.bias) ZIGMA_LIN(4, 2, true, false); else ZIGMA_LIN(4, 2, false, false); }
+        else if (plan.stages == 2) { if (plan.bias) ZIGMA_LIN(2, 2, true, false); else ZIGMA_LIN(2, 2, false, false); }
+        else if (plan.res) { if (plan.bias) ZIGMA_LIN(2, 3, true, true); else ZIGMA_LIN(2, 3, false, true); }
+        else { if (plan.bias) ZIGMA_LIN(2, 3, true, false); else ZIGMA_LIN(2, 3, false, false); }
+    })
+#undef ZIGMA_LIN
+    return ZIGMA_OK;
+}
 
 }  // namespace zigma
 
 using namespace zigma;
 
+// every refusal and every kernel choice is plan_linear()'s (csrc/linear_plan.h)
 extern "C" int zigma_linear_fwd(const zigma_linear_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_linear_params_t &p = *pp;
-    if (p.m < 0 || p.n < 1 || p.k < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags & ~0xf7ff00) return ZIGMA_ERR_UNSUPPORTED;     // 0x4000: the weight-stationary kernel; 0x8000: the few-token kernel; 0x100 ... 0x1000: timing / A-B probes (tools/linear_probe.py); 0x2000: the 8-wave kernel; 0x10000 .. 0x50000: probes of the 4-wave kernel (probe builds only)
-    if (p.m == 0) return ZIGMA_OK;
-    if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.k % kLinBK != 0 || p.n % 128 != 0 || p.m % 8 != 0) return ZIGMA_ERR_SHAPE;
-    if (p.m * p.x_row_stride * 2 > 0x7fffffff || static_cast<int64_t>(p.n) * p.w_row_stride * 2 > 0x7fffffff ||
-        256 * p.out_row_stride * 2 > 0x7fffffff)
-        return ZIGMA_ERR_SHAPE;                       // 32-bit lane offsets inside an operand tile / a wave's output rows
-    if (p.silu_from_col < 0 || p.silu_from_col % 32 != 0) return ZIGMA_ERR_SHAPE;
-    if (p.x_row_stride % 8 != 0 || p.w_row_stride % 8 != 0 || p.out_row_stride % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.w)) % 16 != 0 || reinterpret_cast<uintptr_t>(p.out) % 8 != 0)
-        return ZIGMA_ERR_STRIDE;
+    const LinearPlan plan = plan_linear(p);
+    if (plan.family == kLinNone) return plan.status;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int tiles_m = static_cast<int>((p.m + kLinBM - 1) / kLinBM);
-    if (p.residual) {                     // gated residual epilogue
-        if (!p.gate || p.rows_per_batch < 1 || p.rows_per_batch % 256 != 0 || p.m % p.rows_per_batch != 0) return ZIGMA_ERR_SHAPE;
-        if (p.res_row_stride % 8 != 0 || p.gate_batch_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.residual) % 16 != 0 ||
-            reinterpret_cast<uintptr_t>(p.gate) % 16 != 0 || 256 * p.res_row_stride * 2 > 0x7fffffff)
-            return ZIGMA_ERR_STRIDE;
+    int rc = ZIGMA_OK;
+    switch (plan.family) {
+        case kLinWs: rc = launch_linear_ws(p, plan, stream); break;
+        case kLinSm: rc = launch_linear_sm(p, plan, stream); break;
+        case kLin4w: rc = launch_linear4w(p, plan, stream); break;
+        default: rc = launch_linear_tn(p, plan, stream);
     }
-    if (p.bias && (p.n > 4096 || reinterpret_cast<uintptr_t>(p.bias) % 4 != 0)) return ZIGMA_ERR_SHAPE;
-    if (p.flags & 0x4000) return linear_ws_eligible(p) ? launch_linear_ws(p, stream) : ZIGMA_ERR_UNSUPPORTED;
-    if (p.flags & 0x8000) return linear_sm_eligible(p) ? launch_linear_sm(p, stream) : ZIGMA_ERR_UNSUPPORTED;
-    if (linear4w_eligible(p)) return launch_linear4w(p, stream);        // (needs flags == 0: any probe flag pins the 8-wave kernel)
-    const bool wide = p.n % 256 == 0 && !(p.flags & 0x1000) && !p.residual;      // 0x1000: force the 256 x 128 tile (probe)
-    const int tiles_n = p.n / (wide ? 256 : 128);
-    const int64_t n_tiles = static_cast<int64_t>(tiles_m) * tiles_n;
-    if (n_tiles > 0x7fffffff) return ZIGMA_ERR_SHAPE;
-    int grid = 256;                                  // one persistent workgroup per CU; multiples of 8 keep the XCD map
-    if (n_tiles < grid) grid = static_cast<int>((n_tiles + 7) / 8 * 8);
-#define ZIGMA_LIN(W_, S_, B_, R_) hipLaunchKernelGGL((linear_tn_kernel<W_, S_, B_, R_, T>), dim3(grid), dim3(512), 0, stream, p, tiles_m, tiles_n)
-    ZIGMA_DISPATCH_16BIT(p.dtype, T, {
-        if (wide) { if (p.bias) ZIGMA_LIN(4, 2, true, false); else ZIGMA_LIN(4, 2, false, false); }
-        else if (p.flags & 0x800) { if (p.bias) ZIGMA_LIN(2, 2, true, false); else ZIGMA_LIN(2, 2, false, false); }      // 0x800: two stages (probe)
-        else if (p.residual) { if (p.bias) ZIGMA_LIN(2, 3, true, true); else ZIGMA_LIN(2, 3, false, true); }
-        else { if (p.bias) ZIGMA_LIN(2, 3, true, false); else ZIGMA_LIN(2, 3, false, false); }
-    })
-#undef ZIGMA_LIN
-    set_last_kernel(wide ? "linear_tn_256x256" : "linear_tn_256x128");
+    if (rc != ZIGMA_OK) return rc;
+    set_last_kernel(plan.kernel);
     return check_launch();
 }

@@ -16,6 +16,7 @@
 // n % 128 == 0, k % 64 == 0, k >= 192, at least 256 tiles; gated residual: residual rows in the output's pitch (a multiple of 128
 // elements), samples of 2^i >= 128 rows; a bias only together with the gated residual (to_out), n <= 8192.
 #include "zigma_common.h"
+#include "linear_plan.h"
 #include "linear4w_body.inc"
 #include "linear4w_body_f16.inc"      // the same loops for fp16 operands (generator cfg f16=True; written by zigma_amd/build.py, not committed): bodies only
 
@@ -102,57 +103,25 @@ void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int
 #undef ZIGMA_L4W_ASM
 }
 
-// which variant serves the call, or -1
-static int linear4w_variant(const zigma_linear_params_t &p) {
-#ifdef ZIGMA_LINEAR4W_PROBES
-    if (p.flags & ~0xf70000) return -1;                    // 0x10000 .. 0x70000: probe variant 1 .. 7; 0x100000 * k: start skew
-#else
-    if (p.flags) return -1;
-#endif
-    if (p.silu_from_col < p.n) return -1;
-    if (p.m % 256 != 0 || p.n % 128 != 0 || p.k % 64 != 0 || p.k < 192 || p.k / 64 > 4095) return -1;
-    if (p.out_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0) return -1;               // 16-byte stores
-    if (p.m * p.out_row_stride * 2 > 0xffffffffll) return -1;                                                // 32-bit tile offsets
-    const int64_t tiles_n = p.n / 256 + (p.n % 256 != 0), n_tiles = (p.m / 256) * tiles_n;
-    if (n_tiles < 256 || n_tiles > 0x7fffffff || tiles_n > 1023 || p.m / 256 > 0xfffff) return -1;   // >= one tile per CU (smaller: the 8-wave kernel)
-    int epi = p.n % 256 != 0 ? 1 : 0;
-    if (p.residual) {
-        if (!p.gate || p.res_row_stride != p.out_row_stride || p.out_row_stride % 128 != 0) return -1;
-        if (p.rows_per_batch < 128 || (p.rows_per_batch & (p.rows_per_batch - 1)) != 0 || p.m % p.rows_per_batch != 0) return -1;
-        if (reinterpret_cast<uintptr_t>(p.residual) % 16 != 0 || reinterpret_cast<uintptr_t>(p.gate) % 16 != 0 || p.gate_batch_stride % 8 != 0) return -1;
-        epi = 2;
-    }
-    if (p.bias) {
-        if (!p.residual || p.n > 8192 || reinterpret_cast<uintptr_t>(p.bias) % 2 != 0) return -1;
-        epi = 3;
-    }
-    if (epi != 0 && (p.flags >> 16)) return -1;
-    return epi;
-}
-
-bool linear4w_eligible(const zigma_linear_params_t &p) { return linear4w_variant(p) >= 0; }
-
-int launch_linear4w(const zigma_linear_params_t &p, hipStream_t stream) {
-    const int n_wide = p.n / 256, tiles_n = n_wide + (p.n % 256 != 0);
-    const int n_tiles = static_cast<int>((p.m / 256) * tiles_n);
-    const dim3 grid(256), block(256);
-#define ZIGMA_L4W(E_, V_) hipLaunchKernelGGL((linear4w_kernel<E_, V_>), grid, block, 0, stream, p, tiles_n, n_wide, n_tiles)
-#define ZIGMA_L4W_F16(E_) hipLaunchKernelGGL((linear4w_kernel<E_, 0, F16>), grid, block, 0, stream, p, tiles_n, n_wide, n_tiles)
+// plan.epi, plan.probe: EPI and VARIANT (a probe variant only with EPI 0 and bf16: plan_linear)
+int launch_linear4w(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream) {
+    const dim3 grid(plan.grid), block(256);
+#define ZIGMA_L4W(E_, V_) hipLaunchKernelGGL((linear4w_kernel<E_, V_>), grid, block, 0, stream, p, plan.tiles_n, plan.n_wide, plan.n_tiles)
+#define ZIGMA_L4W_F16(E_) hipLaunchKernelGGL((linear4w_kernel<E_, 0, F16>), grid, block, 0, stream, p, plan.tiles_n, plan.n_wide, plan.n_tiles)
     if (p.dtype == ZIGMA_F16) {
-        if ((p.flags >> 16) & 7) return ZIGMA_ERR_UNSUPPORTED;              // (probe variants: bf16 only)
-        switch (linear4w_variant(p)) {
+        switch (plan.epi) {
             case 1: ZIGMA_L4W_F16(1); break;
             case 2: ZIGMA_L4W_F16(2); break;
             case 3: ZIGMA_L4W_F16(3); break;
             default: ZIGMA_L4W_F16(0);
         }
     } else
-    switch (linear4w_variant(p)) {
+    switch (plan.epi) {
         case 1: ZIGMA_L4W(1, 0); break;
         case 2: ZIGMA_L4W(2, 0); break;
         case 3: ZIGMA_L4W(3, 0); break;
         default:
-            switch ((p.flags >> 16) & 7) {
+            switch (plan.probe) {
 #ifdef ZIGMA_LINEAR4W_PROBES
                 case 1: ZIGMA_L4W(0, 1); break;
                 case 2: ZIGMA_L4W(0, 2); break;
@@ -167,8 +136,7 @@ int launch_linear4w(const zigma_linear_params_t &p, hipStream_t stream) {
     }
 #undef ZIGMA_L4W_F16
 #undef ZIGMA_L4W
-    set_last_kernel(p.n % 256 ? "linear4w_256x256+128" : "linear4w_256x256");
-    return check_launch();
+    return ZIGMA_OK;
 }
 
 }  // namespace zigma

@@ -17,6 +17,7 @@
 //   the token rows.
 // Limits: bf16 or fp16 (template parameter T), no activation (bias and the gated residual: template flag EPI), k % 64 == 0 and k >= 128, m % 128 == 0, n % (32 NBLK) == 0 for NBLK = 5, 6 or 4 (tried in that order).
 #include "scan_helpers.h"
+#include "linear_plan.h"
 
 namespace zigma {
 namespace lsm {
@@ -186,36 +187,14 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
 
 }  // namespace lsm
 
-// feature blocks per tile (5: n % 160 == 0; 6: n % 192 == 0; 4: n % 128 == 0) the few-token kernel uses for the call, or 0 if it does not serve it
-static int linear_sm_blocks(const zigma_linear_params_t &p) {
-    if (p.silu_from_col < p.n) return 0;
-    if (p.k % 64 != 0 || p.k < 128 || p.m % 128 != 0 || p.m < 128) return 0;
-    if (p.out_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0) return 0;
-    if (128 * p.x_row_stride * 2 > 0x7fffffff || 192 * p.w_row_stride * 2 > 0x7fffffff) return 0;
-    if (p.bias && reinterpret_cast<uintptr_t>(p.bias) % 8 != 0) return 0;
-    if (p.residual) {       // (zigma_linear_fwd has checked pointers, pitches and rows_per_batch % 256 == 0 already)
-        if (!p.gate || p.rows_per_batch % 128 != 0) return 0;
-    }
-    const int nblk = p.n % 160 == 0 ? 5 : p.n % 192 == 0 ? 6 : p.n % 128 == 0 ? 4 : 0;
-    if (!nblk) return 0;
-    if ((p.m / 128) * (p.n / (32 * nblk)) > 0x7fffffff) return 0;
-    return nblk;
-}
-
-bool linear_sm_eligible(const zigma_linear_params_t &p) { return linear_sm_blocks(p) != 0; }
-
-int launch_linear_sm(const zigma_linear_params_t &p, hipStream_t stream) {
-    const int nblk = linear_sm_blocks(p);
-    if (!nblk) return ZIGMA_ERR_UNSUPPORTED;
-    const int tiles_n = p.n / (32 * nblk);
-    const dim3 grid(static_cast<unsigned>((p.m / 128) * tiles_n)), block(256);
-    const bool epi = p.bias || p.residual;
-#define ZIGMA_LSM(N_) do { if (epi) hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, true, T>), grid, block, 0, stream, p, tiles_n); \
-                           else hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, false, T>), grid, block, 0, stream, p, tiles_n); } while (0)
-    ZIGMA_DISPATCH_16BIT(p.dtype, T, { if (nblk == 5) ZIGMA_LSM(5); else if (nblk == 6) ZIGMA_LSM(6); else ZIGMA_LSM(4); })
+// plan.nblk, plan.epi: NBLK and EPI
+int launch_linear_sm(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream) {
+    const dim3 grid(static_cast<unsigned>(plan.grid)), block(256);
+#define ZIGMA_LSM(N_) do { if (plan.epi) hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, true, T>), grid, block, 0, stream, p, plan.tiles_n); \
+                           else hipLaunchKernelGGL((lsm::linear_sm_kernel<N_, false, T>), grid, block, 0, stream, p, plan.tiles_n); } while (0)
+    ZIGMA_DISPATCH_16BIT(p.dtype, T, { if (plan.nblk == 5) ZIGMA_LSM(5); else if (plan.nblk == 6) ZIGMA_LSM(6); else ZIGMA_LSM(4); })
 #undef ZIGMA_LSM
-    set_last_kernel(nblk == 5 ? "linear_sm_128x160" : nblk == 6 ? "linear_sm_128x192" : "linear_sm_128x128");
-    return check_launch();
+    return ZIGMA_OK;
 }
 
 }  // namespace zigma

@@ -21,6 +21,7 @@
 // instantiated, is bit-identical too and does NOT beat the tiled kernel: out_proj shape 102 vs 97 us, to_out shape 48 vs 45 us, its
 // MFMA-only loop 74.5 us against 65 at the FB = 2 rate (profiles/r04_h_linear_ws_probe_128_panels.jsonl) — not shipped.
 #include "zigma_common.h"
+#include "linear_plan.h"
 
 #include <utility>
 
@@ -361,55 +362,25 @@ void linear_ws_kernel(const zigma_linear_params_t p, const int panels, const int
 
 }  // namespace lws
 
-// features per panel the weight-stationary kernel uses for the call (256: k = 512 / 640, two 32-feature blocks per wave; 128: k = 1280 / 1536, one
-// block per wave — the out_proj shapes at serving-size token counts, round 5), or 0 if it does not serve it
-static int linear_ws_panel(const zigma_linear_params_t &p) {
-    if (p.bias || p.residual) return 0;
-    const bool narrow = p.k == 1280 || p.k == 1536;
-    if (!narrow && p.k != 512 && p.k != 640) return 0;                                                // (instantiation set: k / 16 = 32, 40 | 80, 96)
-    const int pw = narrow ? 128 : 256;
-    if (p.silu_from_col < p.n && (narrow || p.silu_from_col < 0 || p.silu_from_col % 128 != 0)) return 0;     // a wave (64 features) is all-or-nothing
-    if (p.n % pw != 0 || p.n > 8192 || p.m % 512 != 0) return 0;
-    if (p.out_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0) return 0;
-    const int panels = p.n / pw;
-    if (panels > 32) return 0;
-    const int ranges = 32 / panels;
-    const int64_t tiles_per_xcd = p.m / 512;
-    if (tiles_per_xcd < ranges || tiles_per_xcd > 0x7fffff) return 0;
-    if (p.out_row_stride * 2 * 16 > 0x7fffffff) return 0;      // 32-bit lane offset of a store (up to 16 rows)
-    // (slot swizzle in the low byte of the lane offset; 32-bit offsets inside a slice)
-    if (p.x_row_stride % 128 != 0 || 64 * p.x_row_stride * 2 >= 0x7fffffff) return 0;
-    return pw;
-}
-
-bool linear_ws_eligible(const zigma_linear_params_t &p) { return linear_ws_panel(p) != 0; }
-
-int launch_linear_ws(const zigma_linear_params_t &p, hipStream_t stream) {
-    const int pw = linear_ws_panel(p);
-    if (!pw) return ZIGMA_ERR_UNSUPPORTED;
-    const int panels = p.n / pw, ranges = 32 / panels, tiles_per_xcd = static_cast<int>(p.m / 512);
-    const int probe = (p.flags >> 16) & 7;
-    const dim3 grid(256), block(256);
-    const bool sl = p.silu_from_col < p.n;
-#define ZIGMA_LWS(KG_, FB_, P_) do { if (sl) hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, true, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); \
-                                     else hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd); } while (0)
+// plan.pw, plan.silu, plan.probe: FB, SL and PROBE (a probe form only in the probe library, SiLU and probes only with 256-feature panels: plan_linear)
+int launch_linear_ws(const zigma_linear_params_t &p, const LinearPlan &plan, hipStream_t stream) {
+    const dim3 grid(plan.grid), block(256);
+#define ZIGMA_LWS_(KG_, FB_, P_, SL_) hipLaunchKernelGGL((lws::linear_ws_kernel<KG_, FB_, P_, SL_, T>), grid, block, 0, stream, p, plan.panels, plan.ranges, plan.tiles_per_xcd)
+#define ZIGMA_LWS(KG_, FB_, P_) do { if (plan.silu) ZIGMA_LWS_(KG_, FB_, P_, true); else ZIGMA_LWS_(KG_, FB_, P_, false); } while (0)
 #ifdef ZIGMA_LINEAR4W_PROBES
-#define ZIGMA_LWS_K(KG_, FB_) { if (probe == 1) ZIGMA_LWS(KG_, FB_, 1); else if (probe == 2) ZIGMA_LWS(KG_, FB_, 2); else if (probe == 3) ZIGMA_LWS(KG_, FB_, 3); else if (probe == 4) ZIGMA_LWS(KG_, FB_, 4); else ZIGMA_LWS(KG_, FB_, 0); }
+#define ZIGMA_LWS_K(KG_, FB_) { if (plan.probe == 1) ZIGMA_LWS(KG_, FB_, 1); else if (plan.probe == 2) ZIGMA_LWS(KG_, FB_, 2); else if (plan.probe == 3) ZIGMA_LWS(KG_, FB_, 3); else if (plan.probe == 4) ZIGMA_LWS(KG_, FB_, 4); else ZIGMA_LWS(KG_, FB_, 0); }
 #else
-#define ZIGMA_LWS_K(KG_, FB_) { if (probe) return ZIGMA_ERR_UNSUPPORTED; ZIGMA_LWS(KG_, FB_, 0); }
+#define ZIGMA_LWS_K(KG_, FB_) ZIGMA_LWS(KG_, FB_, 0);
 #endif
     ZIGMA_DISPATCH_16BIT(p.dtype, T, {
         if (p.k == 640) ZIGMA_LWS_K(40, 2) else if (p.k == 512) ZIGMA_LWS_K(32, 2)
-        else {      // one 32-feature block per wave (128-feature panels): k = 1280 / 1536
-            if (probe || sl) return ZIGMA_ERR_UNSUPPORTED;
-            if (p.k == 1280) hipLaunchKernelGGL((lws::linear_ws_kernel<80, 1, 0, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
-            else hipLaunchKernelGGL((lws::linear_ws_kernel<96, 1, 0, false, T>), grid, block, 0, stream, p, panels, ranges, tiles_per_xcd);
-        }
+        else if (p.k == 1280) ZIGMA_LWS_(80, 1, 0, false);      // one 32-feature block per wave (128-feature panels): k = 1280 / 1536
+        else ZIGMA_LWS_(96, 1, 0, false);
     })
 #undef ZIGMA_LWS_K
 #undef ZIGMA_LWS
-    set_last_kernel(sl ? "linear_ws_silu" : pw == 128 ? "linear_ws_128" : "linear_ws");
-    return check_launch();
+#undef ZIGMA_LWS_
+    return ZIGMA_OK;
 }
 
 }  // namespace zigma

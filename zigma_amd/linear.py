@@ -1,7 +1,9 @@
 """Dense projections on the hand-written MFMA kernel (zigma_linear_fwd): in_proj / out_proj of the Mamba mixer and
 to_q / to_out of the cross-attention (reference call sites mamba_simple.py:290-294, selective_scan_interface.py:365,
 model_zigma.py:104-135, all `F.linear`), the text projections and the training path's forward product and dX (wgrad.LinearTrainFn, whose plan()
-runs with autograd off); linear_eligible itself refuses tensors that require grad.  Which kernel serves which call: plan() and zigma_amd/routing.py."""
+runs with autograd off); linear_eligible itself refuses tensors that require grad.  Which kernel serves which call: plan() and zigma_amd/routing.py.
+The library's own refusals and kernel choice are plan_linear() (csrc/linear_plan.h); linear_eligible, _TENSOR_LIMITS and routing.serves_* restate its limits
+for tensors and shapes, and tests/test_host_cpu.py checks them against the compiled header."""
 import torch
 
 from . import _lib

@@ -15,8 +15,9 @@ kernel = which kernel family of zigma_linear_fwd serves it (KERNELS below), or "
 fuse_add = the caller hands the gated residual to the kernel's epilogue (True) or leaves it to the next norm kernel (False).
 
 The table holds POLICY (what is fastest where, with the measurement that decided it); the shape LIMITS of each kernel family are the
-`serves_*` functions, mirrored from the C side (csrc/linear_ws.hip linear_ws_panel, csrc/linear_sm.hip linear_sm_blocks, csrc/linear4w.hip
-linear4w_variant, zigma_linear_fwd) — a row never returns a kernel whose limits the shape does not meet.  linear.plan walks candidates() and
+`serves_*` functions: the shape part of plan_linear() (csrc/linear_plan.h, where every refusal and kernel choice of zigma_linear_fwd lives), restated here
+because the table is consulted before a parameter block exists and on machines without the library; tests/test_host_cpu.py compiles the header and pins
+them to it (test_linear_mirrors_agree_with_the_plan) — a row never returns a kernel whose limits the shape does not meet.  linear.plan walks candidates() and
 checks each kernel's limits on the tensors (pointer / stride alignment, bias); a row the tensors refuse is counted in REFUSED and the walk goes on
 to the next row (never silent: tests assert REFUSED stays empty on the shipped shapes).
 
@@ -49,7 +50,7 @@ INF = 1 << 40
 REFUSED = []          # (role, tokens, n, k, kernel) of rows a call matched and the tensor-level check of linear.py turned down (the last 64 of them)
 
 
-# ---- shape limits of the kernel families (C side mirrored) ---------------------------------------------------------------------------------
+# ---- shape limits of the kernel families (plan_linear's, pinned by test) ---------------------------------------------------------------------------------
 def serves_tiled(tokens, n, k):
     return tokens > 0 and tokens % 8 == 0 and n % 128 == 0 and k % 64 == 0
 
@@ -59,7 +60,10 @@ def tiles_4w(tokens, n):
 
 
 def serves_4w(tokens, n, k):
-    """the generated one-wave-per-SIMD kernel takes the call (linear4w_variant): whole 256-token tiles, at least one tile per CU"""
+    """the generated one-wave-per-SIMD kernel takes the call: whole 256-token tiles, k >= 192, at least one tile per CU.  Equals plan_linear()'s choice
+    between the 4-wave and the 8-wave kernel (linear4w_variant in csrc/linear_plan.h) on this domain: a call without flags or SiLU range, no bias alone
+    (a bias without the gated residual runs on the 8-wave kernel), contiguous 16-byte aligned out, tokens * n * 2 < 2^32; with the gated residual
+    also samples of 2^i rows and residual rows in the output's pitch, a multiple of 128 elements."""
     return tokens % 256 == 0 and n % 128 == 0 and k % 64 == 0 and k >= 192 and tiles_4w(tokens, n) >= 256
 
 
@@ -68,7 +72,7 @@ def ws_panel_width(k):
 
 
 def serves_ws(tokens, n, k):
-    """linear_ws_panel: instantiated k, whole panels, at most 32 of them, every workgroup of an XCD owns a 512-token tile"""
+    """linear_ws_panel (csrc/linear_plan.h): instantiated k, whole panels, at most 32 of them, every workgroup of an XCD owns a 512-token tile"""
     pw = ws_panel_width(k)
     if not pw or n % pw or n > 8192 or n // pw > 32 or tokens % 512:
         return False
@@ -180,12 +184,13 @@ def route(role, tokens, n, k):
     return next(candidates(role, tokens, n, k))
 
 
-def kernel_name(route_or_kernel, tokens=None, n=None, k=None):
-    """what zigma_last_kernel() reports for a call served by this route (prefix for the families with several tile shapes)"""
+def kernel_name(route_or_kernel, tokens=None, n=None, k=None, bias=False, residual=False):
+    """what zigma_last_kernel() reports for a call served by this route (prefix for the families with several tile shapes); bias / residual: the
+    epilogue operands of the call — a bias without the gated residual runs on the 8-wave kernel (serves_4w's domain)"""
     kern = route_or_kernel.kernel if isinstance(route_or_kernel, Route) else route_or_kernel
     if kern in ("tiled", "tiled_halves"):
         if tokens is None:
             return "linear"
         nn = n // 2 if kern == "tiled_halves" else n
-        return ("linear4w_256x256+128" if nn % 256 else "linear4w_256x256") if serves_4w(tokens, nn, k) else "linear_tn_"
+        return ("linear4w_256x256+128" if nn % 256 else "linear4w_256x256") if serves_4w(tokens, nn, k) and (residual or not bias) else "linear_tn_"
     return {"ws": "linear_ws", "ws128": "linear_ws_128", "sm": "linear_sm_", "split3": "linear_split3_", "split1": "linear_split1_", "library": "library"}[kern]
