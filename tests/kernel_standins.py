@@ -278,12 +278,12 @@ def _dt_proj_fwd(P):
     return "dt_proj_softplus_mfma"
 
 
-def install_lib_call(monkeypatch, plan):
-    """route _lib.call to the stand-ins above.  plan: plan_scan() compiled with g++ (the scan_plan fixture of tests/test_host_cpu.py): names
-    the kernel, fills `info` and refuses what the library refuses"""
+def install_lib_call(monkeypatch, plan=None):
+    """route _lib.call to the stand-ins above and below.  plan: plan_scan() compiled with g++ (the scan_plan fixture of tests/test_host_cpu.py):
+    names the scan's kernel, fills `info` and refuses what the library refuses (only the scan needs it)"""
     from zigma_amd import _lib
     serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": _conv_xproj_fwd, "zigma_x_proj_fwd": _x_proj_fwd,
-             "zigma_dt_proj_softplus_fwd": _dt_proj_fwd}
+             "zigma_dt_proj_softplus_fwd": _dt_proj_fwd, **OUTER_SERVE}
 
     def call(fn_name, params, device):
         LAST_KERNEL[0] = serve[fn_name](params)
@@ -292,3 +292,193 @@ def install_lib_call(monkeypatch, plan):
     monkeypatch.setattr(_lib, "call", call)
     monkeypatch.setattr(_lib, "require_device", lambda *t: torch.device("cpu"))
     monkeypatch.setattr(_lib, "last_kernel", lambda: LAST_KERNEL[0])
+
+
+# ---------------------------------------------------------------------------------------------------
+# Stand-ins AT THE C ABI for add-norm forward and the operators around the blocks (tests/test_gpu_outer_fwd.py on the CPU).  The torch_*
+# functions are float64 torch restatements of the five operators (F.layer_norm, F.linear, unfold + matmul, TimestepEmbedder.timestep_embedding),
+# UNROUNDED except at the 16-bit intermediates the ABI defines; the CPU test holds the numpy references of tests/outer_fwd_cases.py against
+# them.  The _*_fwd functions read and write through the parameter block's pointers and strides, refuse what the library refuses and name the
+# kernel the library would name (add_norm: launch_norm's selection restated on the block's pointers and pitches; LAST_INSTANTIATION).
+# ---------------------------------------------------------------------------------------------------
+LAST_INSTANTIATION = [None]
+F = torch.nn.functional
+
+
+def _r(t, dt):
+    """a float64 tensor after being stored in dt (through fp32, as the kernels and the numpy references round)"""
+    return t.float().to(dt).double()
+
+
+def _refuse(rc):
+    raise RuntimeError(f"stand-in: refused (status {rc})")
+
+
+def torch_add_norm(x, branch, gate, residual, weight, bias, shift, scale, eps, is_rms, xdt):
+    """everything (rows, cols) float64 or None (gate / shift / scale already expanded over the rows) -> dict(x_out, residual_out, y_out, y_mod)"""
+    r = {}
+    if branch is not None:
+        r["x_out"] = x + gate * branch
+        x = _r(r["x_out"], xdt)
+    if residual is not None:
+        x = x + residual
+    r["residual_out"] = x
+    cols = x.shape[-1]
+    if is_rms:
+        y = x * torch.rsqrt((x * x).mean(-1, keepdim=True) + eps)
+        y = y if weight is None else y * weight
+        y = y if bias is None else y + bias
+    else:
+        y = F.layer_norm(x, (cols,), weight, bias, eps)
+    r["y_out"] = y
+    if shift is not None:
+        r["y_mod"] = _r(y, xdt) * (1.0 + scale) + shift
+    return r
+
+
+def _norm_instantiation(P, es):
+    """launch_norm of csrc/add_norm.hip -> ((VEC, ITERS, LPR), kernel name); es: element sizes of (x, residual, weight, modulation)"""
+    xs, rs, ws, ms = es
+    strides = [P.x_row_stride, P.branch_row_stride, P.x_out_row_stride, P.res_row_stride, P.res_out_row_stride, P.y_row_stride, P.y_mod_row_stride,
+               P.mod_batch_stride]
+    ptrs = [(P.x, xs), (P.branch, xs), (P.x_out, xs), (P.y_out, xs), (P.y_mod, xs), (P.residual, rs), (P.residual_out, rs), (P.weight, ws), (P.bias, ws),
+            (P.gate, ms), (P.shift, ms), (P.scale, ms)]
+    al = lambda n: all(not p or p % (n * s) == 0 for p, s in ptrs)
+    vec = P.cols % 4 == 0 and all(s % 4 == 0 for s in strides) and al(4)
+    al8 = all(not p or p % (16 if (p in (P.residual, P.residual_out)) else 8 * s) == 0 for p, s in ptrs)
+    vec8 = vec and P.cols % 8 == 0 and all(s % 8 == 0 for s in strides) and al8 and xs == 2
+    light = (not P.residual and not P.residual_out) or rs == 2
+    name = "add_norm_v4" if vec else "add_norm_v1"
+    if vec8 and light and P.cols % 128 == 0 and P.cols <= 1024 and P.rows % 4 == 0 and not P.flags & 1:
+        return (8, P.cols // 128, 16), "add_norm_v8x4"
+    if vec8 and P.cols <= 1024:
+        return (8, 2, 64), name
+    if vec and P.cols <= 1024:
+        return (4, 4, 64), name
+    if vec and P.cols <= 4096:
+        return (4, 16, 64), name
+    if P.cols <= 1024:
+        return (1, 16, 64), name
+    if P.cols <= 4096:
+        return (1, 64, 64), name
+    _refuse(-2)
+
+
+def _add_norm_fwd(P):
+    if not P.x or bool(P.branch) != bool(P.gate) or bool(P.shift) != bool(P.scale) or (P.shift and not P.y_mod) or not (P.y_out or P.y_mod):
+        _refuse(-1)
+    if P.rows < 0 or P.cols < 1 or P.rows_per_batch < 1:
+        _refuse(-2)
+    if P.flags & ~1:
+        _refuse(-6)
+    xdt, rdt, wdt = _io_dtype(P.x_dtype), _io_dtype(P.res_dtype), _io_dtype(P.w_dtype)
+    if (P.mod_dtype != P.x_dtype and (P.gate or P.shift)) or (P.res_dtype not in (0, P.x_dtype)) or (P.w_dtype not in (0, P.x_dtype)):
+        _refuse(-3)
+    es = [torch.empty((), dtype=d).element_size() for d in (xdt, rdt, wdt, xdt)]
+    inst, name = _norm_instantiation(P, es)
+    rows, cols, nb = P.rows, P.cols, -(-P.rows // P.rows_per_batch)
+    row = lambda ptr, stride, dt: _view(ptr, (rows, cols), (stride, 1), dt)
+    d = lambda t: None if t is None else t.double()
+    mod = lambda ptr: None if not ptr else _view(ptr, (nb, cols), (P.mod_batch_stride, 1), xdt).double().repeat_interleave(P.rows_per_batch, 0)[:rows]
+    r = torch_add_norm(d(row(P.x, P.x_row_stride, xdt)), d(row(P.branch, P.branch_row_stride, xdt)), mod(P.gate), d(row(P.residual, P.res_row_stride, rdt)),
+                       d(_view(P.weight, (cols,), (1,), wdt)), d(_view(P.bias, (cols,), (1,), wdt)), mod(P.shift), mod(P.scale), float(P.eps), bool(P.is_rms), xdt)
+    for key, ptr, stride, dt in (("x_out", P.x_out, P.x_out_row_stride, xdt), ("residual_out", P.residual_out, P.res_out_row_stride, rdt),
+                                 ("y_out", P.y_out, P.y_row_stride, xdt), ("y_mod", P.y_mod, P.y_mod_row_stride, xdt)):
+        if ptr and key in r:
+            row(ptr, stride, dt).copy_(r[key].float().to(dt))
+    LAST_INSTANTIATION[0] = inst
+    return name
+
+
+def torch_patch_embed(x, w, bias, pos):
+    """x (B, C, H, W), w (E, C, p, p), bias (E) | None, pos (L, E) | None, float64 -> (B, L, E): unfold + matmul; conv + bias is a bf16 tensor
+    before `+ pos`"""
+    E, p = w.shape[0], w.shape[-1]
+    cols = F.unfold(x, kernel_size=p, stride=p).transpose(1, 2)            # (B, L, C p p), (channel, dy, dx) fastest
+    conv = cols @ w.reshape(E, -1).T
+    conv = conv if bias is None else conv + bias
+    return conv if pos is None else _r(conv, torch.bfloat16) + pos
+
+
+def _patch_embed_fwd(P):
+    if P.batch < 0 or P.in_chans < 1 or P.patch < 1 or P.embed_dim < 8 or P.height < 1 or P.width < 1:
+        _refuse(-2)
+    if P.dtype != 2:
+        _refuse(-3)
+    B, C, p, E, H, W = P.batch, P.in_chans, P.patch, P.embed_dim, P.height, P.width
+    if E % 8 or H % p or W % p or C * p * p * E * 4 > 65536:
+        _refuse(-2)
+    if P.out % 16 or P.out_row_stride % 8 or P.out_batch_stride % 8 or P.weight % 16 or (P.bias and P.bias % 16) or (P.pos and (P.pos % 16 or P.pos_row_stride % 8)):
+        _refuse(-4)
+    bf, L = torch.bfloat16, (H // p) * (W // p)
+    d = lambda t: None if t is None else t.double()
+    x = _view(P.x, (B, C, H, W), (P.x_batch_stride, P.x_chan_stride, P.x_row_stride, 1), bf)
+    r = torch_patch_embed(d(x), d(_view(P.weight, (E, C, p, p), _contig((E, C, p, p)), bf)), d(_view(P.bias, (E,), (1,), bf)),
+                          d(_view(P.pos, (L, E), (P.pos_row_stride, 1), bf)))
+    _view(P.out, (B, L, E), (P.out_batch_stride, P.out_row_stride, 1), bf).copy_(r.float().to(bf))
+    return "patch_embed"
+
+
+def torch_timestep_embed(t, freqs, dim):
+    """t (B,), freqs (dim // 2,) float64 -> (B, dim) float64 through the model's own timestep_embedding"""
+    from zigma_amd.model_zigma import TimestepEmbedder
+    return TimestepEmbedder.timestep_embedding(t.float(), dim, dtype=torch.float64, freqs=freqs)       # (t holds bf16 values: .float() is exact)
+
+
+def _timestep_embed_fwd(P):
+    if P.batch < 0 or P.dim < 2:
+        _refuse(-2)
+    if P.dtype != 2:
+        _refuse(-3)
+    bf = torch.bfloat16
+    r = torch_timestep_embed(_view(P.t, (P.batch,), (1,), bf).double(), _view(P.freqs, (P.dim // 2,), (1,), bf).double(), P.dim)
+    _view(P.out, (P.batch, P.dim), (P.out_row_stride, 1), bf).copy_(r.float().to(bf))
+    return "timestep_embed"
+
+
+def torch_skinny_linear(x, w, bias, silu):
+    if silu:
+        x = _r(F.silu(x), torch.bfloat16)
+    return F.linear(x, w, bias)
+
+
+def _skinny_linear_fwd(P):
+    if P.m < 0 or P.n < 0 or P.k < 0:
+        _refuse(-2)
+    if P.dtype != 2:
+        _refuse(-3)
+    if P.m > 64 or P.n % 16 or P.k % 128 or P.k > 1024:
+        _refuse(-2)
+    if P.x % 16 or P.x_row_stride % 8 or P.w % 16 or P.w_row_stride % 8 or P.out % 8 or P.out_row_stride % 4 or (P.bias and P.bias % 8):
+        _refuse(-4)
+    bf = torch.bfloat16
+    x, w = _view(P.x, (P.m, P.k), (P.x_row_stride, 1), bf), _view(P.w, (P.n, P.k), (P.w_row_stride, 1), bf)
+    bias = _view(P.bias, (P.n,), (1,), bf)
+    r = torch_skinny_linear(x.double(), w.double(), None if bias is None else bias.double(), bool(P.flags & 1))
+    _view(P.out, (P.m, P.n), (P.out_row_stride, 1), bf).copy_(r.float().to(bf))
+    return "skinny_linear_mfma"
+
+
+def torch_final_layer(x, w, bias, eps):
+    return F.linear(_r(F.layer_norm(x, (x.shape[-1],), eps=eps), torch.bfloat16), w, bias)
+
+
+def _final_layer_fwd(P):
+    if P.rows < 0 or P.cols < 8 or P.n_out < 1:
+        _refuse(-2)
+    if P.dtype != 2:
+        _refuse(-3)
+    if P.cols % 8 or P.cols > 2048 or P.n_out > 16:
+        _refuse(-2)
+    if P.x % 16 or P.x_row_stride % 8 or P.weight % 16:
+        _refuse(-4)
+    bf = torch.bfloat16
+    x, w = _view(P.x, (P.rows, P.cols), (P.x_row_stride, 1), bf), _view(P.weight, (P.n_out, P.cols), (P.cols, 1), bf)
+    bias = _view(P.bias, (P.n_out,), (1,), bf)
+    r = torch_final_layer(x.double(), w.double(), None if bias is None else bias.double(), float(P.eps))
+    _view(P.out, (P.rows, P.n_out), (P.out_row_stride, 1), bf).copy_(r.float().to(bf))
+    return "final_layer"
+
+
+OUTER_SERVE = {"zigma_add_norm_fwd": _add_norm_fwd, "zigma_patch_embed_fwd": _patch_embed_fwd, "zigma_timestep_embed_fwd": _timestep_embed_fwd,
+               "zigma_skinny_linear_fwd": _skinny_linear_fwd, "zigma_final_layer_fwd": _final_layer_fwd}

@@ -104,7 +104,14 @@ __global__ __launch_bounds__(256) void add_norm_kernel(const zigma_norm_params_t
                 loadv<XT, VEC>(p.branch, r * p.branch_row_stride + c, br);
                 loadv<MT, VEC>(p.gate, b * p.mod_batch_stride + c, g);
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) x[i] = rnd<XT>(x[i] + g[i] * br[i]);
+                for (int i = 0; i < VEC; ++i) {
+                    float s = x[i] + g[i] * br[i];
+                    // fp16: keep the fp32 sum a value of its own.  hipcc otherwise folds product, sum and narrowing into one
+                    // v_fma_mixlo_f16, which rounds the exact sum ONCE to fp16; x' is the fp32 sum rounded to x's type, which is what
+                    // the unfused composition stores (they differ where the fp32 rounding lands on an fp16 tie: 12 of 1 M elements)
+                    if constexpr (XT::id == ZIGMA_F16) asm("" : "+v"(s));
+                    x[i] = rnd<XT>(s);
+                }
                 if (p.x_out) {
                     storev<XT, VEC>(p.x_out, r * p.x_out_row_stride + c, x);
                 }
