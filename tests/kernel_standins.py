@@ -244,7 +244,16 @@ def _softplus(x):
     return torch.nn.functional.softplus(x)          # beta 1, threshold 20: the reference's
 
 
-def _conv_xproj_fwd(P):
+def _front_kernel(fn_name, P, plan):
+    """the kernel the compiled front plan (csrc/front_plan.h) names for the call; refuses what it refuses"""
+    got = plan(P)
+    if got["status"] != 0:
+        raise RuntimeError(f"{fn_name}: refused (status {got['status']})")
+    return got["kernel"]
+
+
+def _conv_xproj_fwd(P, plan):
+    kernel = _front_kernel("zigma_conv_x_proj_fwd", P, plan)
     dt = _io_dtype(P.dtype)
     Bsz, L, dim, n = P.batch, P.seqlen, P.dim, P.n
     x = _view(P.x, (Bsz, L, dim), (P.x_batch_stride, P.x_l_stride, 1), dt).double()
@@ -258,32 +267,35 @@ def _conv_xproj_fwd(P):
     u = _view(P.u, (Bsz, L, dim), (P.u_batch_stride, P.u_l_stride, 1), dt)
     u.copy_((pre * torch.sigmoid(pre)).to(dt))
     _view(P.out, (Bsz * L, n), (P.out_row_stride, 1), dt).copy_((u.double().reshape(Bsz * L, dim) @ w.T).to(dt))
-    return "conv_x_proj_mfma"
+    return kernel
 
 
-def _x_proj_fwd(P):
+def _x_proj_fwd(P, plan):
+    kernel = _front_kernel("zigma_x_proj_fwd", P, plan)
     dt = _io_dtype(P.dtype)
     x, w = _view(P.x, (P.m, P.k), (P.x_row_stride, 1), dt), _view(P.w, (P.n, P.k), (P.w_row_stride, 1), dt)
     _view(P.out, (P.m, P.n), (P.out_row_stride, 1), dt).copy_((x.double() @ w.double().T).to(dt))
-    return "x_proj_splitk" if P.m < 16384 and P.k % 128 == 0 and P.k // 128 <= 12 else "x_proj_mfma"
+    return kernel
 
 
-def _dt_proj_fwd(P):
+def _dt_proj_fwd(P, plan):
+    kernel = _front_kernel("zigma_dt_proj_softplus_fwd", P, plan)
     dt = _io_dtype(P.dtype)
     x, w = _view(P.x, (P.m, P.k), (P.x_row_stride, 1), dt), _view(P.w, (P.n, P.k), (P.w_row_stride, 1), dt)
     pre = x.double() @ w.double().T
     if P.bias:
         pre = pre + _view(P.bias, (P.n,), (1,), torch.float32).double()
     _view(P.out, (P.m, P.n), (P.out_row_stride, 1), dt).copy_((_softplus(pre) if P.softplus else pre).to(dt))
-    return "dt_proj_softplus_mfma"
+    return kernel
 
 
-def install_lib_call(monkeypatch, plan=None):
-    """route _lib.call to the stand-ins above and below.  plan: plan_scan() compiled with g++ (the scan_plan fixture of tests/test_host_cpu.py):
-    names the scan's kernel, fills `info` and refuses what the library refuses (only the scan needs it)"""
+def install_lib_call(monkeypatch, plan=None, front_plan=None):
+    """route _lib.call to the stand-ins above and below.  plan / front_plan: plan_scan() and the plans of csrc/front_plan.h compiled with g++ (the
+    scan_plan and front_plan fixtures of tests/test_host_cpu.py): they name the kernel, fill the scan's `info` and refuse what the library refuses
+    (only the scan and the three front entry points need them)"""
     from zigma_amd import _lib
-    serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": _conv_xproj_fwd, "zigma_x_proj_fwd": _x_proj_fwd,
-             "zigma_dt_proj_softplus_fwd": _dt_proj_fwd, **OUTER_SERVE}
+    serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": lambda P: _conv_xproj_fwd(P, front_plan),
+             "zigma_x_proj_fwd": lambda P: _x_proj_fwd(P, front_plan), "zigma_dt_proj_softplus_fwd": lambda P: _dt_proj_fwd(P, front_plan), **OUTER_SERVE}
 
     def call(fn_name, params, device):
         LAST_KERNEL[0] = serve[fn_name](params)

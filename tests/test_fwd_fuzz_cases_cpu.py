@@ -4,7 +4,7 @@ agrees to < 1e-12 with an independent float64 restatement on exactly these input
 tests/kernel_standins.py), carries and checkpoints included.  Rounding model: the reference rounded to the I/O type needs < 1 x every limit,
 the fp32 numpy model <= 1/2 x every limit or the case carries the raised bound of fwd_fuzz_cases.RAISED.  Known answers are exact in float64
 and in a step-by-step fp32 recurrence.  And every function of tests/test_gpu_fwd_fuzz.py runs here against float64 stand-ins served at the C
-ABI, with plan_scan() compiled with g++ naming the kernel: the kernel each case expects is the one the plan picks.
+ABI, with plan_scan() and the front's plans compiled with g++ naming the kernel: the kernel each case expects is the one the plan picks.
 
 `python tests/test_fwd_fuzz_cases_cpu.py` prints the RAISED table (2 x d_model of the cases whose fp32 model needs more than half a limit)."""
 import os
@@ -278,13 +278,13 @@ def test_dtproj_reference_and_rounding_model(c):
 # ---------------------------------------------------------------------------------------------------
 # tests/test_gpu_fwd_fuzz.py on the CPU: float64 stand-ins at the C ABI, plan_scan() compiled with g++ names the kernel
 # ---------------------------------------------------------------------------------------------------
-from test_host_cpu import scan_plan  # noqa: E402,F401  (the module-scoped fixture)
+from test_host_cpu import front_plan, scan_plan  # noqa: E402,F401  (the module-scoped fixtures)
 
 
 @pytest.fixture
-def gpu_file(monkeypatch, scan_plan):  # noqa: F811
+def gpu_file(monkeypatch, scan_plan, front_plan):  # noqa: F811
     import test_gpu_fwd_fuzz as gf
-    ks.install_lib_call(monkeypatch, scan_plan)
+    ks.install_lib_call(monkeypatch, scan_plan, front_plan)
     monkeypatch.setattr(gf, "DEV", "cpu")
     return gf
 

@@ -620,13 +620,14 @@ def _compile_plan(driver):
         return ctypes.CDLL(so)
 
 
-def _plan_caller(L, params_type, names):
+def _plan_caller(L, params_type, names, fn="plan"):
     """plan(P) -> dict of the driver's integer fields and the kernel string"""
-    L.plan.argtypes = [ctypes.POINTER(params_type), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
+    entry = getattr(L, fn)
+    entry.argtypes = [ctypes.POINTER(params_type), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
 
     def plan(P):
         f, k = (ctypes.c_int * len(names))(), ctypes.c_char_p()
-        L.plan(ctypes.byref(P), f, ctypes.byref(k))
+        entry(ctypes.byref(P), f, ctypes.byref(k))
         return dict(zip(names, f), kernel=k.value.decode() if k.value else None)
     return plan
 
@@ -695,6 +696,12 @@ class _Dev:
         self._strides = tuple(math.prod(shape[i + 1:]) for i in range(len(shape)))
     stride, dim, data_ptr = (lambda self, i: self._strides[i]), (lambda self: len(self.shape)), (lambda self: self._ptr)
     numel, requires_grad = (lambda self: math.prod(self.shape)), False
+    is_contiguous = lambda self: self._strides == tuple(math.prod(self.shape[i + 1:]) for i in range(len(self.shape)))
+
+    def pitched(self, *strides):
+        """the same tensor with these strides (a view of a wider allocation)"""
+        self._strides = strides
+        return self
 
 
 def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
@@ -734,6 +741,172 @@ def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
                                     assert dt_in_scan_eligible(u, x_dbl, w, rp, None, dstate=N, z=z) == planned, (dt, B, L, Di, R, N, rp, off, pl)
                                     seen.add(planned)
     assert seen == {True, False}
+
+
+_FRONT_PLAN_DRIVER = r"""
+#include "front_plan.h"
+using namespace zigma;
+static int report(const FrontPlan &s, int *f, const char **kernel) {
+    f[0] = s.status; f[1] = s.gx; f[2] = s.gy; f[3] = s.gz; f[4] = s.block; f[5] = s.tok; f[6] = s.silu; f[7] = s.contig_l; f[8] = s.width;
+    f[9] = s.stages; f[10] = s.waves; f[11] = s.splitk;
+    *kernel = s.kernel;
+    return s.status;
+}
+// what the library reports for a call: the plan, or for a sliced batch the plan of the slice that runs last
+extern "C" int plan_conv(const zigma_conv_params_t *p, int *f, const char **kernel) {
+    const FrontPlan top = plan_conv1d(*p);
+    FrontPlan s = top;
+    for (int b0 = 0; top.slice && b0 < p->batch && (b0 == 0 || s.kernel); b0 += top.slice) s = plan_conv1d(conv_slice(*p, b0, top.slice));
+    return report(s, f, kernel);
+}
+extern "C" int plan_cx(const zigma_conv_xproj_params_t *p, int *f, const char **kernel) { return report(plan_conv_x_proj(*p), f, kernel); }
+extern "C" int plan_xp(const zigma_xproj_params_t *p, int *f, const char **kernel) { return report(plan_x_proj(*p), f, kernel); }
+extern "C" int plan_dt(const zigma_dtproj_params_t *p, int *f, const char **kernel) { return report(plan_dt_proj(*p), f, kernel); }
+"""
+_FRONT_FIELDS = ("status", "gx", "gy", "gz", "block", "tok", "silu", "contig_l", "width", "stages", "waves", "splitk")
+
+
+@pytest.fixture(scope="module")
+def front_plan():
+    """plan_conv1d() / plan_conv_x_proj() / plan_x_proj() / plan_dt_proj() of zigma_amd/csrc/front_plan.h compiled on their own with g++ (no HIP):
+    plan(params) -> status, grid, block, switches, kernel, by the type of the parameter block"""
+    from zigma_amd import _lib
+    L = _compile_plan(_FRONT_PLAN_DRIVER)
+    by_type = {t: _plan_caller(L, t, _FRONT_FIELDS, fn) for t, fn in ((_lib.ConvParams, "plan_conv"), (_lib.ConvXProjParams, "plan_cx"),
+                                                                      (_lib.XProjParams, "plan_xp"), (_lib.DtProjParams, "plan_dt"))}
+    return lambda P: by_type[type(P)](P)
+
+
+@pytest.mark.parametrize("name", sorted(__import__("front_plan_cases").CASES))
+def test_front_plan_case_table(name, front_plan):
+    """the four plans (compiled) on the parameter block the product's bindings build for every case of the table: status, last kernel"""
+    import front_plan_cases
+    got, _ = front_plan_cases.call(name, "cpu", lambda fn, P: front_plan(P))
+    assert (got["status"], got["kernel"]) == tuple(front_plan_cases.CASES[name][2])
+
+
+def test_front_plan_geometry(front_plan):
+    """grid, block and template switches of the serving leaves against the closed forms of the kernels' headers"""
+    import front_plan_cases
+
+    def geometry(name, *fields):
+        got, _ = front_plan_cases.call(name, "cpu", lambda fn, P: front_plan(P))
+        return tuple(got[f] for f in fields)
+    conv = ("gx", "gy", "gz", "block", "tok", "width", "silu", "contig_l")
+    assert geometry("conv_tok_L17_w3_silu", *conv) == (1, 2, 2, 64, 1, 3, 1, 0)
+    assert geometry("conv_tok_L1_w2_silu", *conv) == (1, 1, 2, 64, 1, 2, 1, 0) and geometry("conv_tok_L17_w4", *conv) == (1, 2, 2, 64, 1, 4, 0, 0)
+    assert geometry("conv_tok_sliced_65536_samples", *conv) == (1, 1, 1, 64, 1, 4, 1, 0)               # the last slice: one sample
+    assert geometry("conv_generic_channel_first", *conv) == (1, 1, 1, 256, 0, 0, 0, 1)                 # ceil(2 * 4 * 17 / 256) blocks
+    assert geometry("conv_generic_dim_6", *conv) == (1, 1, 1, 256, 0, 0, 0, 0)
+    cx = ("gx", "gy", "gz", "block", "stages", "waves")
+    assert [geometry(f"cx_served_flags_{f}", *cx) for f in ("0", "1", "2", "3_f16")] == [(2, 1, 1, 256, 2, 4), (2, 1, 1, 256, 3, 4), (1, 1, 1, 512, 2, 8),
+                                                                                       (1, 1, 1, 512, 3, 8)]
+    xp = ("gx", "gy", "gz", "block", "splitk")
+    assert geometry("xp_splitk", *xp) == (1, 1, 1, 512, 1) and geometry("xp_splitk_k_1536_f16_m_33", *xp) == (2, 1, 1, 512, 1)
+    assert geometry("xp_streaming_k_1792", *xp) == (1, 1, 1, 512, 0) and geometry("xp_streaming_16384_rows", *xp) == (64, 1, 1, 512, 0)
+    assert geometry("xp_splitk_16383_rows", *xp) == (512, 1, 1, 512, 1)
+    dt = ("gx", "gy", "gz", "block")
+    assert geometry("dt_served_1_row", *dt) == (1, 1, 1, 256) and geometry("dt_served_513_rows_f16", *dt) == (1, 2, 1, 256)
+
+
+_TORCH_ID = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _sweep_verdict(eligible, pl, kernels, policy, point, seen):
+    """one point of a predicate sweep: predicate true => the plan serves with one of `kernels`; predicate false where the plan serves => one of the
+    named `policy` clauses ({name: holds at this point}) explains it"""
+    served = pl["status"] == 0 and pl["kernel"] is not None
+    if eligible:
+        assert served and pl["kernel"] in kernels, (point, pl)
+    elif served:
+        why = [name for name, holds in policy.items() if holds]
+        assert why, ("the predicate refuses what the plan serves and no policy clause says why", point, pl)
+        seen.update(why)
+    seen.add(bool(eligible))
+
+
+def test_x_proj_eligible_agrees_with_the_plan(front_plan):
+    """x_proj_eligible() (Python) against plan_x_proj() (compiled) on the parameter block x_proj() builds: yes only where the plan serves, with the kernel
+    the token count implies; no where the plan serves only by one of its three policy clauses"""
+    from zigma_amd import _lib
+    from zigma_amd.selective_scan_interface import x_proj_eligible
+    seen = set()
+    for dt in (torch.bfloat16, torch.float16, torch.float32):
+        for tokens in (1, 255, 256, 16383, 16384):
+            for k in (64, 128, 256, 1280, 1536, 1792):
+                for n in (0, 8, 96, 97):
+                    for x_pitch in (k, k + 4, k + 8):
+                        for w_pitch in (k, k + 4, k + 8):
+                            for x_off, w_off in ((0, 0), (2, 0), (8, 0), (0, 2), (0, 8)):
+                                u = _Dev(dt, tokens, k, ptr=(1 << 30) + x_off * 2).pitched(x_pitch, 1)
+                                w = _Dev(dt, n, k, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                P = _lib.XProjParams()
+                                P.m, P.n, P.k, P.dtype = tokens, n, k, _TORCH_ID[dt]
+                                P.x_row_stride, P.w_row_stride, P.out_row_stride = u.stride(0), w.stride(0), n
+                                P.x, P.w, P.out = u.data_ptr(), w.data_ptr(), 1 << 40
+                                policy = {"tokens >= 256": tokens < 256, "tokens >= 16384 or k <= 1536": tokens < 16384 and k > 1536,
+                                          "u.is_contiguous()": x_pitch != k}
+                                kernels = ("x_proj_splitk",) if tokens < 16384 else ("x_proj_mfma",)
+                                _sweep_verdict(x_proj_eligible(u, w), front_plan(P), kernels, policy, (dt, tokens, k, n, x_pitch, w_pitch, x_off, w_off), seen)
+    assert seen == {True, False, "tokens >= 256", "tokens >= 16384 or k <= 1536", "u.is_contiguous()"}, seen
+
+
+def test_dt_proj_eligible_agrees_with_the_plan(front_plan):
+    """dt_proj_eligible() (Python) against plan_dt_proj() (compiled) on the parameter block dt_proj_softplus() builds: the predicate has no policy
+    clause, so it says yes exactly where the plan serves"""
+    from zigma_amd import _lib
+    from zigma_amd.selective_scan_interface import dt_proj_eligible
+    seen = set()
+    for dt in (torch.bfloat16, torch.float16, torch.float32):
+        for tokens in (1, 512, 513):
+            for R in (0, 4, 8, 40, 48, 56):
+                for Di in (64, 96, 1280):
+                    for width in (R + 32, R + 36, R + 40):
+                        for w_pitch in (R, R + 4, R + 8):
+                            for x_off, w_off in ((0, 0), (2, 0), (8, 0), (0, 2), (0, 8)):
+                                x_dbl = _Dev(dt, tokens, width, ptr=(1 << 30) + x_off * 2)
+                                w = _Dev(dt, Di, R, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                P = _lib.DtProjParams()
+                                P.m, P.n, P.k, P.dtype, P.softplus = tokens, Di, R, _TORCH_ID[dt], 1
+                                P.x_row_stride, P.w_row_stride, P.out_row_stride = x_dbl.stride(0), w.stride(0), Di
+                                P.x, P.w, P.out, P.bias = x_dbl.data_ptr(), w.data_ptr(), 1 << 40, 1 << 42
+                                _sweep_verdict(dt_proj_eligible(x_dbl, R, w), front_plan(P), ("dt_proj_softplus_mfma",), {},
+                                               (dt, tokens, R, Di, width, w_pitch, x_off, w_off), seen)
+    assert seen == {True, False}, seen
+
+
+def test_conv_x_proj_eligible_agrees_with_the_plan(front_plan):
+    """conv_x_proj_eligible() (Python) against plan_conv_x_proj() (compiled) on the parameter block conv_x_proj() builds (x_half the first half of an
+    in_proj output, fresh u and x_dbl, no reset_period: the entry point has none): yes only where the plan serves; no where the plan serves only by
+    CONV_X_PROJ_MIN_POSITIONS or because conv_w / conv_b / perm are not contiguous, which the parameter block cannot say"""
+    from zigma_amd import _lib
+    from zigma_amd.selective_scan_interface import CONV_X_PROJ_MIN_POSITIONS, conv_x_proj_eligible
+    seen = set()
+    offs = ((0, 0, 0, 0), (2, 0, 0, 0), (8, 0, 0, 0), (0, 2, 0, 0), (0, 8, 0, 0), (0, 0, 2, 0), (0, 0, 8, 0), (0, 0, 0, 2), (0, 0, 0, 8))
+    for dt in (torch.bfloat16, torch.float16, torch.float32):
+        for Bsz, L in ((1, 256), (1, 16384), (1, 16384 - 32), (64, 1024), (512, 32), (513, 32), (16, 1040), (16, 1048), (2, 8192 - 128)):
+            for Di in (64, 96, 1280):
+                for n in (0, 8, 12, 72, 96, 104):
+                    for x_pitch in (2 * Di, 2 * Di + 4, 2 * Di + 8):
+                        for w_pitch in (Di, Di + 4, Di + 8):
+                            for x_off, cw_off, cb_off, w_off in offs:
+                                for loose in ("", "conv_w", "conv_b", "perm") if (x_off, cw_off, cb_off, w_off) == (0, 0, 0, 0) else ("",):
+                                    x = _Dev(dt, Bsz, L, Di, ptr=(1 << 30) + x_off * 2).pitched(L * x_pitch, x_pitch, 1)
+                                    cw, cb = _Dev(dt, Di, 4, ptr=(1 << 34) + cw_off * 2), _Dev(dt, Di, ptr=(1 << 35) + cb_off * 2)
+                                    w = _Dev(dt, n, Di, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                    perm = _Dev(torch.int32, L, ptr=1 << 38)
+                                    if loose:
+                                        {"conv_w": cw, "conv_b": cb, "perm": perm}[loose].pitched(*((8, 1) if loose == "conv_w" else (2,)))
+                                    P = _lib.ConvXProjParams()
+                                    P.batch, P.seqlen, P.dim, P.n, P.dtype = Bsz, L, Di, n, _TORCH_ID[dt]
+                                    P.x_batch_stride, P.x_l_stride, P.u_batch_stride, P.u_l_stride = x.stride(0), x.stride(1), L * Di, Di
+                                    P.w_row_stride, P.out_row_stride = w.stride(0), n
+                                    P.x, P.conv_weight, P.conv_bias, P.w = x.data_ptr(), cw.data_ptr(), cb.data_ptr(), w.data_ptr()
+                                    P.u, P.out, P.x_row_index = 1 << 40, 1 << 41, perm.data_ptr()
+                                    policy = {"CONV_X_PROJ_MIN_POSITIONS": Bsz * L < CONV_X_PROJ_MIN_POSITIONS, "is_contiguous()": bool(loose)}
+                                    _sweep_verdict(conv_x_proj_eligible(x, cw, cb, w, perm), front_plan(P), ("conv_x_proj_mfma",), policy,
+                                                   (dt, Bsz, L, Di, n, x_pitch, w_pitch, x_off, cw_off, cb_off, w_off, loose), seen)
+    assert seen == {True, False, "CONV_X_PROJ_MIN_POSITIONS", "is_contiguous()"}, seen
 
 
 def test_inner_plan_rules(monkeypatch):

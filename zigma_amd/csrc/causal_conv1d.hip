@@ -10,6 +10,7 @@
 //  conv_generic_kernel — any strides (channel-first views of the reference, channel-last, ...): one
 //      output element per thread, threads run along the contiguous dimension.
 #include "conv_helpers.h"
+#include "front_plan.h"
 
 namespace zigma {
 
@@ -110,49 +111,33 @@ __global__ __launch_bounds__(256) void conv_generic_kernel(const zigma_conv_para
     st<IO>(p.out, b * p.out_batch_stride + c * p.out_c_stride + l * p.out_l_stride, acc);
 }
 
+// one planned call (a slice at most): the plan's kernel with its template switches
 template <typename IO, typename WT>
-static int launch_conv(const zigma_conv_params_t &p, hipStream_t stream) {
-    constexpr size_t es = sizeof(typename IO::raw);
-    if (p.batch > 65535) {              // batch rides in gridDim.z: larger batches (video: batch x tokens-per-frame rows) go in slices
-        for (int b0 = 0; b0 < p.batch; b0 += 65535) {
-            zigma_conv_params_t q = p;
-            q.batch = p.batch - b0 < 65535 ? p.batch - b0 : 65535;
-            q.x = reinterpret_cast<const char *>(p.x) + static_cast<int64_t>(b0) * p.x_batch_stride * es;
-            q.out = reinterpret_cast<char *>(p.out) + static_cast<int64_t>(b0) * p.out_batch_stride * es;
-            const int rc = launch_conv<IO, WT>(q, stream);
-            if (rc != ZIGMA_OK) return rc;
-        }
-        return ZIGMA_OK;
-    }
-    const bool tok = p.x_c_stride == 1 && p.out_c_stride == 1 && p.dim % 4 == 0 &&
-                     reinterpret_cast<uintptr_t>(p.x) % (4 * es) == 0 && reinterpret_cast<uintptr_t>(p.out) % (4 * es) == 0 &&
-                     p.x_l_stride % 4 == 0 && p.out_l_stride % 4 == 0 && p.x_batch_stride % 4 == 0 && p.out_batch_stride % 4 == 0 &&
-                     p.x_l_stride >= 0 && p.out_l_stride >= 0 &&
-                     (p.x_l_stride * p.seqlen + p.dim) * static_cast<int64_t>(es) < (int64_t(1) << 31) &&
-                     (p.out_l_stride * p.seqlen + p.dim) * static_cast<int64_t>(es) < (int64_t(1) << 31);
-    if (p.reset_period < 0 || p.reset_period % 16 != 0) return ZIGMA_ERR_SHAPE;
-    if (p.reset_period > 0 && !tok) return ZIGMA_ERR_STRIDE;   // only the token-major kernel restarts sequences
-    if (tok) {
-        constexpr int LT = 16;
-        dim3 grid((p.dim / 4 + 63) / 64, (p.seqlen + LT - 1) / LT, p.batch), block(64);
-#define ZIGMA_CONV_TOK(W_)                                                                                          \
-    if (p.silu_activation) hipLaunchKernelGGL((conv_tok_kernel<IO, WT, W_, LT, true>), grid, block, 0, stream, p);  \
-    else hipLaunchKernelGGL((conv_tok_kernel<IO, WT, W_, LT, false>), grid, block, 0, stream, p);
-        switch (p.width) {
+static int launch_conv(const zigma_conv_params_t &p, const FrontPlan &plan, hipStream_t stream) {
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), block(plan.block);
+    if (plan.tok) {
+#define ZIGMA_CONV_TOK(W_)                                                                                                   \
+    if (plan.silu) hipLaunchKernelGGL((conv_tok_kernel<IO, WT, W_, kConvTokLT, true>), grid, block, 0, stream, p);           \
+    else hipLaunchKernelGGL((conv_tok_kernel<IO, WT, W_, kConvTokLT, false>), grid, block, 0, stream, p);
+        switch (plan.width) {
             case 2: ZIGMA_CONV_TOK(2) break;
             case 3: ZIGMA_CONV_TOK(3) break;
             default: ZIGMA_CONV_TOK(4) break;
         }
 #undef ZIGMA_CONV_TOK
-        set_last_kernel("conv_tok");
-        return check_launch();
+    } else if (plan.contig_l) {
+        hipLaunchKernelGGL((conv_generic_kernel<IO, WT, true>), grid, block, 0, stream, p);
+    } else {
+        hipLaunchKernelGGL((conv_generic_kernel<IO, WT, false>), grid, block, 0, stream, p);
     }
-    const int64_t total = static_cast<int64_t>(p.batch) * p.dim * p.seqlen;
-    dim3 grid(static_cast<unsigned>((total + 255) / 256)), block(256);
-    if (p.x_l_stride == 1) hipLaunchKernelGGL((conv_generic_kernel<IO, WT, true>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((conv_generic_kernel<IO, WT, false>), grid, block, 0, stream, p);
-    set_last_kernel("conv_generic");
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+static int launch(const zigma_conv_params_t &p, const FrontPlan &plan, hipStream_t stream) {
+    ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, { ZIGMA_DISPATCH_DTYPE(p.w_dtype, WT, { return launch_conv<IO, WT>(p, plan, stream); }) })
+    return ZIGMA_ERR_DTYPE;
 }
 
 }  // namespace zigma
@@ -163,14 +148,13 @@ extern "C" int zigma_causal_conv1d_fwd(const zigma_conv_params_t *pp, void *stre
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();  // a stale error of an unrelated earlier call is not ours to report
     const zigma_conv_params_t &p = *pp;
-    if (p.width < 2 || p.width > 4) return ZIGMA_ERR_SHAPE;  // causal_conv1d.cpp:157
-    if (p.batch < 0 || p.dim < 0 || p.seqlen < 0) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.batch == 0 || p.dim == 0 || p.seqlen == 0) return ZIGMA_OK;  // empty (pointers may be NULL)
-    if (!p.x || !p.weight || !p.out) return ZIGMA_ERR_NULL;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, {
-        ZIGMA_DISPATCH_DTYPE(p.w_dtype, WT, { return launch_conv<IO, WT>(p, stream); })
-    })
-    return ZIGMA_ERR_DTYPE;
+    const FrontPlan plan = plan_conv1d(p);
+    if (!plan.slice) return plan.kernel ? launch(p, plan, stream) : plan.status;
+    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
+        const zigma_conv_params_t q = conv_slice(p, b0, plan.slice);
+        const int rc = launch(q, plan_conv1d(q), stream);
+        if (rc != ZIGMA_OK) return rc;
+    }
+    return ZIGMA_OK;
 }

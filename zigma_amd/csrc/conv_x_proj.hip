@@ -23,6 +23,7 @@
 // Measured at the headline shape (B=64, L=1024, d_inner=1280, n=72): 72 us against 131 us for conv_tok + x_proj_mfma
 // (tools/conv_xproj_ab.py); loads + MFMA alone 35 us, + conv 64 us, + stores 64 us (probe flags).
 // bf16 or fp16 (template parameter T: the dot products of the conv, the packs, the MFMA); width 4; bias required; seqlen % 32 == 0; d_inner % 64 == 0; n <= 96, n % 8 == 0.
+#include "front_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
@@ -33,7 +34,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
 typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
 
-constexpr int kCxTok = 32, kCxBK = 64, kCxHalo = 3;
+constexpr int kCxHalo = 3;                                         // kCxTok, kCxBK: front_plan.h
 constexpr int kCxXBytes = 40 * 128;                                  // per wave and stage: 35 rows used, 5 load instructions
 // stage layout for NW waves: [NW x input rows][W_x slab: 96 rows x 128 B][conv taps (64 ch x 8 B) + bias (64 x 2 B), 1 KB]
 constexpr int cx_w_off(int nw) { return nw * kCxXBytes; }
@@ -279,33 +280,17 @@ extern "C" int zigma_conv_x_proj_fwd(const zigma_conv_xproj_params_t *pp, void *
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_conv_xproj_params_t &p = *pp;
-    if (p.batch < 0 || p.seqlen < 0 || p.dim < 1 || p.n < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags & ~15) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
-    if (!p.x || !p.conv_weight || !p.conv_bias || !p.w || !p.u || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.n > 96 || p.n % 8 != 0 || p.dim % kCxBK != 0 || p.seqlen % kCxTok != 0) return ZIGMA_ERR_SHAPE;
-    if (p.out_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0) return ZIGMA_ERR_STRIDE;
-    const int64_t m = static_cast<int64_t>(p.batch) * p.seqlen;
-    if (m % (kCxTok * 8) != 0) return ZIGMA_ERR_SHAPE;       // (either workgroup size)
-    auto al16 = [](const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
-    if (p.x_l_stride % 8 != 0 || p.x_batch_stride % 8 != 0 || p.u_l_stride % 8 != 0 || p.u_batch_stride % 8 != 0 || p.w_row_stride % 8 != 0 ||
-        !al16(p.x) || !al16(p.u) || !al16(p.w) || !al16(p.conv_weight) || !al16(p.conv_bias))
-        return ZIGMA_ERR_STRIDE;
+    const FrontPlan plan = plan_conv_x_proj(p);
+    if (!plan.kernel) return plan.status;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // default: 4-wave workgroups (128 positions), two stages = 66 KB of LDS: two workgroups per CU that drift apart, one computing
-    // while the other waits for its loads (measured 72 us; 8 waves in lockstep 75 us; a third stage does not pay, the second
-    // workgroup does its job).  flags: 1 = three stages, 2 = eight-wave workgroups; probes (wrong results): 4 = no u stores,
-    // 8 = no conv arithmetic.
+    const dim3 grid(plan.gx), block(plan.block);
 #define ZIGMA_CX(S_, W_) ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((conv_x_proj_kernel<S_, W_, T>), grid, block, 0, stream, p))
-    if (p.flags & 2) {
-        const dim3 grid(static_cast<unsigned>(m / (kCxTok * 8))), block(64 * 8);
-        if (p.flags & 1) { ZIGMA_CX(3, 8) } else { ZIGMA_CX(2, 8) }
+    if (plan.waves == 8) {
+        if (plan.stages == 3) { ZIGMA_CX(3, 8) } else { ZIGMA_CX(2, 8) }
     } else {
-        const dim3 grid(static_cast<unsigned>(m / (kCxTok * 4))), block(64 * 4);
-        if (p.flags & 1) { ZIGMA_CX(3, 4) } else { ZIGMA_CX(2, 4) }
+        if (plan.stages == 3) { ZIGMA_CX(3, 4) } else { ZIGMA_CX(2, 4) }
     }
 #undef ZIGMA_CX
-    set_last_kernel("conv_x_proj_mfma");
+    set_last_kernel(plan.kernel);
     return check_launch();
 }

@@ -14,17 +14,12 @@
 // then transposed through a wave-private LDS tile and leaves as 16-byte stores (8 tokens x 128 B per instruction: 16 four-byte
 // stores per lane made the store instruction rate the limit, 62-66 -> 59-60 us).  A / B fragments are 16-byte loads straight from global
 // (x_dbl is 9 MB, the weight 100 KB: L2 resident), no LDS.
+#include "front_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kDtTokPerWave = 32, kDtChPerBlock = 64, kDtWaves = 4;
-#ifndef ZIGMA_DT_ITERS
-#define ZIGMA_DT_ITERS 4
-#endif
-constexpr int kDtIters = ZIGMA_DT_ITERS;
 
 template <typename T>
 __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(const zigma_dtproj_params_t p) {
@@ -128,20 +123,10 @@ extern "C" int zigma_dt_proj_softplus_fwd(const zigma_dtproj_params_t *pp, void 
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_dtproj_params_t &p = *pp;
-    if (p.m < 0 || p.n < 0 || p.k < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags & ~1) return ZIGMA_ERR_UNSUPPORTED;         // 1: four-byte stores as the accumulators lie (A/B probe)
-    if (p.m == 0 || p.n == 0) return ZIGMA_OK;
-    if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.k > 48 || p.k % 8 != 0 || p.n % kDtChPerBlock != 0) return ZIGMA_ERR_SHAPE;
-    // 16-byte fragment loads, 4-byte packed stores
-    if (p.x_row_stride % 8 != 0 || p.w_row_stride % 8 != 0 || p.out_row_stride % 2 != 0 ||
-        reinterpret_cast<uintptr_t>(p.x) % 16 != 0 || reinterpret_cast<uintptr_t>(p.w) % 16 != 0 ||
-        reinterpret_cast<uintptr_t>(p.out) % 4 != 0)
-        return ZIGMA_ERR_STRIDE;
-    const int64_t tok_per_block = kDtTokPerWave * kDtWaves * kDtIters;
-    dim3 grid(p.n / kDtChPerBlock, static_cast<unsigned>((p.m + tok_per_block - 1) / tok_per_block)), block(64 * kDtWaves);
+    const FrontPlan plan = plan_dt_proj(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx, plan.gy), block(plan.block);
     ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(dt_proj_softplus_kernel<T>, grid, block, 0, static_cast<hipStream_t>(stream_), p))
-    set_last_kernel("dt_proj_softplus_mfma");
+    set_last_kernel(plan.kernel);
     return check_launch();
 }

@@ -9,6 +9,7 @@
 //   (v_mfma_f32_32x32x16_bf16: lane -> token row, 8 consecutive channels; 4 k-steps deep in flight) and keeps the
 //   32 x 96 accumulator in registers; output rows leave as bf16.
 // bf16 or fp16 (template parameter T: the MFMA and the output rounding); n <= 96; k % 256 == 0; rows 16-byte aligned.
+#include "front_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
@@ -16,7 +17,6 @@ namespace zigma {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kXpWaves = 8, kXpTok = 32, kXpChunk = 256, kXpRows = 96, kXpDepth = 4;
 constexpr int kXpPitch = kXpChunk * 2 + 16;          // bytes per staged weight row (16 B skew)
 
 template <typename T>
@@ -80,8 +80,6 @@ __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj
 // workgroup of 32 tokens — m / 32 workgroups, each wave k / 8 columns (12 k-steps at k = 1536) — with BOTH operands straight from memory
 // as MFMA fragments (W_x is 245 KB: L2-resident, every workgroup reads all of it once), all of a wave's token fragments in flight at once;
 // the eight partial 32 x 96 tiles are added through LDS in wave order (a fixed summation order: results do not depend on timing).
-constexpr int kXsWaves = 8, kXsMaxSteps = 12;
-
 template <typename T>
 __global__ __launch_bounds__(64 * kXsWaves) void x_proj_splitk_kernel(const zigma_xproj_params_t p) {
     __shared__ __attribute__((aligned(16))) float s_part[kXsWaves][3][16][64];     // 96 KB: [wave][feature block][accumulator register][lane]
@@ -153,25 +151,15 @@ extern "C" int zigma_x_proj_fwd(const zigma_xproj_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_xproj_params_t &p = *pp;
-    if (p.m < 0 || p.n < 1 || p.k < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.m == 0) return ZIGMA_OK;
-    if (!p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.n > kXpRows || p.k % kXpChunk != 0 || p.k / 16 < kXpDepth) return ZIGMA_ERR_SHAPE;
-    if (p.x_row_stride % 8 != 0 || p.w_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.x) % 16 != 0 ||
-        reinterpret_cast<uintptr_t>(p.w) % 16 != 0)
-        return ZIGMA_ERR_STRIDE;
-    // few tokens: K split over the waves of 32-token workgroups (the streaming form would leave most CUs idle)
-    if (p.m < 16384 && p.k % (16 * kXsWaves) == 0 && p.k / (16 * kXsWaves) <= kXsMaxSteps) {
-        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_splitk_kernel<T>, dim3(static_cast<unsigned>((p.m + kXpTok - 1) / kXpTok)), dim3(64 * kXsWaves), 0,
-                                                          static_cast<hipStream_t>(stream_), p))
-        set_last_kernel("x_proj_splitk");
-        return check_launch();
+    const FrontPlan plan = plan_x_proj(p);
+    if (!plan.kernel) return plan.status;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const dim3 grid(plan.gx), block(plan.block);
+    if (plan.splitk) {
+        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_splitk_kernel<T>, grid, block, 0, stream, p))
+    } else {
+        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_kernel<T>, grid, block, 0, stream, p))
     }
-    const int64_t tok_per_wg = kXpTok * kXpWaves;
-    ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(x_proj_kernel<T>, dim3(static_cast<unsigned>((p.m + tok_per_wg - 1) / tok_per_wg)), dim3(64 * kXpWaves), 0,
-                                                      static_cast<hipStream_t>(stream_), p))
-    set_last_kernel("x_proj_mfma");
+    set_last_kernel(plan.kernel);
     return check_launch();
 }

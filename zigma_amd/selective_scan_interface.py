@@ -206,13 +206,16 @@ def scan_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
 
 
 def x_proj_eligible(u, weight):
-    """limits of zigma_x_proj_fwd: bf16 or fp16 (u and weight alike), n <= 96, k % 256 == 0, 16-byte aligned contiguous rows.  From 16 384 tokens on a workgroup streams
-    256 token rows over the whole K; below, K is split over the waves of 32-token workgroups (x_proj_splitk_kernel, round 5: the streaming
-    form was 32 workgroups and 31 us at 8192 tokens against 21 for the library), which needs k <= 1536."""
+    """limits of zigma_x_proj_fwd, restating plan_x_proj() (csrc/front_plan.h): bf16 or fp16 (u and weight alike), n <= 96, k % 256 == 0, rows a multiple of
+    8 elements apart on 16-byte boundaries.  From 16 384 tokens on a workgroup streams 256 token rows over the whole K; below, K is split over the waves of
+    32-token workgroups (x_proj_splitk_kernel, round 5: the streaming form was 32 workgroups and 31 us at 8192 tokens against 21 for the library),
+    which needs k <= 1536.  tests/test_host_cpu.py sweeps the predicate against the compiled plan."""
     tokens = u.numel() // u.shape[-1]
-    return (u.is_cuda and u.dtype in (torch.bfloat16, torch.float16) and weight.dtype == u.dtype and u.is_contiguous()
-            and (tokens >= 16384 or (tokens >= 256 and weight.shape[1] <= 1536))
-            and weight.shape[0] <= 96 and weight.shape[1] % 256 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
+    return (u.is_cuda and u.dtype in (torch.bfloat16, torch.float16) and weight.dtype == u.dtype
+            and u.is_contiguous()                                                   # policy: the plan takes any row pitch % 8 == 0
+            and (tokens >= 16384 or (tokens >= 256                                  # policy: below 256 tokens the library GEMM is kept
+                                     and weight.shape[1] <= 1536))                  # policy: few tokens only on the split-K form, never the streaming one
+            and 1 <= weight.shape[0] <= 96 and weight.shape[1] % 256 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
             and u.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
 
 
@@ -232,16 +235,19 @@ def x_proj(u, weight):
 
 
 def conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_weight, perm, reset_period=0):
-    """limits of zigma_conv_x_proj_fwd: bf16 or fp16 (all four operands alike), width-4 taps as contiguous (d_inner, 4), a bias, seqlen % 32 == 0,
-    batch * seqlen % 256 == 0 and >= 16384 positions (a workgroup walks 256 positions over the whole d_inner: fewer than ~64
-    workgroups leave the chip idle), d_inner % 64 == 0, n <= 96, 16-byte aligned rows, one sequence per batch row."""
+    """limits of zigma_conv_x_proj_fwd, restating plan_conv_x_proj() (csrc/front_plan.h): bf16 or fp16 (all four operands alike), width-4 taps as
+    contiguous (d_inner, 4), a bias, seqlen % 32 == 0, batch * seqlen % 256 == 0, d_inner % 64 == 0, n <= 96 and % 8 == 0, rows a multiple of 8 elements
+    apart on 16-byte boundaries, one sequence per batch row (the entry point has no reset_period).  tests/test_host_cpu.py sweeps the predicate
+    against the compiled plan."""
     if conv_b is None or reset_period or not x_half.is_cuda:
         return False
     Bsz, L, Di = x_half.shape
     return (x_half.dtype in (torch.bfloat16, torch.float16) and conv_w.dtype == x_half.dtype and conv_b.dtype == x_half.dtype
-            and x_proj_weight.dtype == x_half.dtype and conv_w.shape == (Di, 4) and conv_w.is_contiguous() and conv_b.is_contiguous()
-            and L % 32 == 0 and (Bsz * L) % 256 == 0 and Bsz * L >= CONV_X_PROJ_MIN_POSITIONS and Di % 64 == 0
-            and x_proj_weight.shape[0] <= 96 and x_proj_weight.shape[0] % 8 == 0
+            and x_proj_weight.dtype == x_half.dtype and conv_w.shape == (Di, 4)
+            and conv_w.is_contiguous() and conv_b.is_contiguous()                   # (the parameter block carries no pitch for them)
+            and L % 32 == 0 and (Bsz * L) % 256 == 0 and Di % 64 == 0
+            and Bsz * L >= CONV_X_PROJ_MIN_POSITIONS                                # policy: fewer than ~64 workgroups of 256 positions leave the chip idle
+            and 1 <= x_proj_weight.shape[0] <= 96 and x_proj_weight.shape[0] % 8 == 0
             and x_half.stride(2) == 1 and x_half.stride(1) % 8 == 0 and x_half.stride(0) % 8 == 0
             and x_proj_weight.stride(1) == 1 and x_proj_weight.stride(0) % 8 == 0
             and all(t.data_ptr() % 16 == 0 for t in (x_half, conv_w, conv_b, x_proj_weight))
@@ -291,8 +297,10 @@ def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z
 
 
 def dt_proj_eligible(x_dbl, dt_rank, weight):
-    """bf16 or fp16 (x_dbl and weight alike) token-major x_dbl rows / weight rows on 16-byte boundaries, d_inner a multiple of 64, dt_rank <= 48, % 8 == 0."""
-    return (x_dbl.is_cuda and x_dbl.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x_dbl.dtype and dt_rank <= 48
+    """limits of zigma_dt_proj_softplus_fwd, restating plan_dt_proj() (csrc/front_plan.h): bf16 or fp16 (x_dbl and weight alike) token-major x_dbl rows /
+    weight rows a multiple of 8 elements apart on 16-byte boundaries, d_inner a multiple of 64, 8 <= dt_rank <= 48, % 8 == 0.  No policy on top of the
+    limits.  tests/test_host_cpu.py sweeps the predicate against the compiled plan."""
+    return (x_dbl.is_cuda and x_dbl.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x_dbl.dtype and 8 <= dt_rank <= 48
             and dt_rank % 8 == 0
             and weight.shape[0] % 64 == 0 and x_dbl.stride(-1) == 1 and weight.stride(1) == 1
             and x_dbl.stride(-2) % 8 == 0 and weight.stride(0) % 8 == 0
