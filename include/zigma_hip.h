@@ -38,7 +38,8 @@ extern "C" {
                                * 9: zigma_scan_params_t grew: dt_x / dt_w (dt_proj + softplus inside the scan kernel)
                                * 10: zigma_calib_launch (bench.py's box calibration) added; new ZIGMA_LINEAR_* kernel selectors of round 6
                                * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added
-                               * (10, no block changed): zigma_linear_f32_split added */
+                               * (10, no block changed): zigma_linear_f32_split added
+                               * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -529,6 +530,33 @@ typedef struct zigma_linear_params {
 } zigma_linear_params_t;
 
 int zigma_linear_fwd(const zigma_linear_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * LayerNorm (no affine weight) + adaLN modulate + dense projection in one pass over x:
+ *   y[r, :]   = r16((x[r, :] - mean_r) * rstd_r)                                   (statistics in fp32, two-pass variance over k)
+ *   xa[r, :]  = r16(y[r, :] * (1 + scale[b, :]) + shift[b, :]),  b = r / rows_per_batch       (r16: rounded to the I/O type)
+ *   out[r, :] = xa[r, :] @ w^T                                                     (fp32 accumulation, rounded once)
+ * Replaces the pre-attention `modulate(norm_msa(h), shift_mca, scale_mca)` of the reference's Block (model_zigma.py:441-446) together with
+ * CrossAttention.to_q (model_zigma.py:104-128): the arithmetic and the two rounding points of zigma_add_norm_fwd (y_mod) followed by zigma_linear_fwd, but xa
+ * is formed in registers as the MFMA operand and never reaches memory.  x: (m, k) rows; w: (n, k) rows; shift / scale: (m / rows_per_batch, k)
+ * rows of pitch mod_batch_stride (column slices of a wider tensor pass as they are); out: (m, n) rows of pitch out_row_stride.  The batch index
+ * is per row: tiles that straddle a sample boundary are served.  bf16 or fp16 throughout (one dtype).
+ * Limits, else ZIGMA_ERR_SHAPE: n = 512, k = 512 / 640 / 768, m % 128 == 0; 16-byte aligned rows of x, w, shift, scale and out, else ZIGMA_ERR_STRIDE.
+ * Every refusal and the launch geometry: plan_norm_linear(), csrc/norm_linear_plan.h.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_norm_linear_params {
+    int64_t m;
+    int32_t n, k;
+    int32_t dtype;           /* ZIGMA_BF16 or ZIGMA_F16 */
+    int32_t flags;           /* 0 */
+    int32_t rows_per_batch;
+    float eps;
+    int64_t x_row_stride, w_row_stride, out_row_stride, mod_batch_stride;
+    const void *x, *w, *shift, *scale;
+    void *out;
+} zigma_norm_linear_params_t;
+
+int zigma_norm_linear_fwd(const zigma_norm_linear_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Weight gradient of a dense projection:  out[n][k] = sum_m dy[m][n] * x[m][k]  (dW = dY^T X), bf16 or fp16 in / fp32 accumulate.

@@ -33,6 +33,8 @@ from .attention import attention_math, cross_attn, cross_attn_bwd_eligible, cros
 from . import embed as _embed
 from .layernorm import RMSNorm, block_norm, glue_bwd_eligible, layer_norm_fn, rms_norm_fn, scale_reduce_bwd
 from .linear import plan, project, run
+from .norm_linear import norm_linear, norm_linear_eligible
+from . import routing
 from .mamba_simple import Mamba
 from .scan_paths import hilbert_path, reverse_permut_np, zigzag_path
 
@@ -132,14 +134,17 @@ class CrossAttention(nn.Module):
             return y if residual is None else torch.addcmul(residual, gate.unsqueeze(1), y)
         return project("to_out", o, lin.weight, lin.bias, residual=residual, gate=gate)
 
-    def forward(self, x, text, mask=None, kv=None, residual=None, gate=None):
+    def forward(self, x, text, mask=None, kv=None, residual=None, gate=None, q=None):
         """kv: optional precomputed (to_k(text), to_v(text)), each (B, n_ctx, inner) — ZigMa.forward batches these
         projections of all layers into one GEMM since `text` is the same for every block.
-        residual (B, L, E), gate (B, E): return residual + gate * attention(x) instead of attention(x)."""
-        Bsz, L, _ = x.shape
+        residual (B, L, E), gate (B, E): return residual + gate * attention(x) instead of attention(x).
+        q: optional precomputed to_q(x) (B, L, inner) — the block forms it together with the LayerNorm + modulate that produce x (fuse_norm_to_q); x is
+        then not read and may be None."""
+        Bsz, L, _ = x.shape if q is None else q.shape
         H = self.heads
         k, v = kv[:2] if kv is not None else (self.to_k(text), self.to_v(text))
-        q = project("to_q", x, self.to_q.weight, self.to_q.bias)
+        if q is None:
+            q = project("to_q", x, self.to_q.weight, self.to_q.bias)
         needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
         if cross_attn_eligible(q, k, v, H) and (not needs_grad or cross_attn_bwd_eligible(q, k, v, H)):
             # HIP kernel: attention core in one pass (K/V of the head in LDS); under autograd its differentiable form (backward =
@@ -286,8 +291,28 @@ def _text_linear(x, weight, bias=None):
 # the HBM-bound norm kernels into the projection epilogues, the forward is 0.1-0.3 % faster.
 FUSE_OUT_PROJ_ADD = True       # (module-level knob for tests / tools; no environment switch)
 FUSE_OUT_PROJ_ADD_NO_TEXT = True     # the same for blocks without the attention branch (tools/outproj_notext_ab.py: 14.82 -> 14.78 ms on config 3's model)
+# The pre-attention LayerNorm + modulate inside the to_q projection (zigma_norm_linear_fwd, csrc/norm_linear.hip) instead of the norm kernel writing xa and
+# to_q reading it back: one launch and 168 MB per block less at 65 536 tokens (tools/norm_to_q_ab.py).
+FUSE_NORM_TO_Q = True
+NORM_TO_Q_MIN_TOKENS = 65536          # 512 tiles of 128 rows = two workgroups per CU; below, the pair stays (whether the kernel pays there is a later routing question: tools/norm_to_q_ab.py --batch 32 / 16)
 from . import _knobs  # noqa: E402
 _knobs.apply(globals(), "model_zigma")      # ZIGMA_KNOBS="model_zigma.FUSE_OUT_PROJ_ADD=False,..." (A/B tools)
+
+
+def fuse_norm_to_q(pend, to_q, shift, scale):
+    """the block's decision to form q = to_q(modulate(norm_msa(h))) in ONE kernel: the pending input carries no branch (out_proj made the gated add, so the
+    LayerNorm call would only read h and write xa), the routing table serves to_q at this shape with an own kernel (routing.POLICY = "off" therefore switches
+    this off too), at least NORM_TO_Q_MIN_TOKENS tokens, tensors the kernel takes (norm_linear_eligible: 16-bit, no bias, no autograd)."""
+    if not FUSE_NORM_TO_Q or pend.branch is not None:
+        return False
+    x = pend.base
+    if x.dim() != 3:
+        return False
+    tokens = x.shape[0] * x.shape[1]
+    n, k = to_q.weight.shape
+    if tokens < NORM_TO_Q_MIN_TOKENS or routing.route("to_q", tokens, n, k).kernel == "library":
+        return False
+    return norm_linear_eligible(x, to_q.weight, shift, scale, to_q.bias)
 
 
 class Block(nn.Module):
@@ -330,6 +355,10 @@ class Block(nn.Module):
         pend = Pending(y) if fused else Pending(n, y, g)
         if not self.has_text:
             return pend, residual
+        if fuse_norm_to_q(pend, self.msa.to_q, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E]):
+            # xa = modulate(norm_msa(h)) never leaves the registers of the to_q kernel; h itself is the residual of to_out's epilogue
+            q = norm_linear(pend.base, self.msa.to_q.weight, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E], self.norm_msa.eps)
+            return Pending(self.msa(None, text=text, mask=None, kv=kv, residual=pend.base, gate=mod[:, 5 * E:6 * E], q=q)), residual
         h, _, _, xa = block_norm(pend.base, None, None, None, self.norm_msa.eps, False, residual_in_fp32=False, branch=pend.branch,
                                  gate=pend.gate, shift=mod[:, 3 * E:4 * E], scale=mod[:, 4 * E:5 * E], want_x=True, want_y=False, want_res_out=False)
         # h + gate_msa * attention(xa): the add rides in to_out's epilogue (one read of att less for the next block's add + norm)
