@@ -523,7 +523,8 @@ typedef struct zigma_linear_params {
     /* optional gated residual in the epilogue (ABI 4) — CrossAttention's `hidden + gate_msa * to_out(...)` (model_zigma.py:447-449):
      *   out[m, :] = residual[m, :] + gate[m / rows_per_batch, :] * r16(x @ w^T + bias)[m, :]     (r16: rounded to the operand dtype)
      * residual: (m, n) rows of pitch res_row_stride; gate: (m / rows_per_batch, n) rows of pitch gate_batch_stride, both in the operand dtype;
-     * rows_per_batch % 256 == 0.  residual == NULL: plain projection. */
+     * rows_per_batch % 256 == 0.  residual == NULL: plain projection.  The sum is ONE fp32 fma rounded to the operand dtype, r16(fl32(fma(gate, r16(.), residual))),
+     * in both dtypes (the 4-wave kernel forms residual + gate * (x @ w^T + bias) from its fp32 accumulator without the inner rounding). */
     const void *residual, *gate;
     int64_t res_row_stride, gate_batch_stride;
     int32_t rows_per_batch, pad2_;

@@ -289,13 +289,15 @@ def _dt_proj_fwd(P, plan):
     return kernel
 
 
-def install_lib_call(monkeypatch, plan=None, front_plan=None):
-    """route _lib.call to the stand-ins above and below.  plan / front_plan: plan_scan() and the plans of csrc/front_plan.h compiled with g++ (the
-    scan_plan and front_plan fixtures of tests/test_host_cpu.py): they name the kernel, fill the scan's `info` and refuse what the library refuses
-    (only the scan and the three front entry points need them)"""
+def install_lib_call(monkeypatch, plan=None, front_plan=None, linear_plan=None, norm_linear_plan=None):
+    """route _lib.call to the stand-ins above and below.  plan / front_plan / linear_plan / norm_linear_plan: plan_scan(), the plans of
+    csrc/front_plan.h, plan_linear() and plan_norm_linear() compiled with g++ (the fixtures of tests/test_host_cpu.py and
+    tests/test_linear_cases_cpu.py): they name the kernel, fill the scan's `info` and refuse what the library refuses (only the scan, the three
+    front entry points and the two dense projections need them)"""
     from zigma_amd import _lib
     serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": lambda P: _conv_xproj_fwd(P, front_plan),
-             "zigma_x_proj_fwd": lambda P: _x_proj_fwd(P, front_plan), "zigma_dt_proj_softplus_fwd": lambda P: _dt_proj_fwd(P, front_plan), **OUTER_SERVE}
+             "zigma_x_proj_fwd": lambda P: _x_proj_fwd(P, front_plan), "zigma_dt_proj_softplus_fwd": lambda P: _dt_proj_fwd(P, front_plan),
+             "zigma_linear_fwd": lambda P: _linear_fwd(P, linear_plan), "zigma_norm_linear_fwd": lambda P: _norm_linear_fwd(P, norm_linear_plan), **OUTER_SERVE}
 
     def call(fn_name, params, device):
         LAST_KERNEL[0] = serve[fn_name](params)
@@ -494,3 +496,61 @@ def _final_layer_fwd(P):
 
 OUTER_SERVE = {"zigma_add_norm_fwd": _add_norm_fwd, "zigma_patch_embed_fwd": _patch_embed_fwd, "zigma_timestep_embed_fwd": _timestep_embed_fwd,
                "zigma_skinny_linear_fwd": _skinny_linear_fwd, "zigma_final_layer_fwd": _final_layer_fwd}
+
+
+# ---------------------------------------------------------------------------------------------------
+# Stand-ins AT THE C ABI for the dense projections, zigma_linear_fwd and zigma_norm_linear_fwd (tests/test_gpu_linear_sweep.py on the CPU).  The
+# torch_* functions are float64 torch restatements (F.linear, F.silu, F.layer_norm, torch.addcmul), UNROUNDED except at the 16-bit intermediates the
+# ABI defines; the CPU test holds the numpy references of tests/linear_cases.py against them, and the GPU test forms them on the device, in row
+# chunks, where a case is too large for the host.  The _*_fwd functions read and write through the parameter block; the compiled plan refuses
+# what the library refuses, names the kernel and tells the family (the 4-wave kernel's gated epilogue does not round in the middle).
+# ---------------------------------------------------------------------------------------------------
+LIN_4W = 2              # enum LinearFamily
+
+
+def torch_linear(x, w, bias, silu_from_col, res, gate_rows, dt, round_mid):
+    """float64 operands (gate_rows already expanded over the rows) -> (out, (residual, gate * v) | None)"""
+    v = F.linear(x, w, bias)
+    if silu_from_col < w.shape[0]:
+        v = torch.cat([v[:, :silu_from_col], F.silu(v[:, silu_from_col:])], 1)
+    if res is None:
+        return v, None
+    return torch.addcmul(res, gate_rows, _r(v, dt) if round_mid else v), (res, gate_rows * v)
+
+
+def torch_norm_linear(x, w, shift_rows, scale_rows, eps, dt):
+    """-> dict(y_mod: the unrounded second stage on the rounded LayerNorm, xa, out, terms of y_mod)"""
+    a = _r(F.layer_norm(x, (x.shape[-1],), eps=eps), dt) * (1.0 + scale_rows)
+    xa = _r(a + shift_rows, dt)
+    return dict(y_mod=a + shift_rows, xa=xa, out=F.linear(xa, w), terms=(a, shift_rows))
+
+
+def _planned(fn_name, P, plan):
+    got = plan(P)
+    if got["status"] != 0:
+        raise RuntimeError(f"{fn_name}: refused (status {got['status']})")
+    return got
+
+
+def _linear_fwd(P, plan):
+    got = _planned("zigma_linear_fwd", P, plan)
+    dt, m, n, k = _io_dtype(P.dtype), P.m, P.n, P.k
+    d = lambda t: None if t is None else t.double()
+    x, w = _view(P.x, (m, k), (P.x_row_stride, 1), dt), _view(P.w, (n, k), (P.w_row_stride, 1), dt)
+    res, gate = _view(P.residual, (m, n), (P.res_row_stride, 1), dt), None
+    if res is not None:
+        gate = _view(P.gate, (m // P.rows_per_batch, n), (P.gate_batch_stride, 1), dt).double().repeat_interleave(P.rows_per_batch, 0)
+    out, _ = torch_linear(d(x), d(w), d(_view(P.bias, (n,), (1,), dt)), P.silu_from_col, d(res), gate, dt, got["family"] != LIN_4W)
+    _view(P.out, (m, n), (P.out_row_stride, 1), dt).copy_(out.float().to(dt))
+    return got["kernel"]
+
+
+def _norm_linear_fwd(P, plan):
+    got = _planned("zigma_norm_linear_fwd", P, plan)
+    dt, m, n, k = _io_dtype(P.dtype), P.m, P.n, P.k
+    x, w = _view(P.x, (m, k), (P.x_row_stride, 1), dt), _view(P.w, (n, k), (P.w_row_stride, 1), dt)
+    nb = m // P.rows_per_batch
+    mod = lambda ptr: _view(ptr, (nb, k), (P.mod_batch_stride, 1), dt).double().repeat_interleave(P.rows_per_batch, 0)
+    r = torch_norm_linear(x.double(), w.double(), mod(P.shift), mod(P.scale), float(P.eps), dt)
+    _view(P.out, (m, n), (P.out_row_stride, 1), dt).copy_(r["out"].float().to(dt))
+    return got["kernel"]

@@ -115,8 +115,12 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = __builtin_fmaf(lo16<T>(gq[e]), lo16<T>(row[i][e]), lo16<T>(res[i][e]));
-                    const float hi = __builtin_fmaf(hi16<T>(gq[e]), hi16<T>(row[i][e]), hi16<T>(res[i][e]));
+                    float lo = __builtin_fmaf(lo16<T>(gq[e]), lo16<T>(row[i][e]), lo16<T>(res[i][e]));
+                    float hi = __builtin_fmaf(hi16<T>(gq[e]), hi16<T>(row[i][e]), hi16<T>(res[i][e]));
+                    // fp16: keep the fp32 fma a value of its own.  hipcc otherwise folds it and the narrowing into one v_fma_mixlo_f16 / mixhi, which
+                    // rounds the EXACT sum once to fp16; out is the fp32 result rounded to the I/O type, as in add_norm's x + gate * branch and as
+                    // the unfused composition stores it (they differ where the fp32 rounding lands on an fp16 tie: up to 7e-5 of the elements)
+                    if constexpr (T::id == ZIGMA_F16) asm("" : "+v"(lo), "+v"(hi));
                     row[i][e] = pack2<T>(lo, hi);
                 }
         }

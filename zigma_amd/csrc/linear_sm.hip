@@ -174,8 +174,11 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
                 unsigned oo[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float lo = __builtin_fmaf(lo16<T>(gg[e]), lo16<T>(vv[e]), lo16<T>(rr[e]));
-                    const float hi = __builtin_fmaf(hi16<T>(gg[e]), hi16<T>(vv[e]), hi16<T>(rr[e]));
+                    float lo = __builtin_fmaf(lo16<T>(gg[e]), lo16<T>(vv[e]), lo16<T>(rr[e]));
+                    float hi = __builtin_fmaf(hi16<T>(gg[e]), hi16<T>(vv[e]), hi16<T>(rr[e]));
+                    // fp16: the fp32 fma stays a value of its own, then it is rounded to the I/O type — not one v_fma_mixlo_f16 that rounds the exact
+                    // sum once (csrc/linear.hip, linear_epilogue: the same defined value in both kernels that round the projection before the gate)
+                    if constexpr (T::id == ZIGMA_F16) asm("" : "+v"(lo), "+v"(hi));
                     oo[e] = pack2<T>(lo, hi);
                 }
                 v = make_uint4(oo[0], oo[1], oo[2], oo[3]);
