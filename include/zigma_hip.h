@@ -39,7 +39,8 @@ extern "C" {
                                * 10: zigma_calib_launch (bench.py's box calibration) added; new ZIGMA_LINEAR_* kernel selectors of round 6
                                * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added
                                * (10, no block changed): zigma_linear_f32_split added
-                               * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added */
+                               * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added
+                               * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -690,6 +691,45 @@ typedef struct zigma_calib_params {
     void *dst;
 } zigma_calib_params_t;
 int zigma_calib_launch(const zigma_calib_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rounding of MANY float32 tensors to one 16-bit type in ONE launch (csrc/multi_cast.hip): the 16-bit copies of an fp32 model's matrix
+ * weights that mixed-precision training (torch.autocast) refreshes once per optimizer step — the work of the reference's per-op autocast
+ * casts (`custom_fwd(cast_inputs=...)`, selective_scan_interface.py:295-312), table-driven.  (ABI 10, no block changed.)
+ *
+ *   table      n_entries x {src, dst, numel} in DEVICE memory: dst[i] = round_to_nearest_even(src[i]), i < numel.  numel == 0 is legal.
+ *              Only the natural alignment of the element types is assumed (4 bytes for src, 2 for dst).
+ *   chunk_map  n_chunks x {entry, offset} in DEVICE memory: workgroup w converts elements [offset, min(offset + chunk, numel)) of table[entry].
+ *              The host splits every tensor into pieces of `chunk` elements; a map row whose entry or offset lies outside the table is skipped.
+ *   chunk      elements per workgroup: a multiple of 8 in 8 ... 65536.
+ * A workgroup whose source and destination pieces both start on 16-byte boundaries moves 8 elements per lane and access (two 16-byte loads,
+ * one 16-byte store) and finishes the last numel % 8 elements one by one; any other piece goes element by element.  The choice is uniform
+ * over the workgroup.  NaN stays NaN; every other input gives the bits of the other kernels' roundings (zigma_common.h from_float).
+ * Checked in this order, before any launch: negative counts (or more than 2^31 - 1 chunks) ZIGMA_ERR_SHAPE; out_dtype other than ZIGMA_BF16 /
+ * ZIGMA_F16 ZIGMA_ERR_DTYPE; non-zero flags ZIGMA_ERR_UNSUPPORTED; n_entries == 0 or n_chunks == 0: nothing is launched, ZIGMA_OK (table and
+ * chunk_map may then be NULL); NULL table / chunk_map ZIGMA_ERR_NULL; a chunk outside its range ZIGMA_ERR_SHAPE.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_multi_cast_entry {
+    const float *src;
+    void *dst;
+    int64_t numel;
+} zigma_multi_cast_entry_t;
+
+typedef struct zigma_multi_cast_chunk {
+    int64_t entry;    /* index into the table */
+    int64_t offset;   /* first element of the piece */
+} zigma_multi_cast_chunk_t;
+
+typedef struct zigma_multi_cast_params {
+    const zigma_multi_cast_entry_t *table;
+    const zigma_multi_cast_chunk_t *chunk_map;
+    int64_t n_entries, n_chunks;
+    int32_t out_dtype;   /* ZIGMA_BF16 or ZIGMA_F16 */
+    int32_t chunk;       /* elements per workgroup */
+    int32_t flags;       /* reserved, must be 0 */
+    int32_t pad_;
+} zigma_multi_cast_params_t;
+int zigma_multi_cast_fwd(const zigma_multi_cast_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
 const char *zigma_strerror(int status);

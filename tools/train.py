@@ -27,9 +27,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--amp", default="off", choices=["off", "bf16", "fp16"],
+                    help="mixed precision: the model is fp32 (whatever --dtype says) and the step runs under torch.autocast in this type; fp16 with a GradScaler")
     ap.add_argument("--bucket-mb", type=int, default=100, help="DDP bucket size: xGMI rings are per-link bound, few large buckets")
     args = ap.parse_args()
 
+    from zigma_amd import amp
     from zigma_amd import sharded_sampling as ss
     from zigma_amd.model_zigma import ZigMa
     from zigma_amd.transport import create_transport
@@ -41,7 +44,10 @@ def main():
     rank, world, _ = ss.init_from_env(backend="nccl", device=device)
     cfg = json.loads(args.config)
     torch.manual_seed(0)
-    model = ZigMa(device=device, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, **cfg).train()
+    mdtype = torch.float32 if args.amp != "off" else torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    model = ZigMa(device=device, dtype=mdtype, **cfg).train()
+    cast = torch.autocast("cuda", dtype=torch.bfloat16 if args.amp == "bf16" else torch.float16, enabled=args.amp != "off")
+    scaler = torch.amp.GradScaler("cuda", enabled=args.amp == "fp16")
     net = model
     if world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], bucket_cap_mb=args.bucket_mb,
@@ -60,9 +66,11 @@ def main():
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = tr.training_losses(net, x1, kw)["loss"].mean()
-        loss.backward()
-        opt.step()
+        with cast:
+            loss = tr.training_losses(net, x1, kw)["loss"].mean()
+        scaler.scale(loss).backward()          # (a disabled scaler passes the loss and the step through)
+        scaler.step(opt)
+        scaler.update()
         return loss
 
     losses = []
@@ -77,7 +85,8 @@ def main():
     if rank == 0:
         print(json.dumps(dict(world=world, per_gpu_batch=args.batch, ms_per_step=round(dt * 1e3, 2),
                               samples_per_s=round(world * args.batch / dt, 1), first_loss=round(float(losses[0]), 4),
-                              last_loss=round(float(losses[-1]), 4), max_mem_GB=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))))
+                              last_loss=round(float(losses[-1]), 4), max_mem_GB=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                              amp=args.amp, amp_stats=dict(amp.STATS), use_shadows=amp.USE_SHADOWS)))
     if world > 1:
         torch.distributed.destroy_process_group()
 

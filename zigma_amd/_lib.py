@@ -185,7 +185,11 @@ class NormLinearParams(C.Structure):
                 + [(n, vp) for n in ("x", "w", "shift", "scale", "out")])
 
 
-EXPORTS = ("zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
+class MultiCastParams(C.Structure):
+    _fields_ = [("table", vp), ("chunk_map", vp), ("n_entries", i64), ("n_chunks", i64), ("out_dtype", i32), ("chunk", i32), ("flags", i32), ("pad_", i32)]
+
+
+EXPORTS = ("zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
            "zigma_selective_scan_bwd_workspace_bytes", "zigma_causal_conv1d_bwd",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
@@ -210,7 +214,8 @@ def lib():
                          ("zigma_add_norm_bwd", NormBwdParams), ("zigma_cross_attn_fwd", XAttnParams), ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_patch_embed_fwd", PatchEmbedParams),
                          ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_skinny_linear_fwd", SkinnyParams), ("zigma_x_proj_fwd", XProjParams),
                          ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
-                         ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams)):
+                         ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams),
+                         ("zigma_multi_cast_fwd", MultiCastParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st), vp]
             fn.restype = C.c_int

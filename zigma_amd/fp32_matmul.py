@@ -20,7 +20,7 @@ import weakref
 
 import torch
 
-from . import _knobs, _lib
+from . import _knobs, _lib, amp
 
 MODES = ("highest", "high", "medium")
 PRECISION = "highest"
@@ -74,7 +74,7 @@ def split_weight(w):
     the parameter bumps its version and the next call splits again, replacing the stale entry (one slot per device address); the entry goes
     when the tensor object does."""
     slot = (str(w.device), w.data_ptr())
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), str(w.device))
+    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), str(w.device), amp.step_count())      # (fused optimizers do not move _version)
     hit = _CACHE.get(slot)
     if hit is not None and hit[0] == key:
         CACHE_STATS["hit"] += 1

@@ -7,6 +7,7 @@ for tensors and shapes, and tests/test_host_cpu.py checks them against the compi
 import torch
 
 from . import _lib
+from . import amp
 from . import fp32_matmul
 from . import routing
 
@@ -116,7 +117,13 @@ def plan(role, x, weight, bias=None, residual=None, gate=None):
     """The ONE decision which kernel serves a projection (routing.ROLES) on these tensors: the first route of the table (routing.candidates) whose
     kernel's shape and tensor limits the call meets; a route the tensors refuse is logged in routing.REFUSED and the walk goes on.  Calls no own kernel
     can take (mixed dtypes, CPU tensors, autograd, fp32 models unless fp32_matmul.PRECISION opts them into the bf16-split kernel) are the library's.  fuse_add: the kernel carries residual + gate[:, None] * (.) in its
-    epilogue (the route fuses, residual / gate are given and meet the epilogue's limits, no autograd)."""
+    epilogue (the route fuses, residual / gate are given and meet the epilogue's limits, no autograd).  Under torch.autocast a 16-bit activation beside an fp32
+    weight is planned on the weight's 16-bit shadow (zigma_amd/amp.py): the same rows as for a model of that type."""
+    if torch.is_autocast_enabled():
+        w0, b0 = weight, bias
+        weight, bias = amp.planned(x, weight, bias)          # (stand-ins of the shadows: a plan casts nothing)
+        if weight is not w0 and torch.is_grad_enabled() and (w0.requires_grad or (b0 is not None and b0.requires_grad)):
+            return routing.Route("library", False, "autograd")        # (the shadows require no grad; the parameters do: wgrad.linear_train)
     n, k = weight.shape
     if not linear_eligible(x, weight, bias):
         # fp32 tensors of an inference call, opted in by fp32_matmul.PRECISION: the bf16-split kernel, for every role; its gated add stays where the
@@ -140,6 +147,8 @@ def run(r, x, weight, bias=None, residual=None, gate=None, silu_from_col=None):
     if r.kernel == "library":
         from .wgrad import linear_train
         return linear_train(x, weight, bias)
+    if torch.is_autocast_enabled():                  # (the operands plan() judged; the library route above takes the parameters themselves: autograd)
+        weight, bias = amp.operands(x, weight, bias)
     if r.kernel in ("split3", "split1"):
         return fp32_matmul.linear_split(x, weight, bias, mode="high" if r.kernel == "split3" else "medium")
     if r.kernel == "tiled_halves":

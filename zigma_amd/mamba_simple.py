@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _knobs
+from . import _knobs, amp
 from .linear import plan, project, run
 from .selective_scan_interface import differentiable, mamba_inner_tok, z_preactivated_eligible
 
@@ -166,7 +166,8 @@ class Mamba(nn.Module):
         (mamba_simple.py:298,383-384).  They only change when the parameters do, so they are cached against the
         parameters' version counters instead of being recomputed by three eager kernels per layer per forward."""
         A_log, D, dtb = getattr(self, "A" + sfx + "_log"), getattr(self, "D" + sfx), getattr(self, "dt_proj" + sfx).bias
-        key = (A_log._version, D._version, dtb._version, A_log.data_ptr(), D.data_ptr(), dtb.data_ptr())
+        # (+ the optimizer-step count: torch's fused optimizers write the parameters without moving _version)
+        key = (A_log._version, D._version, dtb._version, A_log.data_ptr(), D.data_ptr(), dtb.data_ptr(), amp.step_count())
         hit = self._const_cache.get(sfx)
         if hit is None or hit[0] != key or torch.is_grad_enabled():
             vals = (-torch.exp(A_log.float()), D.float(), dtb.float())

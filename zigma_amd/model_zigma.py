@@ -29,6 +29,7 @@ import torch.nn.functional as F
 import torch.utils.checkpoint
 from torch import Tensor
 
+from . import amp
 from .attention import attention_math, cross_attn, cross_attn_bwd_eligible, cross_attn_eligible, cross_attn_train
 from . import embed as _embed
 from .layernorm import RMSNorm, block_norm, glue_bwd_eligible, layer_norm_fn, rms_norm_fn, scale_reduce_bwd
@@ -299,20 +300,22 @@ from . import _knobs  # noqa: E402
 _knobs.apply(globals(), "model_zigma")      # ZIGMA_KNOBS="model_zigma.FUSE_OUT_PROJ_ADD=False,..." (A/B tools)
 
 
-def fuse_norm_to_q(pend, to_q, shift, scale):
+def fuse_norm_to_q(pend, to_q, shift, scale, weight=None):
     """the block's decision to form q = to_q(modulate(norm_msa(h))) in ONE kernel: the pending input carries no branch (out_proj made the gated add, so the
     LayerNorm call would only read h and write xa), the routing table serves to_q at this shape with an own kernel (routing.POLICY = "off" therefore switches
-    this off too), at least NORM_TO_Q_MIN_TOKENS tokens, tensors the kernel takes (norm_linear_eligible: 16-bit, no bias, no autograd)."""
+    this off too), at least NORM_TO_Q_MIN_TOKENS tokens, tensors the kernel takes (norm_linear_eligible: 16-bit, no bias, no autograd).  weight: the operand
+    the kernel would read instead of to_q.weight (its 16-bit shadow under torch.autocast)."""
     if not FUSE_NORM_TO_Q or pend.branch is not None:
         return False
     x = pend.base
     if x.dim() != 3:
         return False
     tokens = x.shape[0] * x.shape[1]
-    n, k = to_q.weight.shape
+    w = to_q.weight if weight is None else weight
+    n, k = w.shape
     if tokens < NORM_TO_Q_MIN_TOKENS or routing.route("to_q", tokens, n, k).kernel == "library":
         return False
-    return norm_linear_eligible(x, to_q.weight, shift, scale, to_q.bias)
+    return norm_linear_eligible(x, w, shift, scale, to_q.bias)
 
 
 class Block(nn.Module):
@@ -355,9 +358,12 @@ class Block(nn.Module):
         pend = Pending(y) if fused else Pending(n, y, g)
         if not self.has_text:
             return pend, residual
-        if fuse_norm_to_q(pend, self.msa.to_q, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E]):
+        wq = self.msa.to_q.weight
+        if torch.is_autocast_enabled():                  # mixed precision: the kernel reads the 16-bit shadow
+            wq = amp.operands(pend.base, wq)[0]
+        if fuse_norm_to_q(pend, self.msa.to_q, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E], weight=wq):
             # xa = modulate(norm_msa(h)) never leaves the registers of the to_q kernel; h itself is the residual of to_out's epilogue
-            q = norm_linear(pend.base, self.msa.to_q.weight, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E], self.norm_msa.eps)
+            q = norm_linear(pend.base, wq, mod[:, 3 * E:4 * E], mod[:, 4 * E:5 * E], self.norm_msa.eps)
             return Pending(self.msa(None, text=text, mask=None, kv=kv, residual=pend.base, gate=mod[:, 5 * E:6 * E], q=q)), residual
         h, _, _, xa = block_norm(pend.base, None, None, None, self.norm_msa.eps, False, residual_in_fp32=False, branch=pend.branch,
                                  gate=pend.gate, shift=mod[:, 3 * E:4 * E], scale=mod[:, 4 * E:5 * E], want_x=True, want_y=False, want_res_out=False)
@@ -595,6 +601,14 @@ class ZigMa(nn.Module):
         """x: (N, C, H, W) [or (N, T, C, H, W)] latents; t: (N,) diffusion times; y: (N,) labels or (N, n_ctx, d_ctx) text."""
         in_dtype = hidden_states.dtype
         pdtype = self.x_embedder.proj.weight.dtype
+        # mixed precision (an fp32 model under torch.autocast): the embedders, adaLN, the label embedding and the final layer stay torch ops, which
+        # autocast casts; the token stream enters the blocks in the autocast type (the residual stream stays fp32 as always) and the blocks' matrix
+        # weights are read through their 16-bit shadows (zigma_amd/amp.py), registered on the first such forward
+        adt = amp.autocast_dtype() if torch.is_autocast_enabled() and pdtype == torch.float32 and hidden_states.is_cuda else None
+        if adt is not None and adt not in (torch.bfloat16, torch.float16):
+            adt = None
+        if adt is not None and not amp.attached(self):            # (also a deepcopy of an attached model: its group is a copy)
+            amp.attach(self)
         pos = self.pos_embed if self.use_pe in (1, 2) else None
         hidden_states = self.x_embedder(hidden_states.to(pdtype), pos=pos)      # (N, T, D), position table added
         _B, _T, _D = hidden_states.shape
@@ -602,7 +616,7 @@ class ZigMa(nn.Module):
         t = (t * 1000.0).to(hidden_states)
         t = self.t_embedder(t)                                                  # (N, D)
         if self.has_text:
-            yp = y.to(pdtype)
+            yp = y.to(pdtype if adt is None else adt)
             y = _text_linear(yp, self.y_embedder.weight, self.y_embedder.bias)     # (B, n_ctx, D)
             c = t + y.mean(dim=1)
         elif self.num_classes > 0:
@@ -614,6 +628,8 @@ class ZigMa(nn.Module):
             K = _T // self.video_frames
             hidden_states = (hidden_states.view(_B, self.video_frames, K, _D)
                              + self.temporal_pos_embedding.view(1, self.video_frames, 1, _D)).view(_B, _T, _D)
+        if adt is not None:
+            hidden_states, c = hidden_states.to(adt), c.to(adt)
 
         residual = None
         # autograd recording -> the per-block differentiable composition (HIP forward + backward kernels);
@@ -666,12 +682,15 @@ class ZigMa(nn.Module):
         plist = [b.adaLN_modulation[-1].weight for b in blocks] + [b.adaLN_modulation[-1].bias for b in blocks]
         if self.has_text:
             plist += [b.msa.to_k.weight for b in blocks] + [b.msa.to_v.weight for b in blocks]
-        key = tuple((p._version, p.data_ptr()) for p in plist)
+        # (mixed precision: the stacked K / V weight is built from the 16-bit shadows, the adaLN product stays autocast's)
+        adt = text.dtype if self.has_text and amp.mixed(text, blocks[0].msa.to_k.weight) else None
+        kvw = (lambda p: p) if adt is None else (lambda p: amp.shadow(p, adt))
+        key = tuple((p._version, p.data_ptr()) for p in plist) + (adt, amp.step_count())      # (the step count: fused optimizers do not move _version)
         cache = getattr(self, "_cond_cache", None)
         if cache is None or cache[0] != key:
             Wm = torch.cat([b.adaLN_modulation[-1].weight for b in blocks], 0)
             bm = torch.cat([b.adaLN_modulation[-1].bias for b in blocks], 0)
-            Wkv = torch.cat([torch.cat([b.msa.to_k.weight, b.msa.to_v.weight], 0) for b in blocks], 0) if self.has_text else None
+            Wkv = torch.cat([torch.cat([kvw(b.msa.to_k.weight), kvw(b.msa.to_v.weight)], 0) for b in blocks], 0) if self.has_text else None
             cache = (key, Wm.detach(), bm.detach(), None if Wkv is None else Wkv.detach())
             self._cond_cache = cache
         _, Wm, bm, Wkv = cache

@@ -23,7 +23,7 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
-from . import _knobs, _lib
+from . import _knobs, _lib, amp
 from .causal_conv1d_interface import causal_conv1d_raw, conv_bwd_tok
 from .wgrad import plan_wgrad, wgrad
 
@@ -492,10 +492,25 @@ class MambaInnerTokFn(torch.autograd.Function):
     zigzag reordering fused into the kernels' row tables in BOTH directions (no index_select / index_add / cat):
     forward  = conv (x_row_index) -> GEMMs -> scan (z_row_index, out_row_index), saving u, x_dbl, delta and the ungated y;
     backward = scan bwd (same tables; dz lands in token order) -> the two skinny GEMM pairs -> conv bwd (dx scattered
-    through x_row_index).  Mirrors MambaInnerFn (selective_scan_interface.py:296-434) without its out_proj."""
+    through x_row_index).  Mirrors MambaInnerFn (selective_scan_interface.py:296-434) without its out_proj.
+    Under torch.autocast with a 16-bit xz and fp32 parameters (the reference's custom_fwd, :295-312): x_proj_w and dt_proj_w are replaced by their
+    16-bit shadows (zigma_amd/amp.py) — the shadows are what is saved —, the conv taps, A, D and delta_bias stay fp32 (the kernels take them so);
+    the backward runs with autocast off on operands of one type and returns every parameter gradient in the parameter's own type, the two GEMM
+    weight gradients in fp32 straight from the fp32 sums."""
 
     @staticmethod
-    def forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan):
+    def forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan, *shadows):
+        # shadows: (x_proj_w, dt_proj_w) in xz's type when the caller (mamba_inner_tok) already holds them for its plan
+        ctx.amp = amp.mixed(xz, x_proj_w) and amp.mixed(xz, dt_proj_w)
+        ctx.w_dtypes, ctx.n_extra = (x_proj_w.dtype, dt_proj_w.dtype), len(shadows)
+        if ctx.amp:
+            x_proj_w, dt_proj_w = shadows if shadows else (amp.shadow(x_proj_w, xz.dtype), amp.shadow(dt_proj_w, xz.dtype))
+            with torch.autocast("cuda", enabled=False):
+                return MambaInnerTokFn._forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan)
+        return MambaInnerTokFn._forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan)
+
+    @staticmethod
+    def _forward(ctx, xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, perm, out_rows, reset_period, plan):
         # reset_period > 0 (the video temporal layers): xz is the (k, b * t, 2 Di) strided VIEW of the (b * t, k, 2 Di) projection output —
         # batch = pixel, sequence = the frames of every sample one after the other, conv window and state restart every t steps; the
         # result and d(xz) are views of (b * t, k, .) allocations, so neither direction pays a transposing copy
@@ -523,7 +538,16 @@ class MambaInnerTokFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if ctx.amp:
+            with torch.autocast("cuda", enabled=False):
+                return MambaInnerTokFn._backward(ctx, dy)
+        return MambaInnerTokFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
         xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias, u, x_dbl, delta, out = ctx.saved_tensors
+        # mixed precision: the fp32 sums of the two weight gradients, not rounded to the operand type
+        wg = (lambda dy2, x2: wgrad(dy2, x2, out_dtype=torch.float32)) if ctx.amp else wgrad
         Bsz, L, C2 = xz.shape
         Di, R, N = C2 // 2, dt_proj_w.shape[1], A.shape[1]
         x_half, z_half = xz[:, :, :Di], xz[:, :, Di:]
@@ -542,14 +566,14 @@ class MambaInnerTokFn(torch.autograd.Function):
         x_dt = x_dbl.reshape(-1, R + 2 * N)[:, :R]
         if plan_wgrad(dd2, x_dt) != "own":                                          # (the own kernel takes the 72-pitch column view as it is)
             x_dt = x_dt.contiguous()
-        d_dt_w = wgrad(dd2, x_dt)                                                   # (Di, R)  zigma_linear_wgrad or token-slab GEMMs (zigma_amd/wgrad.py)
+        d_dt_w = wg(dd2, x_dt)                                                      # (Di, R)  zigma_linear_wgrad or token-slab GEMMs (zigma_amd/wgrad.py)
         dxd = dx_dbl.to(xz.dtype).reshape(-1, R + 2 * N)
         du = torch.addmm(du.reshape(-1, Di), dxd, x_proj_w).reshape(Bsz, L, Di)    # x_dbl = u @ W_x^T
-        d_x_w = wgrad(dxd, u.reshape(-1, Di))                                      # (R + 2N, Di)
+        d_x_w = wg(dxd, u.reshape(-1, Di))                                         # (R + 2N, Di)
         _, d_cw, d_cb = conv_bwd_tok(x_half, conv_w, conv_b, du, True, ctx.perm, dx=dxz[:, :, :Di], reset_period=rp)
         return (dxz, d_cw.to(conv_w.dtype).reshape(conv_w.shape), None if d_cb is None else d_cb.to(conv_b.dtype),
-                d_x_w.to(x_proj_w.dtype), d_dt_w.to(dt_proj_w.dtype), dA.to(A.dtype), dD.to(D.dtype),
-                None if dbias is None else dbias.to(delta_bias.dtype), None, None, None, None)
+                d_x_w.to(ctx.w_dtypes[0]), d_dt_w.to(ctx.w_dtypes[1]), dA.to(A.dtype), dD.to(D.dtype),
+                None if dbias is None else dbias.to(delta_bias.dtype), None, None, None, None) + (None,) * ctx.n_extra
 
 
 def selective_scan_cuda_fwd(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus):
@@ -634,13 +658,17 @@ def mamba_inner_tok(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_we
     Bsz, L, C2 = xz.shape
     Di, R, N = C2 // 2, delta_proj_weight.shape[1], A.shape[1]
     w, x_half, z_half = conv1d_weight.reshape(Di, -1), xz[:, :, :Di], xz[:, :, Di:]
+    params, shadows = (x_proj_weight, delta_proj_weight), ()          # what MambaInnerTokFn differentiates; what its kernels read instead
+    if amp.mixed(xz, x_proj_weight) and amp.mixed(xz, delta_proj_weight):
+        # mixed precision: the kernels (and the plan) read the 16-bit shadows of the two GEMM weights; conv taps, A, D, delta_bias stay fp32
+        x_proj_weight, delta_proj_weight = shadows = (amp.shadow(x_proj_weight, xz.dtype), amp.shadow(delta_proj_weight, xz.dtype))
     plan = plan_inner(x_half, z_half, w, conv1d_bias, x_proj_weight, delta_proj_weight, A, delta_bias, perm=perm, reset_period=reset_period,
                       z_preactivated=z_preactivated, out=out, add_to=add_to, B_proj_bias=B_proj_bias, C_proj_bias=C_proj_bias,
                       delta_softplus=delta_softplus, train=train)
     out_rows = perm if out_rows is None else out_rows
     if train:
-        return MambaInnerTokFn.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, perm, out_rows,
-                                     int(reset_period), plan)
+        return MambaInnerTokFn.apply(xz, conv1d_weight, conv1d_bias, *params, A, D, delta_bias, perm, out_rows,
+                                     int(reset_period), plan, *shadows)
     u, x_dbl = _run_front(plan, x_half, w, conv1d_bias, x_proj_weight, perm, reset_period)
     delta = None                     # "in_scan": dt_proj + bias + softplus inside the scan kernel's tile prologue, delta never exists
     if plan.dt == "in_split":        # the split's first pass forms delta and writes it into this workspace for the second

@@ -16,7 +16,7 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
-from . import _knobs, _lib
+from . import _knobs, _lib, amp
 from .linear import plan, run
 
 SPLIT_WGRAD = True        # False: one GEMM (A/B in tools/train_probe.py)
@@ -175,14 +175,20 @@ def wgrad_workspace_bytes(m, n, k, dtype=torch.bfloat16, slabs=0):
     return int(_lib.lib().zigma_linear_wgrad_workspace_bytes(ctypes.byref(P)))
 
 
-def wgrad(dy2, x2):
+def wgrad(dy2, x2, out_dtype=None):
     """dy2 (m, n), x2 (m, k), same 16-bit dtype -> dy2^T x2 (n, k) in that dtype: the own split-K kernel where plan_wgrad says so, else the fp32
-    sum of the library's slab products"""
+    sum of the library's slab products.  out_dtype=torch.float32 (the gradient of an fp32 weight under autocast): the same sums, delivered without the
+    rounding to the operand type."""
+    f32 = out_dtype == torch.float32 and dy2.dtype != torch.float32
     if plan_wgrad(dy2, x2) == "own":
-        return wgrad_own(dy2, x2)
+        return wgrad_own(dy2, x2, out_dtype=torch.float32 if f32 else None)
     m, n = dy2.shape
     k = x2.shape[1]
     s = _slabs(m, n, k) if (SPLIT_WGRAD and dy2.is_cuda and dy2.dtype in (torch.bfloat16, torch.float16)) else 1
+    if s <= 1 and f32:               # one product of the library with an fp32 result
+        if _bmm_takes_out_dtype(dy2):
+            return torch.bmm(dy2.t().unsqueeze(0), x2.unsqueeze(0), out_dtype=torch.float32)[0]
+        return dy2.t().float() @ x2.float()
     if s <= 1:
         return dy2.t() @ x2
     dy3 = dy2.reshape(s, m // s, n)
@@ -192,14 +198,20 @@ def wgrad(dy2, x2):
         part = torch.bmm(dy3.transpose(1, 2), x3, out_dtype=torch.float32)
     else:                                  # (a torch without out_dtype on bmm)
         part = torch.bmm(dy3.transpose(1, 2), x3).float()
-    return part.sum(0).to(dy2.dtype)
+    return part.sum(0) if f32 else part.sum(0).to(dy2.dtype)
 
 
 class LinearTrainFn(torch.autograd.Function):
-    """F.linear whose weight gradient is formed slab-wise (see the module docstring); dX and dbias as autograd forms them."""
+    """F.linear whose weight gradient is formed slab-wise (see the module docstring); dX and dbias as autograd forms them.
+    Mixed precision (a 16-bit x beside an fp32 weight under torch.autocast): the forward and dX read the weight's 16-bit shadow (zigma_amd/amp.py) — the
+    shadow is what is saved —, dW and dbias are delivered in fp32 from the fp32 sums, and the backward runs with autocast off, as under the reference's
+    custom_fwd / custom_bwd."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
+        ctx.amp = amp.mixed(x, weight)
+        if ctx.amp:
+            weight, bias = amp.operands(x, weight, bias)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         r = plan("train", x, weight, bias)            # (autograd is off in here)
@@ -207,6 +219,13 @@ class LinearTrainFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if ctx.amp:
+            with torch.autocast("cuda", enabled=False):
+                return LinearTrainFn._backward(ctx, dy)
+        return LinearTrainFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
         x, weight = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1])
         dx = dw = db = None
@@ -215,14 +234,20 @@ class LinearTrainFn(torch.autograd.Function):
             r = plan("train", dyc, _ContiguousLike(weight))        # dX = dY W = dY (W^T)^T: the same kernels on the transposed weight (a few MB)
             dx = (dy2 @ weight if r.kernel == "library" else run(r, dyc, weight.t().contiguous())).view(x.shape)
         if ctx.needs_input_grad[1]:
-            dw = wgrad(dy2, x.reshape(-1, x.shape[-1]))
+            dw = wgrad(dy2, x.reshape(-1, x.shape[-1]), out_dtype=torch.float32 if ctx.amp else None)
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy2.sum(0)
+            db = dy2.sum(0, dtype=torch.float32) if ctx.amp else dy2.sum(0)
         return dx, dw, db
 
 
 def linear_train(x, weight, bias=None):
-    """differentiable projection of the training path: the slab-wise weight gradient where it pays (many tokens), F.linear otherwise"""
+    """differentiable projection of the training path: the slab-wise weight gradient where it pays (many tokens), F.linear otherwise.
+    Under torch.autocast a 16-bit x beside an fp32 weight (amp.mixed) runs on the weight's shadow: LinearTrainFn at every token count when autograd records
+    (the fp32 parameter receives an fp32 gradient), F.linear on the shadows otherwise."""
+    if torch.is_autocast_enabled() and amp.mixed(x, weight) and (bias is None or bias.dtype == weight.dtype):
+        if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+            return LinearTrainFn.apply(x, weight, bias)
+        return F.linear(x, *amp.operands(x, weight, bias))
     if (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x.dtype and (bias is None or bias.dtype == x.dtype)
             and x.numel() // x.shape[-1] >= 4096 and torch.is_grad_enabled() and not torch.is_autocast_enabled()):
         return LinearTrainFn.apply(x, weight, bias)
