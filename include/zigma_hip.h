@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ZIGMA_ABI_VERSION 10  /* 2: parameter blocks grew (row tables in the backward, checkpoints, reset_period)
+#define ZIGMA_ABI_VERSION 11  /* 2: parameter blocks grew (row tables in the backward, checkpoints, reset_period)
                                * 3: scan block: `info` out-field, ZIGMA_SCAN_Z_PREACTIVATED flag; zigma_linear_fwd
                                * 4: zigma_linear_params_t grew (gated residual epilogue); zigma_conv_x_proj_fwd, zigma_q_attn_fwd
                                * 5: pruned — zigma_q_attn_fwd and the dt product of zigma_conv_xproj_params_t removed (measured no faster,
@@ -40,7 +40,8 @@ extern "C" {
                                * (10, no block changed): zigma_linear_wgrad / zigma_linear_wgrad_workspace_bytes added
                                * (10, no block changed): zigma_linear_f32_split added
                                * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added
-                               * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added */
+                               * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added
+                               * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -730,6 +731,24 @@ typedef struct zigma_multi_cast_params {
     int32_t pad_;
 } zigma_multi_cast_params_t;
 int zigma_multi_cast_fwd(const zigma_multi_cast_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Host-only plan queries of the Mamba inner's five forward entry points (ABI 11): what the launch would do with this parameter block,
+ * asked before anything is allocated or launched.  Each runs the same plan_*() (csrc/scan_plan.h, csrc/front_plan.h) as its launcher.
+ *
+ *   returns   the status the launch would return for this block (never ZIGMA_ERR_LAUNCH);
+ *   *kernel   the name zigma_last_kernel() would report after the launch, or NULL where nothing would launch (a refusal, an empty call).
+ *             For a call the launcher runs in batch slices: the first refusing slice's status, else the last slice's kernel.
+ *
+ * A query makes no HIP call, reads the block's sizes, strides, flags and pointer VALUES only (no operand is dereferenced, so the
+ * addresses of tensors yet to be allocated may be placeholders with the alignment the allocator guarantees), writes neither p->info nor
+ * the last-kernel record, and may be called with no device present and during stream capture.
+ */
+int zigma_selective_scan_fwd_plan(const zigma_scan_params_t *p, const char **kernel);
+int zigma_causal_conv1d_fwd_plan(const zigma_conv_params_t *p, const char **kernel);
+int zigma_conv_x_proj_fwd_plan(const zigma_conv_xproj_params_t *p, const char **kernel);
+int zigma_x_proj_fwd_plan(const zigma_xproj_params_t *p, const char **kernel);
+int zigma_dt_proj_softplus_fwd_plan(const zigma_dtproj_params_t *p, const char **kernel);
 
 /* ------------------------------------------------------------------------------------------ */
 const char *zigma_strerror(int status);

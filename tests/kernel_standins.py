@@ -303,7 +303,13 @@ def install_lib_call(monkeypatch, plan=None, front_plan=None, linear_plan=None, 
         LAST_KERNEL[0] = serve[fn_name](params)
         if _lib.TRACE is not None:
             _lib.TRACE.append((fn_name, LAST_KERNEL[0], params))
+    plans = dict.fromkeys(("zigma_causal_conv1d_fwd", "zigma_conv_x_proj_fwd", "zigma_x_proj_fwd", "zigma_dt_proj_softplus_fwd"), front_plan)
+
+    def ask(fn_name, params):            # _lib.plan: the host-only queries (zigma_*_fwd_plan), from the same compiled plans
+        got = {"zigma_selective_scan_fwd": plan, **plans}[fn_name](params)
+        return got["status"], got["kernel"]
     monkeypatch.setattr(_lib, "call", call)
+    monkeypatch.setattr(_lib, "plan", ask)
     monkeypatch.setattr(_lib, "require_device", lambda *t: torch.device("cpu"))
     monkeypatch.setattr(_lib, "last_kernel", lambda: LAST_KERNEL[0])
 

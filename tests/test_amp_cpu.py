@@ -35,7 +35,7 @@ def test_multi_cast_struct_matches_the_header():
     for f, _ in st._fields_:
         assert got[f] == [getattr(st, f).offset], f
     assert got["row_entry"] == [24, 0, 8, 16] and got["row_chunk"] == [16, 0, 8]
-    assert got["abi"] == [10]
+    assert got["abi"] == [11]
     assert "zigma_multi_cast_fwd" in _lib.EXPORTS
     from zigma_amd import build
     assert "multi_cast.hip" in build.SOURCES and build.SOURCE_FLAGS["multi_cast.hip"] == build._RES and "multi_cast_kernel" in build.NO_SCRATCH_KERNELS

@@ -24,9 +24,13 @@ KIND = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}
 def _launch(fn, P):
     from zigma_amd import _lib
     before = _lib.last_kernel()
+    asked = _lib.plan(fn, P)                                    # the host-only query first: it must foretell the launch and report nothing itself
+    assert _lib.last_kernel() == before
     rc = getattr(_lib.lib(), fn)(ctypes.byref(P), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    return rc, before, _lib.last_kernel()
+    after = _lib.last_kernel()
+    assert asked == (rc, after if asked[1] is not None else None) and (asked[1] is not None or after == before), (asked, rc, before, after)
+    return rc, before, after
 
 
 @pytest.mark.parametrize("name", sorted(fpc.CASES))

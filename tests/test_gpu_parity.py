@@ -1473,9 +1473,46 @@ def test_batch_beyond_the_grid_limit_runs_in_slices():
     assert torch.equal(y[sel], run(sel))
 
 
+@pytest.mark.parametrize("B,kw,dt", [(2, {}, "in_split"), (16, {}, "in_scan"), (16, {"add_to": True}, "in_scan"), (2, {"add_to": True}, "in_split"),
+                                     (16, {"out": True, "z_preactivated": True}, "in_scan")])
+def test_planned_scan_block_equals_the_built_one(B, kw, dt, monkeypatch):
+    """mamba_inner_tok launches the scan block its dt decision built on descriptors of tensors that were yet to be allocated (scan_planned): byte for
+    byte the block scan_block builds from the real tensors of that call — every size, stride, flag and address — and the result is the one of the
+    ordinary launch (scan_raw on the same operands), bit for bit"""
+    import ctypes
+    import zigma_amd.selective_scan_interface as ssi
+    L, Di, R, N = 1024, 1280, 40, 16                 # B = 2: 40 workgroups, the sequence split; B = 16: 320, the whole sequence
+    g = torch.Generator().manual_seed(B)
+    mk = lambda *s, dtype=torch.bfloat16: (torch.randn(*s, generator=g) * 0.3).to(device=DEV, dtype=dtype)
+    xz, cw, cb, xw, dw = mk(B, L, 2 * Di), mk(Di, 1, 4), mk(Di), mk(R + 2 * N, Di), mk(Di, R)
+    A, D, db = -torch.rand(Di, N, generator=g).to(DEV), mk(Di, dtype=torch.float32), mk(Di, dtype=torch.float32)
+    perm = torch.randperm(L, generator=g).to(device=DEV, dtype=torch.int32)
+    given = lambda: {k: (mk(B, L, Di) if k in ("add_to", "out") else v) for k, v in kw.items()}
+    seen, real = [], ssi.scan_planned
+
+    def planned(P, u, x_dbl, delta, xc, y, z, A_, D_, bias, zi, oi, zact, acc):
+        real(P, u, x_dbl, delta, xc, y, z, A_, D_, bias, zi, oi, zact, acc)
+        tok, cols = (lambda t: None if t is None else t.transpose(1, 2)), (lambda a: x_dbl[:, :, a:a + N].transpose(1, 2).unsqueeze(1))
+        Q = ssi.scan_block(tok(u), tok(delta), A_, cols(R), cols(R + N), D_, tok(z), bias, True, out_z=tok(y), x=xc, z_row_index=zi, out_row_index=oi,
+                           chunk_len=P.chunk_len, z_preactivated=zact, dt_x=x_dbl, dt_w=dw, accumulate=acc)
+        seen.append(bytes(P) == bytes(Q) and bool(P.x) == (dt == "in_split"))
+    monkeypatch.setattr(ssi, "scan_planned", planned)
+    torch.manual_seed(0)
+    with torch.no_grad():
+        k1 = given()
+        y0 = k1["add_to"].clone() if "add_to" in k1 else None
+        y1 = ssi.mamba_inner_tok(xz, cw, cb, xw, dw, A, D, db, perm=perm, **k1)
+        assert seen == [True] * (dt == "in_scan" or "add_to" not in kw)       # (the split does not add in its epilogue: that call is built the ordinary way)
+        monkeypatch.setattr(ssi, "dt_in_scan_eligible", lambda *a, keep=None, **k: True)     # same plan, no block handed over
+        k2 = dict(k1, **({"add_to": y0} if y0 is not None else {}), **({"out": torch.empty_like(k1["out"])} if "out" in k1 else {}))
+        y2 = ssi.mamba_inner_tok(xz, cw, cb, xw, dw, A, D, db, perm=perm, **k2)
+    assert len(seen) <= 1 and torch.equal(y1, y2) and torch.isfinite(y1.float()).all()
+
+
 @pytest.mark.parametrize("name", sorted(__import__("scan_plan_cases").CASES))
 def test_scan_dispatch_case_table(name):
-    """every case of the dispatch table (tests/scan_plan_cases.py) through zigma_selective_scan_fwd: status, info, last kernel"""
+    """every case of the dispatch table (tests/scan_plan_cases.py) through zigma_selective_scan_fwd: status, info, last kernel; the host-only query
+    (zigma_selective_scan_fwd_plan), asked first, foretells status and kernel and leaves info and the last kernel alone"""
     import ctypes
     import scan_plan_cases
     from zigma_amd import _lib
@@ -1483,8 +1520,11 @@ def test_scan_dispatch_case_table(name):
 
     def launch(P):
         before = _lib.last_kernel()
+        asked = _lib.plan("zigma_selective_scan_fwd", P)
+        assert _lib.last_kernel() == before and (P.info[0], P.info[1]) == (0, 0)
         rc = _lib.lib().zigma_selective_scan_fwd(ctypes.byref(P), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
+        assert asked == (rc, _lib.last_kernel() if asked[1] is not None else None), (asked, rc, _lib.last_kernel())
         return rc, (P.info[0], P.info[1]), before, _lib.last_kernel()
     rc, info, before, after = scan_plan_cases.call(case, DEV, launch)
     assert rc == want.status

@@ -33,7 +33,7 @@ def test_cabi_exports_every_declared_symbol(libpath):
         assert hasattr(L, name), name
     L.zigma_abi_version.restype = ctypes.c_int
     L.zigma_strerror.restype = ctypes.c_char_p
-    assert L.zigma_abi_version() == 10
+    assert L.zigma_abi_version() == 11
     assert L.zigma_strerror(-2) == b"size out of the supported range"
     from zigma_amd import _lib
     assert set(_lib.EXPORTS) <= declared
@@ -79,7 +79,7 @@ def test_flag_constants_match_the_header():
     assert defs["ZIGMA_SCAN_KERNEL_TOK2"] == _lib.SCAN_KERNEL_TOK2
     assert defs["ZIGMA_SCAN_Z_PREACTIVATED"] == _lib.SCAN_Z_PREACTIVATED and defs["ZIGMA_SCAN_PROBE_V1"] == _lib.SCAN_PROBE_V1
     assert defs["ZIGMA_SCAN_PROBE_PRIO_SHIFT"] == _lib.SCAN_PROBE_PRIO_SHIFT and defs["ZIGMA_SCAN_PROBE_R5_SHIFT"] == _lib.SCAN_PROBE_R5_SHIFT
-    assert defs["ZIGMA_ABI_VERSION"] == 10
+    assert defs["ZIGMA_ABI_VERSION"] == 11
 
 
 def test_knobs_env_override():
@@ -597,11 +597,10 @@ def test_sequence_split_policy():
 _PLAN_DRIVER = r"""
 #include "scan_plan.h"
 using namespace zigma;
-// what the library reports for a call: the plan, or for a sliced batch the plan of the slice that runs last
+// what the library reports for a call: the plan, or for a sliced batch the plan of the slice its walk ends on
 extern "C" int plan(const zigma_scan_params_t *p, int *fields, const char **kernel) {
-    const ScanPlan top = plan_scan(*p);
-    ScanPlan s = top;
-    for (int b0 = 0; top.slice && b0 < p->batch && (b0 == 0 || s.family); b0 += top.slice) s = plan_scan(batch_slice(*p, b0, top.slice));
+    ScanPlan s;
+    for_each_scan_call(*p, [&s](const zigma_scan_params_t &, const ScanPlan &each) { s = each; return each.family ? int(ZIGMA_OK) : each.status; });
     fields[0] = s.status; fields[1] = s.family; fields[2] = s.info1;
     *kernel = s.kernel;
     return s.status;
@@ -644,19 +643,34 @@ def scan_plan():
     return plan
 
 
-def _split_ok(scan_plan, batch, d_inner, seqlen, chunk_len):
+def _split_dtp_block(batch, d_inner, seqlen, chunk_len):
+    """the scan block of the sequence split with dt_proj in its first pass (x, the delta workspace, dt_x / dt_w), on operands the in-kernel dt_proj
+    accepts at every size: bf16, dt_rank 40, 16 states, 72-wide x_dbl rows, every activation one broadcast row (pitch 0: no in-sample offset grows
+    with seqlen)"""
     from zigma_amd import _lib
     P = _lib.ScanParams()
-    P.batch, P.dim, P.seqlen, P.chunk_len = batch, d_inner, seqlen, chunk_len
-    return scan_plan.split_ok(P)
+    P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.chunk_len = batch, d_inner, seqlen, 16, 1, chunk_len
+    P.io_dtype = P.bc_dtype = _lib.BF16
+    P.delta_softplus, P.is_variable_B, P.is_variable_C = 1, 1, 1
+    for k, name in enumerate(("u", "delta", "z", "out_z")):
+        setattr(P, name, (k + 1) << 40), setattr(P, f"{name}_d_stride", 1)
+    for name, col in (("B", 40), ("C", 56)):
+        setattr(P, name, (5 << 40) + col * 2), setattr(P, f"{name}_l_stride", 72), setattr(P, f"{name}_dstate_stride", 1)
+    P.A, P.A_d_stride, P.A_dstate_stride, P.x = 6 << 40, 16, 1, 7 << 40
+    P.dt_x, P.dt_w, P.dt_rank, P.dt_x_l_stride, P.dt_w_row_stride = 5 << 40, 8 << 40, 40, 72, 40
+    return P
 
 
-def test_split_chunks_pass_the_c_side_split_limits(monkeypatch, scan_plan):
-    """split_chunk_len under the default knobs only returns chunks the C side's sequence split accepts, and split_limits_ok refuses
-    exactly what tok2_split_ok (scan_plan.h, compiled) refuses — including the chunks a raised SPLIT_MAX_WGS produces and more than 65535 chunks."""
+def test_split_chunks_pass_the_c_side_split_limits(monkeypatch, scan_plan, libpath):
+    """split_chunk_len under the default knobs only returns chunks the C side's sequence split accepts, and the library serves the split with dt_proj
+    inside (what plan_inner asks before it takes "in_split") exactly where tok2_split_ok (scan_plan.h, compiled) says yes — including the chunks a
+    raised SPLIT_MAX_WGS produces and more than 65535 chunks."""
     import zigma_amd.selective_scan_interface as ssi
+    from zigma_amd import _lib
     Ls = (16, 32, 48, 128, 240, 256, 272, 1008, 1024, 1040, 2048, 4080, 4096, 4112, 8192, 16384, 65552, 1 << 20)
     Dis = (64, 128, 640, 1280, 1536, 3072, 4096)
+    served = lambda b, di, L, c: _lib.plan("zigma_selective_scan_fwd", _split_dtp_block(b, di, L, c)) == (0, "scan_tok2_n16_split_dtproj")
+    split_ok = lambda b, di, L, c: scan_plan.split_ok(_split_dtp_block(b, di, L, c))
 
     def sweep():
         hits = []
@@ -665,28 +679,35 @@ def test_split_chunks_pass_the_c_side_split_limits(monkeypatch, scan_plan):
                 for L in Ls:
                     c = ssi.split_chunk_len(b, di, L)
                     if c:
-                        hits.append((b, di, L, c, ssi.split_limits_ok(b, di, L, c)))
+                        hits.append((b, di, L, c, served(b, di, L, c)))
         return hits
     hits = sweep()
     assert len(hits) > 1000 and all(ok for *_, ok in hits)
-    assert all(_split_ok(scan_plan, b, di, L, c) for b, di, L, c, _ in hits)
+    assert all(split_ok(b, di, L, c) for b, di, L, c, _ in hits)
     monkeypatch.setattr(ssi, "SPLIT_MAX_WGS", 1024)
     hits = sweep()
     refused = [h for h in hits if not h[4]]
     assert refused and all(b * (di // 64) >= 768 for b, di, *_ in refused)
-    assert all(ok == _split_ok(scan_plan, b, di, L, c) for b, di, L, c, ok in hits)
-    assert ssi.split_limits_ok(1, 64, 16 * 65535, 16) and not ssi.split_limits_ok(1, 64, 16 * 65536, 16)
-    assert not ssi.split_limits_ok(1, 64, 1024, 24) and not ssi.split_limits_ok(1, 64, 1024, 1024) and not ssi.split_limits_ok(1, 64, 1024, 0)
+    assert all(ok == split_ok(b, di, L, c) for b, di, L, c, ok in hits)
+    assert served(1, 64, 16 * 65535, 16) and not served(1, 64, 16 * 65536, 16)
+    assert not served(1, 64, 1024, 24) and not served(1, 64, 1024, 1024) and not served(1, 64, 1024, 0)
+    # ... and the same answers through the predicate plan_inner calls, on descriptors as it passes them
+    bf = torch.bfloat16
+    asks = lambda c, L=1024: ssi.dt_in_scan_eligible(_Dev(bf, 1, L, 64), _Dev(bf, 1, L, 72), _Dev(bf, 64, 40), dstate=16, chunk_len=c)
+    assert asks(32) and not asks(24) and not asks(1024) and asks(16, 16 * 65535) and not asks(16, 16 * 65536)
 
 
 @pytest.mark.parametrize("name", sorted(__import__("scan_plan_cases").CASES))
-def test_scan_plan_case_table(name, scan_plan):
-    """plan_scan() (compiled) on the parameter block scan_raw builds for every case of the table: status, family, info, last kernel"""
+def test_scan_plan_case_table(name, scan_plan, libpath):
+    """plan_scan() (compiled) on the parameter block scan_raw builds for every case of the table: status, family, info, last kernel; and the built
+    library's host-only query (zigma_selective_scan_fwd_plan, no device here) answers the same status and kernel"""
     import scan_plan_cases
+    from zigma_amd import _lib
     case, want = scan_plan_cases.CASES[name]
-    got = scan_plan_cases.call(case, "cpu", scan_plan)
+    got, asked = scan_plan_cases.call(case, "cpu", lambda P: (scan_plan(P), _lib.plan("zigma_selective_scan_fwd", P)))
     family = got["family"] or None
     assert (got["status"], family, (family, got["info1"]) if family else None, got["kernel"]) == tuple(want)
+    assert asked == (want.status, want.kernel)
 
 
 class _Dev:
@@ -719,7 +740,8 @@ def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
                             for rp in (0, 16, 24):
                                 for off in (0, 2):
                                     W, es = R + 2 * N, 2 if dt != torch.float32 else 4
-                                    u, x_dbl, z = _Dev(dt, B, L, Di), _Dev(dt, B, L, W, ptr=(1 << 24) + off * es), _Dev(dt, B, L, 2 * Di)
+                                    u, x_dbl = _Dev(dt, B, L, Di), _Dev(dt, B, L, W, ptr=(1 << 24) + off * es)
+                                    z = _Dev(dt, B, L, Di).pitched(L * 2 * Di, 2 * Di, 1)
                                     w = _Dev(dt, Di, R, ptr=1 << 28)
                                     P = _lib.ScanParams()
                                     P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.reset_period = B, Di, L, N, 1, rp
@@ -752,11 +774,10 @@ static int report(const FrontPlan &s, int *f, const char **kernel) {
     *kernel = s.kernel;
     return s.status;
 }
-// what the library reports for a call: the plan, or for a sliced batch the plan of the slice that runs last
+// what the library reports for a call: the plan, or for a sliced batch the plan of the slice its walk ends on
 extern "C" int plan_conv(const zigma_conv_params_t *p, int *f, const char **kernel) {
-    const FrontPlan top = plan_conv1d(*p);
-    FrontPlan s = top;
-    for (int b0 = 0; top.slice && b0 < p->batch && (b0 == 0 || s.kernel); b0 += top.slice) s = plan_conv1d(conv_slice(*p, b0, top.slice));
+    FrontPlan s;
+    for_each_conv_call(*p, [&s](const zigma_conv_params_t &, const FrontPlan &each) { s = each; return each.status; });
     return report(s, f, kernel);
 }
 extern "C" int plan_cx(const zigma_conv_xproj_params_t *p, int *f, const char **kernel) { return report(plan_conv_x_proj(*p), f, kernel); }
@@ -778,11 +799,13 @@ def front_plan():
 
 
 @pytest.mark.parametrize("name", sorted(__import__("front_plan_cases").CASES))
-def test_front_plan_case_table(name, front_plan):
-    """the four plans (compiled) on the parameter block the product's bindings build for every case of the table: status, last kernel"""
+def test_front_plan_case_table(name, front_plan, libpath):
+    """the four plans (compiled) on the parameter block the product's bindings build for every case of the table: status, last kernel; and the built
+    library's host-only queries (zigma_*_fwd_plan, no device here) answer the same"""
     import front_plan_cases
-    got, _ = front_plan_cases.call(name, "cpu", lambda fn, P: front_plan(P))
-    assert (got["status"], got["kernel"]) == tuple(front_plan_cases.CASES[name][2])
+    from zigma_amd import _lib
+    (got, asked), _ = front_plan_cases.call(name, "cpu", lambda fn, P: (front_plan(P), _lib.plan(fn, P)))
+    assert (got["status"], got["kernel"]) == tuple(front_plan_cases.CASES[name][2]) == asked
 
 
 def test_front_plan_geometry(front_plan):

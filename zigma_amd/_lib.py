@@ -194,7 +194,9 @@ EXPORTS = ("zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", 
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
            "zigma_cross_attn_bwd", "zigma_cross_attn_bwd_chunks", "zigma_patch_embed_fwd", "zigma_timestep_embed_fwd", "zigma_final_layer_fwd",
-           "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel")
+           "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel",
+           "zigma_selective_scan_fwd_plan", "zigma_causal_conv1d_fwd_plan", "zigma_conv_x_proj_fwd_plan", "zigma_x_proj_fwd_plan",
+           "zigma_dt_proj_softplus_fwd_plan")
 
 _lib = None
 
@@ -226,13 +228,18 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st)]
             fn.restype = C.c_int64
+        for name, st in (("zigma_selective_scan_fwd", ScanParams), ("zigma_causal_conv1d_fwd", ConvParams), ("zigma_conv_x_proj_fwd", ConvXProjParams),
+                         ("zigma_x_proj_fwd", XProjParams), ("zigma_dt_proj_softplus_fwd", DtProjParams)):
+            fn = getattr(L, name + "_plan")
+            fn.argtypes = [C.POINTER(st), C.POINTER(C.c_char_p)]
+            fn.restype = C.c_int
         L.zigma_cross_attn_bwd_chunks.argtypes = [C.c_int]
         L.zigma_cross_attn_bwd_chunks.restype = C.c_int
         L.zigma_strerror.argtypes = [C.c_int]
         L.zigma_strerror.restype = C.c_char_p
         L.zigma_abi_version.restype = C.c_int
         L.zigma_last_kernel.restype = C.c_char_p
-        if L.zigma_abi_version() != 10:
+        if L.zigma_abi_version() != 11:
             raise RuntimeError("zigma_amd: libzigma_hip.so ABI version mismatch")
         _lib = L
     return _lib
@@ -274,6 +281,16 @@ def workspace(fn_name, params, device):
     ws = torch.empty(max(int(nbytes), 16), device=device, dtype=torch.uint8)
     params.workspace, params.workspace_bytes = ws.data_ptr(), nbytes
     return ws
+
+
+def plan(fn_name, params):
+    """Ask the library what the entry point `fn_name` would do with this parameter block -> (status, kernel name or None): the status the launch
+    would return and what zigma_last_kernel() would report after it (None: a refusal or an empty call).  The five forward entry points of the Mamba
+    inner answer (plan_scan() of csrc/scan_plan.h, the plans of csrc/front_plan.h).  Host only: nothing is launched or dereferenced, so the block
+    may describe tensors that are yet to be allocated."""
+    kernel = C.c_char_p()
+    rc = getattr(lib(), fn_name + "_plan")(C.byref(params), C.byref(kernel))
+    return rc, kernel.value.decode() if kernel.value else None
 
 
 TRACE = None        # tests / tools: set to a list to receive (entry point, kernel that served it, parameter block) per call

@@ -10,9 +10,9 @@ import torch
 from . import _lib
 
 
-def causal_conv1d_raw(x, weight, bias, silu, *, out=None, x_row_index=None, reset_period=0):
-    """x, out: logical (batch, dim, seqlen) views, any strides.  weight (dim, width), bias (dim,) or None."""
-    dev = _lib.require_device(x, weight, bias, out, x_row_index)
+def conv_block(x, weight, bias, silu, out, x_row_index=None, reset_period=0):
+    """The parameter block of zigma_causal_conv1d_fwd from its operands (checked here).  Reads shapes, strides, dtypes and addresses only, so
+    a description of a tensor that is yet to be allocated serves as well as the tensor."""
     if x.dim() != 3:
         raise RuntimeError("x must be (batch, dim, seqlen)")
     batch, dim, L = x.shape
@@ -21,29 +21,34 @@ def causal_conv1d_raw(x, weight, bias, silu, *, out=None, x_row_index=None, rese
     width = weight.shape[1]
     if not 2 <= width <= 4:
         raise RuntimeError("causal_conv1d only supports width between 2 and 4")
-    if bias is not None:
-        if bias.dtype != weight.dtype or bias.shape != (dim,):
-            raise RuntimeError("bias must be (dim,) with the dtype of weight")
-        if bias.stride(0) != 1:
-            bias = bias.contiguous()
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.shape != x.shape or out.dtype != x.dtype:
+    if bias is not None and (bias.dtype != weight.dtype or tuple(bias.shape) != (dim,) or bias.stride(0) != 1):
+        raise RuntimeError("bias must be (dim,) with the dtype of weight")
+    if tuple(out.shape) != tuple(x.shape) or out.dtype != x.dtype:
         raise RuntimeError("out must match x")
     P = _lib.ConvParams()
     P.batch, P.dim, P.seqlen, P.width = batch, dim, L, width
     P.silu_activation = int(bool(silu))
     P.io_dtype, P.w_dtype, P.flags = _lib.dtype_id(x), _lib.dtype_id(weight), 0
-    P.x_batch_stride, P.x_c_stride, P.x_l_stride = x.stride()
-    P.weight_c_stride, P.weight_width_stride = weight.stride()
-    P.out_batch_stride, P.out_c_stride, P.out_l_stride = out.stride()
+    P.x_batch_stride, P.x_c_stride, P.x_l_stride = x.stride(0), x.stride(1), x.stride(2)
+    P.weight_c_stride, P.weight_width_stride = weight.stride(0), weight.stride(1)
+    P.out_batch_stride, P.out_c_stride, P.out_l_stride = out.stride(0), out.stride(1), out.stride(2)
     P.x, P.weight, P.bias, P.out = _lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out)
     if x_row_index is not None:
-        if x_row_index.dtype != torch.int32 or x_row_index.shape != (L,) or not x_row_index.is_contiguous():
+        if x_row_index.dtype != torch.int32 or tuple(x_row_index.shape) != (L,) or not x_row_index.is_contiguous():
             raise RuntimeError("x_row_index must be a contiguous int32 tensor of length seqlen")
         P.x_row_index = _lib.ptr(x_row_index)
     P.reset_period = int(reset_period)       # > 0: independent sequences of that many positions along seqlen
-    _lib.call("zigma_causal_conv1d_fwd", P, dev)
+    return P
+
+
+def causal_conv1d_raw(x, weight, bias, silu, *, out=None, x_row_index=None, reset_period=0):
+    """x, out: logical (batch, dim, seqlen) views, any strides.  weight (dim, width), bias (dim,) or None."""
+    dev = _lib.require_device(x, weight, bias, out, x_row_index)
+    if bias is not None and bias.dim() == 1 and bias.stride(0) != 1:
+        bias = bias.contiguous()
+    if out is None and x.dim() == 3:
+        out = torch.empty_like(x)
+    _lib.call("zigma_causal_conv1d_fwd", conv_block(x, weight, bias, silu, out, x_row_index, reset_period), dev)
     return out
 
 

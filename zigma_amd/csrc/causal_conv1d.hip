@@ -149,12 +149,9 @@ extern "C" int zigma_causal_conv1d_fwd(const zigma_conv_params_t *pp, void *stre
     (void)hipGetLastError();  // a stale error of an unrelated earlier call is not ours to report
     const zigma_conv_params_t &p = *pp;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const FrontPlan plan = plan_conv1d(p);
-    if (!plan.slice) return plan.kernel ? launch(p, plan, stream) : plan.status;
-    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
-        const zigma_conv_params_t q = conv_slice(p, b0, plan.slice);
-        const int rc = launch(q, plan_conv1d(q), stream);
-        if (rc != ZIGMA_OK) return rc;
-    }
-    return ZIGMA_OK;
+    return for_each_conv_call(p, [stream](const zigma_conv_params_t &q, const FrontPlan &plan) { return plan.kernel ? launch(q, plan, stream) : plan.status; });
+}
+
+extern "C" int zigma_causal_conv1d_fwd_plan(const zigma_conv_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_conv1d(*pp, kernel) : ZIGMA_ERR_NULL;
 }

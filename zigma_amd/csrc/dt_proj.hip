@@ -130,3 +130,7 @@ extern "C" int zigma_dt_proj_softplus_fwd(const zigma_dtproj_params_t *pp, void 
     set_last_kernel(plan.kernel);
     return check_launch();
 }
+
+extern "C" int zigma_dt_proj_softplus_fwd_plan(const zigma_dtproj_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_front(plan_dt_proj(*pp), kernel) : ZIGMA_ERR_NULL;
+}

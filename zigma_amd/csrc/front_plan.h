@@ -74,6 +74,35 @@ inline FrontPlan plan_conv1d(const zigma_conv_params_t &p) {
     return serve("conv_generic", 256);
 }
 
+// every planned call of a zigma_causal_conv1d_fwd block, in launch order: the block itself, or its batch slices one after the other.
+// each(q, plan) -> status; the first one that is not ZIGMA_OK ends the walk and is returned.  The launcher launches in it, the query reports.
+template <typename Each>
+inline int for_each_conv_call(const zigma_conv_params_t &p, Each each) {
+    const FrontPlan plan = plan_conv1d(p);
+    if (!plan.slice) return each(p, plan);
+    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
+        const zigma_conv_params_t q = conv_slice(p, b0, plan.slice);
+        const int rc = each(q, plan_conv1d(q));
+        if (rc != ZIGMA_OK) return rc;
+    }
+    return ZIGMA_OK;
+}
+
+// the zigma_*_fwd_plan queries: the launch's status and the kernel it would report (null: nothing would launch)
+inline int query_front(const FrontPlan &s, const char **kernel) {
+    *kernel = s.kernel;
+    return s.status;
+}
+inline int query_conv1d(const zigma_conv_params_t &p, const char **kernel) {
+    const char *last = nullptr;
+    const int rc = for_each_conv_call(p, [&last](const zigma_conv_params_t &, const FrontPlan &plan) {
+        if (plan.kernel) last = plan.kernel;
+        return plan.status;
+    });
+    *kernel = rc == ZIGMA_OK ? last : nullptr;
+    return rc;
+}
+
 // default: 4-wave workgroups (128 positions), two stages = 66 KB of LDS: two workgroups per CU that drift apart, one computing
 // while the other waits for its loads (measured 72 us; 8 waves in lockstep 75 us; a third stage does not pay, the second
 // workgroup does its job).  flags: 1 = three stages, 2 = eight-wave workgroups; probes (wrong results): 4 = no u stores,

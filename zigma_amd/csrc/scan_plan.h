@@ -152,4 +152,29 @@ inline ScanPlan plan_scan(const zigma_scan_params_t &p) {
     return serve(ZIGMA_SCAN_KERNEL_TOK, p.x && tok_split_ok(p) ? kScanSplit : kScanWhole, p.dstate == 16 ? "scan_tok_n16" : "scan_tok_n8");
 }
 
+// every planned call of a zigma_selective_scan_fwd block, in launch order: the block itself, or its batch slices one after the other.
+// each(q, plan) -> status; the first one that is not ZIGMA_OK ends the walk and is returned.  The launcher launches in it, the query reports.
+template <typename Each>
+inline int for_each_scan_call(const zigma_scan_params_t &p, Each each) {
+    const ScanPlan plan = plan_scan(p);
+    if (!plan.slice) return each(p, plan);
+    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
+        const zigma_scan_params_t q = batch_slice(p, b0, plan.slice);
+        const int rc = each(q, plan_scan(q));
+        if (rc != ZIGMA_OK) return rc;
+    }
+    return ZIGMA_OK;
+}
+
+// zigma_selective_scan_fwd_plan: the launch's status and, where every call is served, the kernel of the last one
+inline int query_scan(const zigma_scan_params_t &p, const char **kernel) {
+    const char *last = nullptr;
+    const int rc = for_each_scan_call(p, [&last](const zigma_scan_params_t &, const ScanPlan &plan) {
+        if (plan.family) last = plan.kernel;
+        return plan.family ? ZIGMA_OK : plan.status;
+    });
+    *kernel = rc == ZIGMA_OK ? last : nullptr;
+    return rc;
+}
+
 }  // namespace zigma

@@ -167,12 +167,9 @@ extern "C" int zigma_selective_scan_fwd(const zigma_scan_params_t *pp, void *str
     (void)hipGetLastError();  // a stale error of an unrelated earlier call is not ours to report
     const zigma_scan_params_t &p = *pp;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const ScanPlan plan = plan_scan(p);
-    if (!plan.slice) return launch(p, plan, stream);
-    for (int b0 = 0; b0 < p.batch; b0 += plan.slice) {
-        const zigma_scan_params_t q = batch_slice(p, b0, plan.slice);
-        const int rc = launch(q, plan_scan(q), stream);
-        if (rc != ZIGMA_OK) return rc;
-    }
-    return ZIGMA_OK;
+    return for_each_scan_call(p, [stream](const zigma_scan_params_t &q, const ScanPlan &plan) { return launch(q, plan, stream); });
+}
+
+extern "C" int zigma_selective_scan_fwd_plan(const zigma_scan_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_scan(*pp, kernel) : ZIGMA_ERR_NULL;
 }

@@ -163,3 +163,7 @@ extern "C" int zigma_x_proj_fwd(const zigma_xproj_params_t *pp, void *stream_) {
     set_last_kernel(plan.kernel);
     return check_launch();
 }
+
+extern "C" int zigma_x_proj_fwd_plan(const zigma_xproj_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_front(plan_x_proj(*pp), kernel) : ZIGMA_ERR_NULL;
+}

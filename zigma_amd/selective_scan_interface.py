@@ -12,6 +12,9 @@ plus `mamba_inner_tok`, the token-major fused form the ZigMa block uses on MI355
 the zigzag gather/scatter run on (B, L, C) activations straight out of / into the projection GEMMs,
 so none of the reference's transposes, `index_select`s or `cat`s exist.  `plan_inner` is the one place that chooses its kernels (conv +
 x_proj front, where dt_proj runs, the sequence split, the accumulating epilogue); `mamba_inner_tok` and `MambaInnerTokFn` carry the plan out.
+What a kernel takes is the library's to say: every binding here is a builder of its parameter block and a launch, and the eligibility predicates
+hand the block the launch would get to the library's host-only plan queries (`_lib.plan`: plan_scan() of csrc/scan_plan.h, the plans of
+csrc/front_plan.h).  Only what a block cannot say, and policy (where a kernel that would serve is not the one to take), is decided in Python.
 
 Backward: `scan_bwd_tok` binds zigma_selective_scan_bwd; `MambaInnerTokFn` is the autograd
 form of `mamba_inner_tok` (MambaInnerFn.backward, :367-434) that the blocks use when autograd is recording.  The
@@ -19,6 +22,8 @@ form of `mamba_inner_tok` (MambaInnerFn.backward, :367-434) that the blocks use 
 """
 
 from collections import namedtuple
+
+import math
 
 import torch
 import torch.nn.functional as F
@@ -60,10 +65,61 @@ def split_chunk_len(batch, d_inner, seqlen, reset_period=0):
     return chunk if -(-seqlen // chunk) >= 2 else 0
 
 
-def split_limits_ok(batch, d_inner, seqlen, chunk_len):
-    """The C side's limits of the sequence split (tok2_split_ok() of plan_scan(), csrc/scan_plan.h): < 768 workgroups, whole-tile chunks,
-    2 <= n_chunks <= 65535.  Every chunk split_chunk_len returns under the default knobs passes; SPLIT_MAX_WGS >= 768 (a probe setting) can break that."""
-    return chunk_len > 0 and chunk_len % 16 == 0 and batch * (d_inner // 64) < 768 and 2 <= -(-seqlen // chunk_len) <= 65535
+FRESH_ADDRESS = 1 << 40     # placeholder address of a tensor that is yet to be allocated (the k-th stand-in of a block: k times this)
+
+
+class _Desc:
+    """What the block builders read of a tensor (shape, strides, dtype, address), for the plan queries: of a tensor that exists (`of`), or of
+    contiguous rows the front is yet to allocate (`fresh`), with the views mamba_inner_tok takes of u and x_dbl.  A fresh tensor's address is a
+    placeholder — non-zero, on a page boundary (the caching allocator hands out blocks on 512-byte boundaries, the plans ask for 16 bytes at
+    most) and 1 TiB from the next one, so no two overlap.  A block built on placeholders is asked about; before one is launched, every address
+    in it is set from the real tensors (scan_planned)."""
+    __slots__ = ("dtype", "shape", "strides", "address", "is_cuda")
+
+    def __init__(self, dtype, shape, strides, address, is_cuda=True):
+        self.dtype, self.shape, self.strides, self.address, self.is_cuda = dtype, shape, strides, address, is_cuda
+
+    @classmethod
+    def of(cls, t):
+        if isinstance(t, cls):
+            return t
+        return cls(t.dtype, tuple(t.shape), tuple([t.stride(i) for i in range(t.dim())]), t.data_ptr(), t.is_cuda)
+
+    @classmethod
+    def fresh(cls, like, shape, k, dtype=None):
+        strides, n = [], 1
+        for d in reversed(shape):
+            strides.append(n)
+            n *= d
+        return cls(dtype or like.dtype, shape, tuple(reversed(strides)), k * FRESH_ADDRESS, like.is_cuda)
+
+    def stride(self, i):
+        return self.strides[i]
+
+    def dim(self):
+        return len(self.shape)
+
+    def data_ptr(self):
+        return self.address
+
+    def is_contiguous(self):
+        n = 1
+        for d, st in zip(reversed(self.shape), reversed(self.strides)):
+            if d != 1 and st != n:
+                return False
+            n *= d
+        return True
+
+    def scan_view(self):
+        """(B, L, C) rows as the scan's (batch, dim, seqlen) operand: t.transpose(1, 2)"""
+        (B, L, C), (sb, sl, sc) = self.shape, self.strides
+        return _Desc(self.dtype, (B, C, L), (sb, sc, sl), self.address, self.is_cuda)
+
+    def columns(self, first, n):
+        """columns [first, first + n) of (B, L, C) rows as the scan's (batch, 1, dstate, seqlen) B / C operand:
+        t[:, :, first:first + n].transpose(1, 2).unsqueeze(1)"""
+        (B, L, _), (sb, sl, sc) = self.shape, self.strides
+        return _Desc(self.dtype, (B, 1, n, L), (sb, n * sc, sc, sl), self.address + first * sc * self.dtype.itemsize, self.is_cuda)
 
 
 def _as_bgnl(M, name):
@@ -73,6 +129,137 @@ def _as_bgnl(M, name):
     if M.dim() != 4:
         raise RuntimeError(f"{name} must be (D, N), (B, N, L) or (B, G, N, L)")
     return M
+
+
+def _scan_flags(z_preactivated, accumulate, probe_flags=0):
+    return (_lib.SCAN_Z_PREACTIVATED if z_preactivated else 0) | (_lib.SCAN_ACCUMULATE if accumulate else 0) | int(probe_flags)
+
+
+def scan_block(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, *, out=None, out_z=None, x=None, z_row_index=None,
+               out_row_index=None, checkpoints=None, reset_period=0, chunk_len=2048, z_preactivated=False, _probe_flags=0, dt_x=None, dt_w=None,
+               accumulate=False):
+    """The parameter block of zigma_selective_scan_fwd from the operands of scan_raw (checked here; outputs as scan_raw allocates them).  Reads
+    shapes, strides, dtypes and addresses only, so a description of a tensor that is yet to be allocated (_Desc) serves as well as the tensor;
+    B / C that vary with the input come as (batch, groups, dstate, seqlen) then."""
+    if delta is None:
+        if dt_x is None or dt_w is None or not delta_softplus:
+            raise RuntimeError("delta=None needs dt_x, dt_w and delta_softplus=True")
+    elif dt_x is not None or dt_w is not None:
+        # (ABI 10) with the carry tensor x — the sequence split — delta is a WORKSPACE: the first pass forms softplus(dt_proj + bias) itself and
+        # writes it there for the second pass; without x the two are alternatives
+        if x is None or dt_x is None or dt_w is None or not delta_softplus:
+            raise RuntimeError("pass either delta or (dt_x, dt_w); both only with x (sequence split: delta is the workspace the first pass fills)")
+    shape = tuple(u.shape)
+    if len(shape) != 3 or (delta is not None and tuple(delta.shape) != shape):
+        raise RuntimeError("u and delta must both be (batch, dim, seqlen)")
+    if A.dtype.is_complex:
+        raise RuntimeError("zigma_amd: complex A is out of scope (ZigMa's A is real, mamba_simple.py:298)")
+    if A.dtype != torch.float32:
+        raise RuntimeError("A must be float32")
+    if delta is not None and delta.dtype != u.dtype:
+        raise RuntimeError("delta must have the dtype of u")
+    batch, dim, L = shape
+    N = A.shape[1]
+    if A.shape[0] != dim:
+        raise RuntimeError("A must be (dim, dstate)")
+    if N > 256:
+        raise RuntimeError("selective_scan only supports state dimension <= 256")
+    if accumulate and (dt_x is None or out_z is None):
+        raise RuntimeError("accumulate=True is served by the in-kernel dt_proj form only (dt_x / dt_w) and needs the out_z to add to")
+    var_b, var_c = B.dim() >= 3, C.dim() >= 3
+    P = _lib.ScanParams()
+    P.batch, P.dim, P.seqlen, P.dstate = batch, dim, L, N
+    P.delta_softplus, P.io_dtype = int(bool(delta_softplus)), _lib.dtype_id(u)
+    P.chunk_len, P.flags = int(chunk_len), _scan_flags(z_preactivated, accumulate, _probe_flags)
+    P.is_variable_B, P.is_variable_C = int(var_b), int(var_c)
+    P.reset_period = int(reset_period)       # > 0: independent sequences of that many steps along seqlen
+    groups, bc = {}, None
+    for name, M, var in (("B", B, var_b), ("C", C, var_c)):
+        if var:
+            if M.dim() != 4:
+                raise RuntimeError(f"{name} must be (D, N), (B, N, L) or (B, G, N, L)")
+            if M.shape[0] != batch or M.shape[2] != N or M.shape[3] != L:
+                raise RuntimeError(f"{name} must be (batch, groups, dstate, seqlen)")
+            groups[name] = M.shape[1]
+            if bc is not None and M.dtype != bc.dtype:
+                raise RuntimeError("variable B and C must share a dtype")
+            bc = M
+        elif tuple(M.shape) != (dim, N) or M.dtype != torch.float32:
+            raise RuntimeError(f"constant {name} must be float32 (dim, dstate)")
+    if var_b:
+        P.B_batch_stride, P.B_group_stride, P.B_dstate_stride, P.B_l_stride = B.stride(0), B.stride(1), B.stride(2), B.stride(3)
+    else:
+        P.B_d_stride, P.B_dstate_stride = B.stride(0), B.stride(1)
+    if var_c:
+        P.C_batch_stride, P.C_group_stride, P.C_dstate_stride, P.C_l_stride = C.stride(0), C.stride(1), C.stride(2), C.stride(3)
+    else:
+        P.C_d_stride, P.C_dstate_stride = C.stride(0), C.stride(1)
+    if var_b and var_c and groups["B"] != groups["C"]:
+        raise RuntimeError("B and C must have the same number of groups")
+    P.n_groups = groups.get("C", groups.get("B", 1))
+    if dim % P.n_groups != 0:
+        raise RuntimeError("dim must be divisible by the number of B/C groups")
+    P.bc_dtype = _lib.dtype_id(u if bc is None else bc)
+    for name, t in (("z", z), ("out", out), ("out_z", out_z)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != u.dtype):
+            raise RuntimeError(f"{name} must match u in shape and dtype")
+    P.u_batch_stride, P.u_d_stride, P.u_l_stride = u.stride(0), u.stride(1), u.stride(2)
+    if delta is not None:
+        P.delta_batch_stride, P.delta_d_stride, P.delta_l_stride = delta.stride(0), delta.stride(1), delta.stride(2)
+    if z is not None:
+        P.z_batch_stride, P.z_d_stride, P.z_l_stride = z.stride(0), z.stride(1), z.stride(2)
+    if out is not None:
+        P.out_batch_stride, P.out_d_stride, P.out_l_stride = out.stride(0), out.stride(1), out.stride(2)
+    if out_z is not None:
+        P.out_z_batch_stride, P.out_z_d_stride, P.out_z_l_stride = out_z.stride(0), out_z.stride(1), out_z.stride(2)
+    if x is not None:
+        n_chunks = (L + int(chunk_len) - 1) // int(chunk_len)
+        if tuple(x.shape) != (batch, dim, n_chunks, 2 * N) or x.dtype != torch.float32 or not x.is_contiguous():
+            raise RuntimeError("x must be contiguous float32 (batch, dim, n_chunks, 2*dstate)")
+    if dt_x is not None:
+        if (dt_x.dim() != 3 or dt_x.shape[0] != batch or dt_x.shape[1] != L or dt_x.dtype != u.dtype or dt_x.stride(2) != 1
+                or dt_w.dim() != 2 or dt_w.shape[0] != dim or dt_w.dtype != u.dtype or dt_w.stride(1) != 1 or dt_x.shape[2] < dt_w.shape[1]):
+            raise RuntimeError("dt_x must be (batch, seqlen, >= dt_rank) rows and dt_w (dim, dt_rank), both in the dtype of u")
+        P.dt_rank, P.dt_x_batch_stride, P.dt_x_l_stride, P.dt_w_row_stride = dt_w.shape[1], dt_x.stride(0), dt_x.stride(1), dt_w.stride(0)
+    return _scan_addresses(P, u, delta, A, B, C, D, z, delta_bias, out, out_z, x, z_row_index, out_row_index, checkpoints, dt_x, dt_w)
+
+
+def _scan_addresses(P, u, delta, A, B, C, D, z, delta_bias, out, out_z, x, z_row_index, out_row_index, checkpoints, dt_x, dt_w):
+    """every address of a scan block (scan_block ends with it)"""
+    P.u, P.delta, P.z, P.out, P.out_z = _lib.ptr(u), _lib.ptr(delta), _lib.ptr(z), _lib.ptr(out), _lib.ptr(out_z)
+    P.B, P.C, P.x, P.dt_x, P.dt_w = _lib.ptr(B), _lib.ptr(C), _lib.ptr(x), _lib.ptr(dt_x), _lib.ptr(dt_w)
+    return _scan_side_operands(P, A, D, delta_bias, z_row_index, out_row_index, checkpoints)
+
+
+def _scan_side_operands(P, A, D, delta_bias, z_row_index, out_row_index, checkpoints=None):
+    """the operands a scan block holds little but the address of, checked and set: A with its two strides, D, delta_bias, the row tables, the
+    checkpoints.  (The dt decision builds its block without them: scan_planned sets them.)"""
+    for v, name in ((D, "D"), (delta_bias, "delta_bias")):
+        if v is not None and (v.dtype != torch.float32 or tuple(v.shape) != (P.dim,) or v.stride(0) != 1):
+            raise RuntimeError(f"{name} must be contiguous float32 (dim,)")
+    for idx, name in ((z_row_index, "z_row_index"), (out_row_index, "out_row_index")):
+        if idx is not None and (idx.dtype != torch.int32 or tuple(idx.shape) != (P.seqlen,) or not idx.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous int32 tensor of length seqlen")
+    if checkpoints is not None and (checkpoints.dtype != torch.float32 or not checkpoints.is_contiguous()):
+        raise RuntimeError("checkpoints must be a contiguous float32 buffer")
+    P.A, P.A_d_stride, P.A_dstate_stride = _lib.ptr(A), A.stride(0), A.stride(1)
+    P.D, P.delta_bias, P.z_row_index, P.out_row_index = _lib.ptr(D), _lib.ptr(delta_bias), _lib.ptr(z_row_index), _lib.ptr(out_row_index)
+    P.checkpoints = _lib.ptr(checkpoints)
+    return P
+
+
+def scan_planned(P, u, x_dbl, delta, xc, y, z, A, D, delta_bias, z_row_index, out_row_index, z_preactivated, accumulate):
+    """Launch the scan block plan_inner's dt decision built and the library accepted (dt_in_scan_eligible(keep=)): the block of the in-kernel
+    dt_proj call on u, x_dbl (dt_x; B and C its columns behind dt_rank), the gate z and the result y (all (B, L, .) rows), with delta and xc the
+    split's workspace and carries or None.  Layout, sizes, reset_period and chunk_len stand as planned; the addresses — placeholders where the
+    tensor was yet to be allocated —, the side operands and the flags are set here.  The caller passes tensors of the planned layout: fresh
+    contiguous u, x_dbl, delta, xc; z and y as the decision saw them (y: fresh rows where it saw none)."""
+    dev = _lib.require_device(u, x_dbl, delta, xc, y, z, A, D, delta_bias, z_row_index, out_row_index)
+    es, rows = u.element_size(), x_dbl.data_ptr()
+    P.u, P.delta, P.z, P.out_z, P.x = u.data_ptr(), _lib.ptr(delta), z.data_ptr(), y.data_ptr(), _lib.ptr(xc)
+    P.dt_x, P.B, P.C = rows, rows + P.dt_rank * es, rows + (P.dt_rank + P.dstate) * es
+    P.flags = _scan_flags(z_preactivated, accumulate)
+    _lib.call("zigma_selective_scan_fwd", _scan_side_operands(P, A, D, delta_bias, z_row_index, out_row_index), dev)
 
 
 def scan_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, *, out=None, out_z=None,
@@ -88,115 +275,15 @@ def scan_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
     dt_x, dt_w AND delta AND x (ABI 10): the sequence split with dt_proj inside its first pass — delta (uninitialised, shape of u) receives the step sizes.
     accumulate (with dt_x / dt_w only): out_z += y * silu(z) — the second sweep of `v2` adds itself to the first one's result (ZIGMA_SCAN_ACCUMULATE)."""
     dev = _lib.require_device(u, delta, A, B, C, D, z, delta_bias, out, out_z, x, z_row_index, out_row_index, dt_x, dt_w)
-    if delta is None:
-        if dt_x is None or dt_w is None or not delta_softplus:
-            raise RuntimeError("delta=None needs dt_x, dt_w and delta_softplus=True")
-    elif dt_x is not None or dt_w is not None:
-        # (ABI 10) with the carry tensor x — the sequence split — delta is a WORKSPACE: the first pass forms softplus(dt_proj + bias) itself and
-        # writes it there for the second pass; without x the two are alternatives
-        if x is None or dt_x is None or dt_w is None or not delta_softplus:
-            raise RuntimeError("pass either delta or (dt_x, dt_w); both only with x (sequence split: delta is the workspace the first pass fills)")
-    if u.dim() != 3 or (delta is not None and delta.shape != u.shape):
-        raise RuntimeError("u and delta must both be (batch, dim, seqlen)")
-    if A.is_complex():
-        raise RuntimeError("zigma_amd: complex A is out of scope (ZigMa's A is real, mamba_simple.py:298)")
-    if A.dtype != torch.float32:
-        raise RuntimeError("A must be float32")
-    if delta is not None and delta.dtype != u.dtype:
-        raise RuntimeError("delta must have the dtype of u")
-    batch, dim, L = u.shape
-    N = A.shape[1]
-    if A.shape[0] != dim:
-        raise RuntimeError("A must be (dim, dstate)")
-    if N > 256:
-        raise RuntimeError("selective_scan only supports state dimension <= 256")
-    var_b, var_c = B.dim() >= 3, C.dim() >= 3
-    P = _lib.ScanParams()
-    P.batch, P.dim, P.seqlen, P.dstate = batch, dim, L, N
-    P.delta_softplus = int(bool(delta_softplus))
-    P.io_dtype = _lib.dtype_id(u)
-    if accumulate and (dt_x is None or out_z is None):
-        raise RuntimeError("accumulate=True is served by the in-kernel dt_proj form only (dt_x / dt_w) and needs the out_z to add to")
-    P.chunk_len, P.flags = int(chunk_len), (_lib.SCAN_Z_PREACTIVATED if z_preactivated else 0) | (_lib.SCAN_ACCUMULATE if accumulate else 0) | int(_probe_flags)
-    P.is_variable_B, P.is_variable_C = int(var_b), int(var_c)
-    groups = 1
-    bc_dt = None
-    for name, M, var in (("B", B, var_b), ("C", C, var_c)):
-        if var:
-            M = _as_bgnl(M, name)
-            if M.shape[0] != batch or M.shape[2] != N or M.shape[3] != L:
-                raise RuntimeError(f"{name} must be (batch, groups, dstate, seqlen)")
-            groups = M.shape[1]
-            if bc_dt is not None and M.dtype != bc_dt:
-                raise RuntimeError("variable B and C must share a dtype")
-            bc_dt = M.dtype
-            sb, sg, sn, sl = M.stride()
-            setattr(P, f"{name}_batch_stride", sb), setattr(P, f"{name}_group_stride", sg)
-            setattr(P, f"{name}_dstate_stride", sn), setattr(P, f"{name}_l_stride", sl)
-        else:
-            if M.shape != (dim, N) or M.dtype != torch.float32:
-                raise RuntimeError(f"constant {name} must be float32 (dim, dstate)")
-            setattr(P, f"{name}_d_stride", M.stride(0)), setattr(P, f"{name}_dstate_stride", M.stride(1))
-        setattr(P, name, _lib.ptr(M))
-        if name == "B":
-            Bk = M
-        else:
-            Ck = M
-    if var_b and var_c and _as_bgnl(B, "B").shape[1] != _as_bgnl(C, "C").shape[1]:
-        raise RuntimeError("B and C must have the same number of groups")
-    if dim % groups != 0:
-        raise RuntimeError("dim must be divisible by the number of B/C groups")
-    P.n_groups = groups
-    P.bc_dtype = _lib.dtype_id(Bk if var_b else (Ck if var_c else u))
-    for name, v in (("D", D), ("delta_bias", delta_bias)):
-        if v is not None:
-            if v.dtype != torch.float32 or v.shape != (dim,):
-                raise RuntimeError(f"{name} must be float32 (dim,)")
-            if v.stride(0) != 1:
-                v = v.contiguous()
-            setattr(P, name, _lib.ptr(v))
-            if name == "D":
-                D = v
-            else:
-                delta_bias = v
-    if z is not None:
-        if z.shape != u.shape or z.dtype != u.dtype:
-            raise RuntimeError("z must match u")
-        if out_z is None:
-            out_z = torch.empty_like(z)
+    B, C = (_as_bgnl(M, name) if M.dim() >= 3 else M for M, name in ((B, "B"), (C, "C")))
+    D, delta_bias = (v.contiguous() if v is not None and v.dim() == 1 and v.stride(0) != 1 else v for v in (D, delta_bias))
+    if z is not None and out_z is None:
+        out_z = torch.empty_like(z)
     if out is None and (want_out or z is None):
         out = torch.empty_like(delta if delta is not None else u)
-    for name, t in (("u", u), ("delta", delta), ("z", z), ("out", out), ("out_z", out_z)):
-        if t is None:
-            continue
-        if t.shape != u.shape or t.dtype != u.dtype:
-            raise RuntimeError(f"{name} must match u in shape and dtype")
-        sb, sd, sl = t.stride()
-        setattr(P, name, _lib.ptr(t))
-        setattr(P, f"{name}_batch_stride", sb), setattr(P, f"{name}_d_stride", sd), setattr(P, f"{name}_l_stride", sl)
-    P.A = _lib.ptr(A)
-    P.A_d_stride, P.A_dstate_stride = A.stride()
-    if x is not None:
-        n_chunks = (L + int(chunk_len) - 1) // int(chunk_len)
-        if x.shape != (batch, dim, n_chunks, 2 * N) or x.dtype != torch.float32 or not x.is_contiguous():
-            raise RuntimeError("x must be contiguous float32 (batch, dim, n_chunks, 2*dstate)")
-        P.x = _lib.ptr(x)
-    for name, idx in (("z_row_index", z_row_index), ("out_row_index", out_row_index)):
-        if idx is not None:
-            if idx.dtype != torch.int32 or idx.shape != (L,) or not idx.is_contiguous():
-                raise RuntimeError(f"{name} must be a contiguous int32 tensor of length seqlen")
-            setattr(P, name, _lib.ptr(idx))
-    if checkpoints is not None:
-        if checkpoints.dtype != torch.float32 or not checkpoints.is_contiguous():
-            raise RuntimeError("checkpoints must be a contiguous float32 buffer")
-        P.checkpoints = _lib.ptr(checkpoints)
-    if dt_x is not None:
-        if (dt_x.dim() != 3 or dt_x.shape[0] != batch or dt_x.shape[1] != L or dt_x.dtype != u.dtype or dt_x.stride(2) != 1
-                or dt_w.dim() != 2 or dt_w.shape[0] != dim or dt_w.dtype != u.dtype or dt_w.stride(1) != 1 or dt_x.shape[2] < dt_w.shape[1]):
-            raise RuntimeError("dt_x must be (batch, seqlen, >= dt_rank) rows and dt_w (dim, dt_rank), both in the dtype of u")
-        P.dt_x, P.dt_w, P.dt_rank = _lib.ptr(dt_x), _lib.ptr(dt_w), dt_w.shape[1]
-        P.dt_x_batch_stride, P.dt_x_l_stride, P.dt_w_row_stride = dt_x.stride(0), dt_x.stride(1), dt_w.stride(0)
-    P.reset_period = int(reset_period)       # > 0: independent sequences of that many steps along seqlen
+    P = scan_block(u, delta, A, B, C, D, z, delta_bias, delta_softplus, out=out, out_z=out_z, x=x, z_row_index=z_row_index,
+                   out_row_index=out_row_index, checkpoints=checkpoints, reset_period=reset_period, chunk_len=chunk_len,
+                   z_preactivated=z_preactivated, _probe_flags=_probe_flags, dt_x=dt_x, dt_w=dt_w, accumulate=accumulate)
     status = (_lib.C.c_int32 * 2)(0, 0)
     P.info = status                          # host out-field: which kernel family ran, whether it writes the checkpoints
     _lib.call("zigma_selective_scan_fwd", P, dev)
@@ -205,18 +292,33 @@ def scan_raw(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=
     return out, out_z
 
 
+def _served(fn_name, block, *kernels):
+    """the library's plan serves this block with one of these kernels (a name ending in * stands for every kernel that begins so)"""
+    status, kernel = _lib.plan(fn_name, block)
+    return status == 0 and kernel is not None and any(kernel.startswith(k[:-1]) if k.endswith("*") else kernel == k for k in kernels)
+
+
+def x_proj_block(u, weight, out):
+    """the parameter block of zigma_x_proj_fwd: u (..., k) rows one pitch apart, weight (n, k), out (..., n)"""
+    P = _lib.XProjParams()
+    P.m, P.n, P.k, P.dtype, P.flags = math.prod(u.shape[:-1]), weight.shape[0], u.shape[-1], _lib.dtype_id(u), 0
+    P.x_row_stride, P.w_row_stride, P.out_row_stride = u.stride(-2), weight.stride(0), out.stride(-2)
+    P.x, P.w, P.out = _lib.ptr(u), _lib.ptr(weight), _lib.ptr(out)
+    return P
+
+
 def x_proj_eligible(u, weight):
-    """limits of zigma_x_proj_fwd, restating plan_x_proj() (csrc/front_plan.h): bf16 or fp16 (u and weight alike), n <= 96, k % 256 == 0, rows a multiple of
-    8 elements apart on 16-byte boundaries.  From 16 384 tokens on a workgroup streams 256 token rows over the whole K; below, K is split over the waves of
-    32-token workgroups (x_proj_splitk_kernel, round 5: the streaming form was 32 workgroups and 31 us at 8192 tokens against 21 for the library),
-    which needs k <= 1536.  tests/test_host_cpu.py sweeps the predicate against the compiled plan."""
-    tokens = u.numel() // u.shape[-1]
-    return (u.is_cuda and u.dtype in (torch.bfloat16, torch.float16) and weight.dtype == u.dtype
-            and u.is_contiguous()                                                   # policy: the plan takes any row pitch % 8 == 0
-            and (tokens >= 16384 or (tokens >= 256                                  # policy: below 256 tokens the library GEMM is kept
-                                     and weight.shape[1] <= 1536))                  # policy: few tokens only on the split-K form, never the streaming one
-            and 1 <= weight.shape[0] <= 96 and weight.shape[1] % 256 == 0 and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
-            and u.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
+    """zigma_x_proj_fwd takes u @ weight.T: what plan_x_proj() (csrc/front_plan.h) serves, asked through the library, and on top of it
+    - the device, one dtype for both operands and contiguous weight columns (the block has one dtype and row pitches only);
+    - policy: contiguous u (the plan takes any row pitch it can load);
+    - policy: from 16 384 tokens on, where a workgroup streams 256 token rows over the whole K; below, from 256 tokens on (fewer stay with the
+      library GEMM) and only where the plan takes the split-K form (x_proj_splitk_kernel, round 5: the streaming form was 32 workgroups and
+      31 us at 8192 tokens against 21 for the library)."""
+    tokens = math.prod(u.shape[:-1])
+    if not (u.is_cuda and weight.dtype == u.dtype and weight.stride(1) == 1 and u.is_contiguous() and tokens >= 256):
+        return False
+    out = _Desc.fresh(u, (tokens, weight.shape[0]), 1)
+    return _served("zigma_x_proj_fwd", x_proj_block(u, weight, out), "x_proj_mfma" if tokens >= 16384 else "x_proj_splitk")
 
 
 def x_proj(u, weight):
@@ -226,32 +328,42 @@ def x_proj(u, weight):
     u2 = u.reshape(-1, K)
     n = weight.shape[0]
     out = torch.empty(u2.shape[0], n, device=u.device, dtype=u.dtype)
-    P = _lib.XProjParams()
-    P.m, P.n, P.k, P.dtype, P.flags = u2.shape[0], n, K, _lib.dtype_id(u), 0
-    P.x_row_stride, P.w_row_stride, P.out_row_stride = u2.stride(0), weight.stride(0), out.stride(0)
-    P.x, P.w, P.out = _lib.ptr(u2), _lib.ptr(weight), _lib.ptr(out)
-    _lib.call("zigma_x_proj_fwd", P, dev)
+    _lib.call("zigma_x_proj_fwd", x_proj_block(u2, weight, out), dev)
     return out.reshape(*lead, n)
 
 
+def conv_x_proj_block(x_half, conv_w, conv_b, x_proj_weight, perm, u, x_dbl, _flags=0):
+    """the parameter block of zigma_conv_x_proj_fwd: x_half (B, L, d_inner) rows, contiguous (d_inner, 4) taps and bias, x_proj_weight (n, d_inner),
+    a contiguous int32 row table or None; u (B, L, d_inner) and x_dbl (B, L, n) receive the results"""
+    P = _lib.ConvXProjParams()
+    P.batch, P.seqlen, P.dim = x_half.shape
+    P.n, P.dtype, P.flags = x_proj_weight.shape[0], _lib.dtype_id(x_half), _flags
+    P.x_batch_stride, P.x_l_stride = x_half.stride(0), x_half.stride(1)
+    P.u_batch_stride, P.u_l_stride = u.stride(0), u.stride(1)
+    P.w_row_stride, P.out_row_stride = x_proj_weight.stride(0), x_dbl.stride(1)
+    P.x, P.conv_weight, P.conv_bias, P.w = _lib.ptr(x_half), _lib.ptr(conv_w), _lib.ptr(conv_b), _lib.ptr(x_proj_weight)
+    P.u, P.out, P.x_row_index = _lib.ptr(u), _lib.ptr(x_dbl), _lib.ptr(perm)
+    return P
+
+
 def conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_weight, perm, reset_period=0):
-    """limits of zigma_conv_x_proj_fwd, restating plan_conv_x_proj() (csrc/front_plan.h): bf16 or fp16 (all four operands alike), width-4 taps as
-    contiguous (d_inner, 4), a bias, seqlen % 32 == 0, batch * seqlen % 256 == 0, d_inner % 64 == 0, n <= 96 and % 8 == 0, rows a multiple of 8 elements
-    apart on 16-byte boundaries, one sequence per batch row (the entry point has no reset_period).  tests/test_host_cpu.py sweeps the predicate
-    against the compiled plan."""
+    """zigma_conv_x_proj_fwd takes the front in one kernel: what plan_conv_x_proj() (csrc/front_plan.h) serves, asked through the library, and on
+    top of it
+    - the device, a bias, one sequence per batch row (the entry point has neither a bias-free form nor a reset_period);
+    - what the block cannot say: one dtype for all four operands, width-4 taps, taps / bias / row table contiguous (it carries no pitch for them),
+      contiguous channels and weight columns, an int32 row table;
+    - policy: at least CONV_X_PROJ_MIN_POSITIONS positions."""
     if conv_b is None or reset_period or not x_half.is_cuda:
         return False
     Bsz, L, Di = x_half.shape
-    return (x_half.dtype in (torch.bfloat16, torch.float16) and conv_w.dtype == x_half.dtype and conv_b.dtype == x_half.dtype
-            and x_proj_weight.dtype == x_half.dtype and conv_w.shape == (Di, 4)
-            and conv_w.is_contiguous() and conv_b.is_contiguous()                   # (the parameter block carries no pitch for them)
-            and L % 32 == 0 and (Bsz * L) % 256 == 0 and Di % 64 == 0
-            and Bsz * L >= CONV_X_PROJ_MIN_POSITIONS                                # policy: fewer than ~64 workgroups of 256 positions leave the chip idle
-            and 1 <= x_proj_weight.shape[0] <= 96 and x_proj_weight.shape[0] % 8 == 0
-            and x_half.stride(2) == 1 and x_half.stride(1) % 8 == 0 and x_half.stride(0) % 8 == 0
-            and x_proj_weight.stride(1) == 1 and x_proj_weight.stride(0) % 8 == 0
-            and all(t.data_ptr() % 16 == 0 for t in (x_half, conv_w, conv_b, x_proj_weight))
-            and (perm is None or (perm.dtype == torch.int32 and perm.is_contiguous())))
+    if not (conv_w.dtype == x_half.dtype and conv_b.dtype == x_half.dtype and x_proj_weight.dtype == x_half.dtype
+            and tuple(conv_w.shape) == (Di, 4) and conv_w.is_contiguous() and conv_b.is_contiguous()
+            and x_half.stride(2) == 1 and x_proj_weight.stride(1) == 1
+            and (perm is None or (perm.dtype == torch.int32 and perm.is_contiguous()))
+            and Bsz * L >= CONV_X_PROJ_MIN_POSITIONS):                              # policy: fewer than ~64 workgroups of 256 positions leave the chip idle
+        return False
+    u, x_dbl = _Desc.fresh(x_half, (Bsz, L, Di), 1), _Desc.fresh(x_half, (Bsz, L, x_proj_weight.shape[0]), 2)
+    return _served("zigma_conv_x_proj_fwd", conv_x_proj_block(x_half, conv_w, conv_b, x_proj_weight, perm, u, x_dbl), "conv_x_proj_mfma")
 
 
 def conv_x_proj(x_half, conv_w, conv_b, x_proj_weight, perm=None, _flags=0):
@@ -261,50 +373,61 @@ def conv_x_proj(x_half, conv_w, conv_b, x_proj_weight, perm=None, _flags=0):
     selective_scan_interface.py:307-322."""
     dev = _lib.require_device(x_half, conv_w, conv_b, x_proj_weight, perm)
     Bsz, L, Di = x_half.shape
-    n = x_proj_weight.shape[0]
     u = torch.empty(Bsz, L, Di, device=x_half.device, dtype=x_half.dtype)
-    x_dbl = torch.empty(Bsz, L, n, device=x_half.device, dtype=x_half.dtype)
-    P = _lib.ConvXProjParams()
-    P.batch, P.seqlen, P.dim, P.n, P.dtype, P.flags = Bsz, L, Di, n, _lib.dtype_id(x_half), _flags
-    P.x_batch_stride, P.x_l_stride = x_half.stride(0), x_half.stride(1)
-    P.u_batch_stride, P.u_l_stride = u.stride(0), u.stride(1)
-    P.w_row_stride, P.out_row_stride = x_proj_weight.stride(0), n
-    P.x, P.conv_weight, P.conv_bias, P.w = _lib.ptr(x_half), _lib.ptr(conv_w), _lib.ptr(conv_b), _lib.ptr(x_proj_weight)
-    P.u, P.out, P.x_row_index = _lib.ptr(u), _lib.ptr(x_dbl), _lib.ptr(perm)
-    _lib.call("zigma_conv_x_proj_fwd", P, dev)
+    x_dbl = torch.empty(Bsz, L, x_proj_weight.shape[0], device=x_half.device, dtype=x_half.dtype)
+    _lib.call("zigma_conv_x_proj_fwd", conv_x_proj_block(x_half, conv_w, conv_b, x_proj_weight, perm, u, x_dbl, _flags), dev)
     return u, x_dbl
 
 
-def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z=None):
-    """limits of the in-kernel dt_proj of scan_tok2_kernel (zigma_scan_params_t.dt_x), mirroring the whole-sequence dt_proj form of plan_scan()
-    (csrc/scan_plan.h: tok_layout_ok(), tok2_layout_ok(), tok2_dt_operands_ok()): bf16 / fp16, whole-sequence mode of the hot kernel (dstate == 16, seqlen % 16 == 0, d_inner % 64 == 0; reset_period a
-    multiple of 16 — the video temporal layers, round 6), 32 <= dt_rank <= 64 and % 8 == 0, x_dbl rows >= 64 wide on 16-byte boundaries, channel-contiguous u / z, and every
-    in-sample offset (seqlen * row stride, in bytes of up to 4-byte elements) below 2^31 / 4.  A caller that gets False keeps the
-    dt_proj kernel (or F.linear) + the ordinary scan call, which serves every shape the reference does."""
+def dt_in_scan_eligible(u, x_dbl, weight, reset_period=0, out=None, dstate=16, z=None, *, chunk_len=0, keep=None):
+    """scan_tok2_kernel takes dt_proj + softplus into the scan (zigma_scan_params_t.dt_x): what plan_scan() (csrc/scan_plan.h) serves with a
+    scan_tok2_n16_dtproj* kernel — chunk_len > 0: with scan_tok2_n16_split_dtproj, the sequence split of that chunk length, whose first pass
+    writes delta — asked through the library on the block mamba_inner_tok launches: u (B, L, d_inner) and x_dbl (B, L, >= dt_rank + 2 * dstate)
+    rows, B / C columns of x_dbl, the gate z and the result `out` as given or fresh rows like u.  A caller that gets False keeps the dt_proj
+    kernel (or F.linear) + the ordinary scan call, which serves every shape the reference does.  On top of the plan: the device, one dtype for
+    u, x_dbl and weight, contiguous weight columns and x_dbl rows (the block has one dtype and pitches only), and x_dbl wide enough to hold B and C.
+    keep: a dict that receives the served block as keep["scan"], for scan_planned to launch."""
     R = weight.shape[1]
-    if not (u.is_cuda and u.dtype in (torch.bfloat16, torch.float16) and x_dbl.dtype == u.dtype and weight.dtype == u.dtype and reset_period >= 0 and reset_period % 16 == 0
-            and dstate == 16 and u.dim() == 3 and x_dbl.dim() == 3
-            and 32 <= R <= 64 and R % 8 == 0 and u.shape[1] % 16 == 0 and u.shape[2] % 64 == 0 and x_dbl.shape[2] >= 64 and x_dbl.shape[2] >= R + 2 * dstate
-            and u.stride(2) == 1 and x_dbl.stride(2) == 1 and x_dbl.stride(1) % 8 == 0 and x_dbl.stride(0) % 8 == 0 and x_dbl.stride(1) >= 64
-            and weight.stride(1) == 1 and weight.stride(0) % 8 == 0
-            and x_dbl.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0 and u.shape[0] <= 65535):
+    if not (u.is_cuda and x_dbl.dtype == u.dtype and weight.dtype == u.dtype and u.dim() == 3 and x_dbl.dim() == 3
+            and x_dbl.shape[2] >= R + 2 * dstate and x_dbl.stride(2) == 1 and weight.stride(1) == 1):
         return False
-    L, lim = u.shape[1], ((1 << 31) - 1) // 4
-    rows = [u.stride(1), x_dbl.stride(1)] + ([z.stride(1)] if z is not None else []) + ([out.stride(1)] if out is not None else [])
-    if z is not None and z.stride(2) != 1:
-        return False
-    return all(0 <= s and s * L <= lim for s in rows)
+    Bsz, L, Di = u.shape
+    u, x_dbl = _Desc.of(u), _Desc.of(x_dbl)
+    z, y = (_Desc.fresh(u, u.shape, k) if t is None else _Desc.of(t) for t, k in ((z, 1), (out, 2)))             # (None: rows like u)
+    A = _Desc.fresh(u, (Di, dstate), 3, torch.float32)
+    delta = xc = None
+    if chunk_len:                                                   # the split: delta is the workspace its first pass fills, xc its carries
+        delta, xc = _Desc.fresh(u, u.shape, 4), _Desc.fresh(u, (Bsz, Di, -(-L // chunk_len), 2 * dstate), 5, torch.float32)
+    P = scan_block(u.scan_view(), None if delta is None else delta.scan_view(), A, x_dbl.columns(R, dstate), x_dbl.columns(R + dstate, dstate), None,
+                   z.scan_view(), None, True, out_z=y.scan_view(), x=xc, reset_period=reset_period, chunk_len=chunk_len or 2048, dt_x=x_dbl, dt_w=weight)
+    served = _served("zigma_selective_scan_fwd", P, "scan_tok2_n16_split_dtproj" if chunk_len else "scan_tok2_n16_dtproj*")
+    if served and keep is not None:
+        keep["scan"] = P
+    return served
+
+
+def dt_proj_block(x_dbl, dt_rank, weight, bias, softplus, out):
+    """the parameter block of zigma_dt_proj_softplus_fwd: x_dbl (..., >= dt_rank) rows one pitch apart, weight (d_inner, dt_rank), float32 bias or
+    None, out (..., d_inner)"""
+    P = _lib.DtProjParams()
+    P.m, P.n, P.k = math.prod(x_dbl.shape[:-1]), weight.shape[0], dt_rank
+    P.dtype, P.softplus, P.flags = _lib.dtype_id(x_dbl), int(bool(softplus)), DT_PROJ_FLAGS
+    P.x_row_stride, P.w_row_stride, P.out_row_stride = x_dbl.stride(-2), weight.stride(0), out.stride(-2)
+    P.x, P.w, P.out = _lib.ptr(x_dbl), _lib.ptr(weight), _lib.ptr(out)
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (weight.shape[0],) or bias.stride(0) != 1:
+            raise RuntimeError("bias must be contiguous float32 (d_inner,)")
+        P.bias = _lib.ptr(bias)
+    return P
 
 
 def dt_proj_eligible(x_dbl, dt_rank, weight):
-    """limits of zigma_dt_proj_softplus_fwd, restating plan_dt_proj() (csrc/front_plan.h): bf16 or fp16 (x_dbl and weight alike) token-major x_dbl rows /
-    weight rows a multiple of 8 elements apart on 16-byte boundaries, d_inner a multiple of 64, 8 <= dt_rank <= 48, % 8 == 0.  No policy on top of the
-    limits.  tests/test_host_cpu.py sweeps the predicate against the compiled plan."""
-    return (x_dbl.is_cuda and x_dbl.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x_dbl.dtype and 8 <= dt_rank <= 48
-            and dt_rank % 8 == 0
-            and weight.shape[0] % 64 == 0 and x_dbl.stride(-1) == 1 and weight.stride(1) == 1
-            and x_dbl.stride(-2) % 8 == 0 and weight.stride(0) % 8 == 0
-            and x_dbl.data_ptr() % 16 == 0 and weight.data_ptr() % 16 == 0)
+    """zigma_dt_proj_softplus_fwd takes dt_proj: what plan_dt_proj() (csrc/front_plan.h) serves, asked through the library; on top of it only the
+    device, one dtype for both operands and contiguous x_dbl rows / weight columns (the block has one dtype and row pitches only).  No policy."""
+    if not (x_dbl.is_cuda and weight.dtype == x_dbl.dtype and x_dbl.stride(-1) == 1 and weight.stride(1) == 1):
+        return False
+    out = _Desc.fresh(x_dbl, (math.prod(x_dbl.shape[:-1]), weight.shape[0]), 1)
+    return _served("zigma_dt_proj_softplus_fwd", dt_proj_block(x_dbl, dt_rank, weight, None, True, out), "dt_proj_softplus_mfma")
 
 
 def dt_proj_softplus(x_dbl, dt_rank, weight, bias=None, softplus=True):
@@ -319,16 +442,7 @@ def dt_proj_softplus(x_dbl, dt_rank, weight, bias=None, softplus=True):
         raise RuntimeError("x_dbl rows must be contiguous")
     n = weight.shape[0]
     out = torch.empty(x2.shape[0], n, device=x_dbl.device, dtype=x_dbl.dtype)
-    P = _lib.DtProjParams()
-    P.m, P.n, P.k = x2.shape[0], n, dt_rank
-    P.dtype, P.softplus, P.flags = _lib.dtype_id(x_dbl), int(bool(softplus)), DT_PROJ_FLAGS
-    P.x_row_stride, P.w_row_stride, P.out_row_stride = x2.stride(0), weight.stride(0), out.stride(0)
-    P.x, P.w, P.out = _lib.ptr(x2), _lib.ptr(weight), _lib.ptr(out)
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.shape != (n,) or bias.stride(0) != 1:
-            raise RuntimeError("bias must be contiguous float32 (d_inner,)")
-        P.bias = _lib.ptr(bias)
-    _lib.call("zigma_dt_proj_softplus_fwd", P, dev)
+    _lib.call("zigma_dt_proj_softplus_fwd", dt_proj_block(x2, dt_rank, weight, bias, softplus, out), dev)
     return out.reshape(*lead, n)
 
 
@@ -436,44 +550,39 @@ def differentiable(*tensors):
 
 def z_preactivated_eligible(batch, seqlen, d_state):
     """scan-side limits of a gate in_proj pre-activated (ZIGMA_SCAN_Z_PREACTIVATED): the hot kernel's inference form, 16 states, whole tiles, one grid
-    (plan_scan() of csrc/scan_plan.h: tok2_layout_ok() without `out`, no batch slices)"""
+    (plan_scan() of csrc/scan_plan.h: tok2_layout_ok() without `out`, no batch slices).  Stated here and not asked of the library: the choice is made
+    before in_proj runs, when xz — and with it every operand of the scan's block — does not exist yet, and it only gates an in_proj epilogue
+    (a scan the plan then does not serve pre-activated is refused by the library, never computed wrongly)."""
     return d_state == 16 and seqlen % 16 == 0 and batch <= 65535 and not torch.is_grad_enabled()
-
-
-class _Fresh:
-    """A contiguous (B, L, C) tensor the front has yet to allocate, as the eligibility predicates read it.  Every u and x_dbl is a new
-    allocation in xz's dtype on xz's device, so the plan judges them before anything launches."""
-    def __init__(self, like, *shape):
-        self.is_cuda, self.dtype, self.shape, self._strides = like.is_cuda, like.dtype, shape, (shape[1] * shape[2], shape[2], 1)
-    stride, numel = (lambda self, i: self._strides[i]), (lambda self: self.shape[0] * self._strides[0])
-    dim, is_contiguous, data_ptr = (lambda self: 3), (lambda self: True), (lambda self: 0)      # (the caching allocator aligns every block)
 
 
 InnerPlan = namedtuple("InnerPlan", "front dt chunk_len accumulate")
 
 
 def plan_inner(x_half, z_half, conv_w, conv_b, x_proj_w, dt_proj_w, A, delta_bias, *, perm=None, reset_period=0, z_preactivated=False, out=None,
-               add_to=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True, train=False):
+               add_to=None, B_proj_bias=None, C_proj_bias=None, delta_softplus=True, train=False, blocks=None):
     """The one place that chooses the kernels of the Mamba inner, from mamba_inner_tok's arguments (xz as its two halves, conv_w as
     (d_inner, width)); knobs and predicates are looked up as module globals at call time.  Returns InnerPlan:
     front       "conv_x_proj" (one kernel) | "conv+x_proj" (conv kernel, x_proj kernel) | "conv+linear" (conv kernel, library GEMM)
     dt          "in_scan" (dt_proj + softplus in the scan's tile prologue) | "in_split" (in the split's first pass, which writes delta)
                 | "kernel" (zigma_dt_proj_softplus_fwd) | "linear" (library GEMM; the scan adds the bias and applies softplus)
     chunk_len   0: the scan takes the whole sequence; else the chunk length of the sequence split
-    accumulate  add_to rides in the scan's epilogue (ZIGMA_SCAN_ACCUMULATE); else an in-place add behind the scan"""
+    accumulate  add_to rides in the scan's epilogue (ZIGMA_SCAN_ACCUMULATE); else an in-place add behind the scan
+    blocks: a dict that receives the parameter blocks the decision built and the library accepted ("scan": with dt "in_scan" / "in_split"), so that
+    the launch completes them instead of building them again"""
     Bsz, L, Di = x_half.shape
     R, N = dt_proj_w.shape[1], A.shape[1]
-    u, x_dbl = _Fresh(x_half, Bsz, L, Di), _Fresh(x_half, Bsz, L, x_proj_w.shape[0])
+    u, x_dbl = _Desc.fresh(x_half, (Bsz, L, Di), 6), _Desc.fresh(x_half, (Bsz, L, x_proj_w.shape[0]), 7)     # every u and x_dbl is a new allocation in xz's dtype
     front = ("conv_x_proj" if USE_CONV_X_PROJ and conv_x_proj_eligible(x_half, conv_w, conv_b, x_proj_w, perm, reset_period)
              else "conv+x_proj" if not train and USE_X_PROJ_KERNEL and x_proj_eligible(u, x_proj_w)
              else "conv+linear")     # training never takes the x_proj kernel (the rule as it has always been; no measurement either way)
     if train:                        # the training scan: whole sequence (it writes the backward's checkpoints), delta from the GEMM
         return InnerPlan(front, "linear", 0, False)
     chunk = split_chunk_len(Bsz, Di, L, reset_period)
+    # policy: the split's first pass forms delta only with a bias and a gate it activates itself
     inside = (delta_softplus and B_proj_bias is None and C_proj_bias is None
-              and (DT_PROJ_IN_SPLIT and delta_bias is not None and not z_preactivated and split_limits_ok(Bsz, Di, L, chunk) if chunk
-                   else DT_PROJ_IN_SCAN)
-              and dt_in_scan_eligible(u, x_dbl, dt_proj_w, reset_period, out if add_to is None else add_to, dstate=N, z=z_half))
+              and (DT_PROJ_IN_SPLIT and delta_bias is not None and not z_preactivated if chunk else DT_PROJ_IN_SCAN)
+              and dt_in_scan_eligible(u, x_dbl, dt_proj_w, reset_period, out if add_to is None else add_to, dstate=N, z=z_half, chunk_len=chunk, keep=blocks))
     dt = ("in_split" if chunk else "in_scan") if inside else "kernel" if delta_softplus and dt_proj_eligible(x_dbl, R, dt_proj_w) else "linear"
     return InnerPlan(front, dt, chunk, add_to is not None and dt == "in_scan" and ACCUMULATE_IN_SCAN)
 
@@ -662,9 +771,10 @@ def mamba_inner_tok(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_we
     if amp.mixed(xz, x_proj_weight) and amp.mixed(xz, delta_proj_weight):
         # mixed precision: the kernels (and the plan) read the 16-bit shadows of the two GEMM weights; conv taps, A, D, delta_bias stay fp32
         x_proj_weight, delta_proj_weight = shadows = (amp.shadow(x_proj_weight, xz.dtype), amp.shadow(delta_proj_weight, xz.dtype))
+    blocks = {}
     plan = plan_inner(x_half, z_half, w, conv1d_bias, x_proj_weight, delta_proj_weight, A, delta_bias, perm=perm, reset_period=reset_period,
                       z_preactivated=z_preactivated, out=out, add_to=add_to, B_proj_bias=B_proj_bias, C_proj_bias=C_proj_bias,
-                      delta_softplus=delta_softplus, train=train)
+                      delta_softplus=delta_softplus, train=train, blocks=blocks)
     out_rows = perm if out_rows is None else out_rows
     if train:
         return MambaInnerTokFn.apply(xz, conv1d_weight, conv1d_bias, *params, A, D, delta_bias, perm, out_rows,
@@ -678,10 +788,15 @@ def mamba_inner_tok(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_we
         delta_bias, delta_softplus = None, False
     elif plan.dt == "linear":
         delta = F.linear(x_dbl[:, :, :R], delta_proj_weight)
-    Bm, Cm = (M if b is None else M + b.to(M.dtype) for M, b in ((x_dbl[:, :, R:R + N], B_proj_bias), (x_dbl[:, :, R + N:R + 2 * N], C_proj_bias)))
     dt_inside = plan.dt in ("in_scan", "in_split")
     y = add_to if plan.accumulate else out if out is not None else torch.empty(Bsz, L, Di, device=u.device, dtype=u.dtype)
     xc = torch.empty(Bsz, Di, -(-L // plan.chunk_len), 2 * N, device=u.device, dtype=torch.float32) if plan.chunk_len else None   # split carries
+    if dt_inside and "scan" in blocks and (add_to is None or plan.accumulate):
+        # the block the dt decision asked the library about describes this very call (the result where the decision saw it: `out` / fresh rows,
+        # or add_to when the scan adds to it): it gets its addresses and is launched, not built a second time
+        scan_planned(blocks["scan"], u, x_dbl, delta, xc, y, z_half, A, D, delta_bias, perm, out_rows, z_preactivated, plan.accumulate)
+        return y
+    Bm, Cm = (M if b is None else M + b.to(M.dtype) for M, b in ((x_dbl[:, :, R:R + N], B_proj_bias), (x_dbl[:, :, R + N:R + 2 * N], C_proj_bias)))
     scan_raw(u.transpose(1, 2), None if delta is None else delta.transpose(1, 2), A, Bm.transpose(1, 2).unsqueeze(1),
              Cm.transpose(1, 2).unsqueeze(1), D, z_half.transpose(1, 2), delta_bias, delta_softplus,
              out_z=y.transpose(1, 2), z_row_index=perm, out_row_index=out_rows, want_out=False, x=xc, reset_period=reset_period,
