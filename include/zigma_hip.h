@@ -597,6 +597,15 @@ int zigma_linear_wgrad(const zigma_linear_wgrad_params_t *p, void *stream);
  *   passes == 3 ("high", bf16 x 3):  out = sum_k (x_hi w_hi + x_lo w_hi + x_hi w_lo) + bias   (lo x lo is omitted)
  *   passes == 1 ("medium"):          out = sum_k x_hi w_hi + bias                             (w_lo is not read, may be NULL)
  * All products are v_mfma_f32_32x32x16_bf16 with fp32 accumulators: one for hi x hi, a second one for the two cross terms, added at the end.
+ * Consequences of the definition at the ends of the range (tests/test_gpu_matmul_sweep.py holds them bit for bit):
+ *   - float(hi) + float(lo) is formed exactly in fp32 for every finite a below the clamp, so with a unit weight "high" returns hi + lo itself
+ *     and "medium" returns float(hi);
+ *   - from the largest finite bf16 (0x7f7f0000) upwards hi stays 0x7f7f and lo takes the rest: split(FLT_MAX) is hi = 0x7f7f, lo = 2^120, whose
+ *     sum is 2^128: "high" with a unit weight returns +inf for an x of FLT_MAX (-inf for -FLT_MAX), although no plane holds an infinity.
+ *     Every product whose true value stays inside fp32 is unaffected (a weight of 1/2 returns 2^127);
+ *   - below 2^-117 lo lies on the bf16 subnormal grid (spacing 2^-133), below 2^-126 hi does too: hi + lo misses a by up to 2^-134 whatever
+ *     its size, and an fp32 subnormal keeps about 7 significant bits.  Subnormals are not flushed: the planes, the products and the fp32
+ *     accumulators hold them (measured on the MI355X with selection weights).
  * x: (m, k) rows of pitch x_row_stride; w_hi / w_lo: (n, k) rows of pitch w_*_row_stride; out: (m, n) rows of pitch out_row_stride (views of
  * wider rows pass as they are); bias (n) or NULL.  Nothing outside out[:m, :n] is written; a partly filled last token tile is predicated.
  * Errors, decided before anything touches the device: NULL block / x / w_hi / out (w_lo with passes == 3) -> ZIGMA_ERR_NULL; flags != 0 or

@@ -560,3 +560,81 @@ def _norm_linear_fwd(P, plan):
     r = torch_norm_linear(x.double(), w.double(), mod(P.shift), mod(P.scale), float(P.eps), dt)
     _view(P.out, (m, n), (P.out_row_stride, 1), dt).copy_(r["out"].float().to(dt))
     return got["kernel"]
+
+
+# ---------------------------------------------------------------------------------------------------
+# Stand-ins AT THE C ABI for zigma_linear_f32_split and zigma_linear_wgrad (tests/test_gpu_matmul_sweep.py on the CPU).  torch_split_linear is
+# fp32_matmul.reference on given weight planes (x is split by fp32_matmul.split, the definition), torch_wgrad the float64 dy^T x; the CPU test
+# holds the numpy references of tests/matmul_sweep_cases.py against them.  The _* functions read and write through the parameter block, refuse
+# what the entry points refuse and name the kernel from the host code's choice (the passes; wgrad_bk / wgrad_slabs of csrc/wgrad.hip).
+# ---------------------------------------------------------------------------------------------------
+def torch_split_linear(x, w_hi, w_lo, bias, passes):
+    """x (m, k) fp32, w_hi / w_lo (n, k) bf16, bias (n) fp32 | None -> (m, n) float64: the bf16-plane products summed in float64"""
+    from zigma_amd.fp32_matmul import split
+    xh, xl = (t.double() for t in split(x))
+    y = xh @ w_hi.double().T
+    if passes == 3:
+        y = y + (xl @ w_hi.double().T + xh @ w_lo.double().T)
+    return y if bias is None else y + bias.double()
+
+
+def torch_wgrad(dy, x):
+    return dy.double().T @ x.double()
+
+
+def _linear_f32_split(P):
+    if not P.x or not P.w_hi or not P.out or (P.passes == 3 and not P.w_lo):
+        _refuse(-1)
+    if P.flags != 0 or P.passes not in (1, 3):
+        _refuse(-6)
+    lo, m, n, k = P.passes == 3, P.m, P.n, P.k
+    if m < 0 or m % 8 or n < 128 or n % 128 or n > 65536 or k < 64 or k % 64 or k > 65536:
+        _refuse(-2)
+    if P.x_row_stride < k or P.w_hi_row_stride < k or (lo and P.w_lo_row_stride < k) or P.out_row_stride < n:
+        _refuse(-2)
+    if (any(p and p % 16 for p in (P.x, P.w_hi, P.w_lo if lo else 0, P.out, P.bias)) or P.x_row_stride % 4 or P.out_row_stride % 4 or P.w_hi_row_stride % 8
+            or (lo and P.w_lo_row_stride % 8)):
+        _refuse(-4)
+    f32, bf = torch.float32, torch.bfloat16
+    if m:
+        y = torch_split_linear(_view(P.x, (m, k), (P.x_row_stride, 1), f32), _view(P.w_hi, (n, k), (P.w_hi_row_stride, 1), bf),
+                               _view(P.w_lo, (n, k), (P.w_lo_row_stride, 1), bf) if lo else None, _view(P.bias, (n,), (1,), f32), P.passes)
+        _view(P.out, (m, n), (P.out_row_stride, 1), f32).copy_(y.float() + 0.0)          # (the accumulators start at +0: no -0 result)
+    return f"linear_split{P.passes}_128x128"
+
+
+def _linear_wgrad(P):
+    from zigma_amd import _lib
+    if not P.dy or not P.x or not P.out:
+        _refuse(-1)
+    if P.dtype not in (_lib.BF16, _lib.F16) or P.out_dtype not in (P.dtype, _lib.F32):
+        _refuse(-3)
+    m, n, k = P.m, P.n, P.k
+    if m < 1 or n < 8 or k < 8 or n % 8 or k % 8 or n > 8192 or k > 8192 or P.slabs < 0 or P.slabs > 4096:
+        _refuse(-2)
+    if P.flags != 0:
+        _refuse(-6)
+    bk = 64 if k <= 64 else 128
+    tiles = -(-n // 128) * -(-k // bk)
+    S = P.slabs if P.slabs > 0 else max(1, min(-(-512 // tiles), m // 512, 64))
+    need = S * n * k * 4 if S > 1 else 0
+    if need and not P.workspace:
+        _refuse(-1)
+    if P.workspace_bytes < need:
+        _refuse(-2)
+    dt, odt = _io_dtype(P.dtype), _io_dtype(P.out_dtype)
+    es = torch.empty((), dtype=odt).element_size()
+    if (P.dy_row_stride < n or P.x_row_stride < k or P.out_row_stride < k or P.dy_row_stride % 8 or P.x_row_stride % 8 or P.dy % 16 or P.x % 16 or P.out % 16
+            or (P.out_row_stride * es) % 16 or (need and P.workspace % 16)):
+        _refuse(-4)
+    dy, x = _view(P.dy, (m, n), (P.dy_row_stride, 1), dt), _view(P.x, (m, k), (P.x_row_stride, 1), dt)
+    if S > 1:                               # the fp32 partials of the slabs, [S][n][k]
+        rows = -(-(-(-m // S)) // 64) * 64
+        ws = _view(P.workspace, (S, n, k), (n * k, k, 1), torch.float32)
+        for s in range(S):
+            ws[s] = torch_wgrad(dy[s * rows:(s + 1) * rows], x[s * rows:(s + 1) * rows]).float()
+    _view(P.out, (n, k), (P.out_row_stride, 1), odt).copy_((torch_wgrad(dy, x).float() + 0.0).to(odt))
+    return f"wgrad_128x{bk}" + ("_splitk" if S > 1 else "")
+
+
+OUTER_SERVE.update({"zigma_linear_f32_split": _linear_f32_split, "zigma_linear_wgrad": _linear_wgrad})

@@ -8,6 +8,8 @@ xf32 MFMA and its fp32 matrix rate is 1/16 of the bf16 rate; an fp32 value is th
     "high":    y = sum_k (x_hi w_hi + x_lo w_hi + x_hi w_lo) + bias      three bf16 MFMA products, fp32 accumulators, lo x lo omitted
     "medium":  y = sum_k x_hi w_hi + bias                                the same kernel with one pass
     "highest": the library's fp32 GEMM, bit for bit what it always was — the default; none of this module's code is entered
+At the ends of the range (include/zigma_hip.h): split(FLT_MAX) is hi = 0x7f7f, lo = 2^120, so "high" returns +inf for FLT_MAX under a unit
+weight; an fp32 subnormal keeps about 7 bits (the planes' subnormal spacing is 2^-133).
 
 The kernel is csrc/linear_split.hip (zigma_linear_f32_split): the weight planes are split once here (split_weight, cached against the
 parameter's version counter — so a warmed-up forward holds no split and a hipGraph capture never captures one), x is split inside the kernel
