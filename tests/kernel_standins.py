@@ -168,6 +168,60 @@ def torch_scan_fwd(u, step, A, Bm, Cm, D, gate, zi, oi, *, reset=0, chunk=0, out
     return dict(y=place(y), y_gated=y_gated, ckpt=ckpt, x_prod=x_prod, x_state=x_state)
 
 
+def torch_scan_ref_layout(u, step, A, Bm, Cm, D, gate, zi, oi, *, chunk=0):
+    """The selective scan of the reference's call surface as an explicit float64 loop over (chunk, step).  u, step (B, dim, L), step = the step
+    sizes the recurrence runs on; Bm, Cm (B, G, N, L) — channel d reads group d // (dim // G) — or constant (dim, N); gate (B, dim, L) multiplier
+    read at row zi[l] or None; results are written at row oi[l].  Returns y (ungated, placed), y_gated (placed) and, with chunk > 0, x_prod /
+    x_state (B, dim, chunk, N): the decay product since the start of the sequence and the state at every chunk end."""
+    f64 = torch.float64
+    u, step, A = u.to(f64), step.to(f64), A.to(f64)
+    Bsz, dim, L = u.shape
+    N = A.shape[1]
+
+    def per_channel(M):         # -> (B | 1, dim, N, L | 1)
+        M = M.to(f64)
+        return M[None, :, :, None] if M.dim() == 2 else M.repeat_interleave(dim // M.shape[1], dim=1)
+    Bm, Cm = per_channel(Bm), per_channel(Cm)
+    at = lambda M, l: M[..., 0] if M.shape[-1] == 1 else M[..., l]
+    y = torch.empty(Bsz, dim, L, dtype=f64)
+    n_chunks = -(-L // chunk) if chunk else 0
+    x_prod, x_state = torch.zeros(Bsz, dim, n_chunks, N, dtype=f64), torch.zeros(Bsz, dim, n_chunks, N, dtype=f64)
+    h, prod = torch.zeros(Bsz, dim, N, dtype=f64), torch.ones(Bsz, dim, N, dtype=f64)
+    for l in range(L):
+        d = step[:, :, l, None]
+        a = torch.exp(d * A)
+        h = a * h + d * u[:, :, l, None] * at(Bm, l)
+        prod = prod * a
+        y[:, :, l] = (h * at(Cm, l)).sum(-1)
+        if chunk and ((l + 1) % chunk == 0 or l == L - 1):
+            x_prod[:, :, l // chunk], x_state[:, :, l // chunk] = prod, h
+    if D is not None:
+        y = y + u * D.to(f64)[:, None]
+    place = lambda t: t if oi is None else torch.empty_like(t).index_copy_(2, oi.long(), t)
+    y_gated = None
+    if gate is not None:
+        g = gate.to(f64)
+        y_gated = place(y * (g if zi is None else g.index_select(2, zi.long())))
+    return dict(y=place(y), y_gated=y_gated, x_prod=x_prod, x_state=x_state)
+
+
+def torch_conv1d(x, w, b, silu, rows=None, reset=0):
+    """the depthwise causal conv of the call surface, float64, tap by tap: x (B, dim, L) read at row rows[l], w (dim, W), b (dim,) | None; with
+    reset > 0 the window restarts every `reset` positions"""
+    x, w = x.double(), w.double()
+    if rows is not None:
+        x = x.index_select(2, rows.long())
+    L, W = x.shape[2], w.shape[1]
+    pos = torch.arange(L)
+    start = pos // reset * reset if reset else torch.zeros(L, dtype=torch.long)
+    y = torch.zeros_like(x) + (0 if b is None else b.double()[:, None])
+    for j in range(W):
+        k = pos - (W - 1 - j)
+        ok = (k >= start).double()
+        y = y + w[:, j, None] * x[:, :, k.clamp(min=0)] * ok
+    return y * torch.sigmoid(y) if silu else y
+
+
 def _view(ptr, shape, strides, dtype):
     """the tensor a parameter block describes: base pointer, shape and strides in elements"""
     if not ptr:
@@ -189,6 +243,8 @@ def _scan_fwd(P, plan):
     got = plan(P)
     if got["status"] != 0:
         raise RuntimeError(f"zigma_selective_scan_fwd: refused (status {got['status']})")
+    if got["family"] == _lib.SCAN_KERNEL_GENERIC:
+        return _scan_generic_fwd(P, got)
     Bsz, dim, L, N = P.batch, P.dim, P.seqlen, P.dstate
     act = lambda name: _view(getattr(P, name), (Bsz, L, dim), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "l", "d")], dt)
     bc = lambda name: _view(getattr(P, name), (Bsz, L, N), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "l", "dstate")], dt)
@@ -230,6 +286,51 @@ def _scan_fwd(P, plan):
     if P.info:
         P.info[0], P.info[1] = got["family"], got["info1"]
     return got["kernel"]
+
+
+def _scan_generic_fwd(P, got):
+    """what scan_generic_kernel serves: every operand through its own strides, B / C per group in bc_dtype or constant fp32 (dim, dstate), the
+    row tables, the carries of every chunk end (tests/test_gpu_ref_layout.py on the CPU)"""
+    f32, dt, bdt = torch.float32, _io_dtype(P.io_dtype), _io_dtype(P.bc_dtype)
+    Bsz, dim, L, N, G = P.batch, P.dim, P.seqlen, P.dstate, P.n_groups
+    act = lambda name: _view(getattr(P, name), (Bsz, dim, L), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "d", "l")], dt)
+
+    def bc(name, variable):
+        if variable:
+            return _view(getattr(P, name), (Bsz, G, N, L), [getattr(P, f"{name}_{s}_stride") for s in ("batch", "group", "dstate", "l")], bdt)
+        return _view(getattr(P, name), (dim, N), [getattr(P, f"{name}_d_stride"), getattr(P, f"{name}_dstate_stride")], f32)
+    A = _view(P.A, (dim, N), (P.A_d_stride, P.A_dstate_stride), f32)
+    D, bias = _view(P.D, (dim,), (1,), f32), _view(P.delta_bias, (dim,), (1,), f32)
+    u, z, delta = act("u"), act("z"), act("delta")
+    pre = delta.double() if bias is None else delta.double() + bias.double()[:, None]
+    step = _softplus(pre) if P.delta_softplus else pre
+    gate = None if z is None else z.double() * torch.sigmoid(z.double())
+    zi, oi = _view(P.z_row_index, (L,), (1,), torch.int32), _view(P.out_row_index, (L,), (1,), torch.int32)
+    chunk = (P.chunk_len if P.chunk_len > 0 else 2048) if P.x else 0
+    r = torch_scan_ref_layout(u, step, A, bc("B", P.is_variable_B), bc("C", P.is_variable_C), D, gate, zi, oi, chunk=chunk)
+    out, out_z = act("out"), act("out_z")
+    if out_z is not None and z is not None:
+        out_z.copy_(r["y_gated"].to(dt))
+    if out is not None:
+        out.copy_(r["y"].to(dt))
+    if P.x:
+        nc = r["x_prod"].shape[2]
+        xv = _view(P.x, (Bsz, dim, nc, 2 * N), _contig((Bsz, dim, nc, 2 * N)), f32)
+        xv[..., 0::2], xv[..., 1::2] = r["x_prod"].float(), r["x_state"].float()
+    if P.info:
+        P.info[0], P.info[1] = got["family"], got["info1"]
+    return got["kernel"]
+
+
+def _conv1d_fwd(P, plan):
+    kernel = _front_kernel("zigma_causal_conv1d_fwd", P, plan)
+    dt, wdt = _io_dtype(P.io_dtype), _io_dtype(P.w_dtype)
+    Bsz, dim, L, W = P.batch, P.dim, P.seqlen, P.width
+    x = _view(P.x, (Bsz, dim, L), (P.x_batch_stride, P.x_c_stride, P.x_l_stride), dt)
+    w, b = _view(P.weight, (dim, W), (P.weight_c_stride, P.weight_width_stride), wdt), _view(P.bias, (dim,), (1,), wdt)
+    y = torch_conv1d(x, w, b, bool(P.silu_activation), _view(_addr(P.x_row_index), (L,), (1,), torch.int32), P.reset_period)
+    _view(P.out, (Bsz, dim, L), (P.out_batch_stride, P.out_c_stride, P.out_l_stride), dt).copy_(y.to(dt))
+    return kernel
 
 
 def _addr(p):
@@ -295,7 +396,7 @@ def install_lib_call(monkeypatch, plan=None, front_plan=None, linear_plan=None, 
     tests/test_linear_cases_cpu.py): they name the kernel, fill the scan's `info` and refuse what the library refuses (only the scan, the three
     front entry points and the two dense projections need them)"""
     from zigma_amd import _lib
-    serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_conv_x_proj_fwd": lambda P: _conv_xproj_fwd(P, front_plan),
+    serve = {"zigma_selective_scan_fwd": lambda P: _scan_fwd(P, plan), "zigma_causal_conv1d_fwd": lambda P: _conv1d_fwd(P, front_plan), "zigma_conv_x_proj_fwd": lambda P: _conv_xproj_fwd(P, front_plan),
              "zigma_x_proj_fwd": lambda P: _x_proj_fwd(P, front_plan), "zigma_dt_proj_softplus_fwd": lambda P: _dt_proj_fwd(P, front_plan),
              "zigma_linear_fwd": lambda P: _linear_fwd(P, linear_plan), "zigma_norm_linear_fwd": lambda P: _norm_linear_fwd(P, norm_linear_plan), **OUTER_SERVE}
 
