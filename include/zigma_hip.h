@@ -41,7 +41,8 @@ extern "C" {
                                * (10, no block changed): zigma_linear_f32_split added
                                * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added
                                * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added
-                               * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added */
+                               * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added
+                               * (11, no block changed): zigma_optim_* added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -740,6 +741,84 @@ typedef struct zigma_multi_cast_params {
     int32_t pad_;
 } zigma_multi_cast_params_t;
 int zigma_multi_cast_fwd(const zigma_multi_cast_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The tail of a training step over MANY float32 parameters in one pass (csrc/optim_step.hip): global-norm gradient clipping, AdamW with
+ * decoupled weight decay, the exponential moving average of the parameters and the refresh of their 16-bit copies — the work of the
+ * reference's `opt.step()`, `grad_clip(...)`, `update_ema(...)` (train_acc.py:443-448, utils/train_utils.py:103-133) and of one
+ * zigma_multi_cast_fwd.  Table-driven like the cast; three launches on ONE parameter block.  (ABI 11, no block changed.)
+ *
+ *   table      n_entries x zigma_optim_row_t in DEVICE memory.  p, g, m, v are float32 and required per row; ema (float32) and shadow
+ *              (elements of shadow_dtype) may be NULL per row.  Only natural alignment is assumed.  numel == 0 is legal.
+ *   chunk_map  n_chunks x {entry, offset} in DEVICE memory, the rows of zigma_multi_cast_chunk_t: workgroup w owns elements
+ *              [offset, min(offset + chunk, numel)) of table[entry].  A map row whose entry or offset lies outside the table is skipped:
+ *              no pointer of the table is followed for it (the sum-of-squares pass stores 0 as that workgroup's partial sum).
+ *   partials   n_chunks floats in DEVICE memory: the per-workgroup sums of squares.  NULL for the prepare call means that no
+ *              sum-of-squares pass ran: there is no norm (grad_norm reads NaN), nothing is clipped, and only found_inf can skip the step.
+ *   state      one zigma_optim_state_t in DEVICE memory; `step` is read and written, the rest written by the prepare call.
+ *   grad_scale, found_inf   optional DEVICE float scalars (what torch.amp.GradScaler hands an optimizer): the gradients are divided by
+ *              *grad_scale, and a non-zero *found_inf skips the step.
+ *
+ * zigma_optim_grad_sumsq   grid n_chunks: partials[w] = the float32 sum of g[i]^2 over workgroup w's piece; each lane sums its elements, then
+ *              the wave, then the four waves through LDS, in a fixed order and without atomics: bit-identical from run to run.
+ * zigma_optim_prepare      one workgroup: sum = partials summed in double in a fixed order; norm = sqrt(sum) / grad_scale;
+ *              skipped = (found_inf && *found_inf != 0) || !isfinite(norm).  If not skipped: step += 1;
+ *              clip = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1; grad_mult = clip / grad_scale;
+ *              step_size = lr / (1 - beta1^step); bc2_sqrt = sqrt(1 - beta2^step), both formed in double.  If skipped, step keeps its
+ *              value and grad_mult = step_size = 0, bc2_sqrt = 1.
+ * zigma_optim_adamw        grid n_chunks: returns before any store if state->skipped; else per element, in float32 and in this order:
+ *                  g = grad * grad_mult;  p -= (lr * weight_decay) * p;  m += (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
+ *                  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps);  ema += (p - ema) * (1 - ema_decay);  shadow = round_to_nearest_even(p)
+ *              (the constants rounded to float32 from their double values; the bits of the cast kernel for the shadow).  The gradient is
+ *              never written.  A workgroup whose present streams all start on 16-byte boundaries moves 8 elements per lane and
+ *              iteration and finishes the last numel % 8 one by one; any other piece goes element by element.
+ *
+ * Checked in this order by all three, before any launch: negative counts (or more than 2^31 - 1 chunks) ZIGMA_ERR_SHAPE; shadow_dtype other
+ * than ZIGMA_BF16 / ZIGMA_F16 / -1 (no shadows) ZIGMA_ERR_DTYPE; non-zero flags ZIGMA_ERR_UNSUPPORTED; n_entries == 0 or n_chunks == 0:
+ * nothing is launched, ZIGMA_OK; a NULL pointer among those the call uses (sumsq: table, chunk_map, partials; prepare: state; adamw: table,
+ * chunk_map, state) ZIGMA_ERR_NULL; a chunk that is not a multiple of 8 in 8 ... 65536 ZIGMA_ERR_SHAPE; beta1 or beta2 outside [0, 1),
+ * eps <= 0, a non-finite lr (or weight_decay, max_grad_norm, ema_decay; NaN anywhere) ZIGMA_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_optim_row {
+    float *p;            /* parameter                          */
+    const float *g;      /* gradient: read only                */
+    float *m;            /* exp_avg                            */
+    float *v;            /* exp_avg_sq                         */
+    float *ema;          /* moving average of p, or NULL       */
+    void *shadow;        /* 16-bit copy of p, or NULL          */
+    int64_t numel;
+    int64_t pad_;        /* rows are 64 bytes                  */
+} zigma_optim_row_t;
+
+typedef struct zigma_optim_state {
+    float step;          /* steps taken (a float, like the step tensors of torch's fused / capturable optimizers) */
+    int32_t skipped;     /* 1: the last step changed nothing   */
+    float grad_norm;     /* global L2 norm of the unscaled gradients before clipping (NaN: not computed) */
+    float grad_mult;     /* clip / grad_scale                  */
+    float step_size;     /* lr / (1 - beta1^step)              */
+    float bc2_sqrt;      /* sqrt(1 - beta2^step)               */
+    int32_t pad_[2];
+} zigma_optim_state_t;
+
+typedef struct zigma_optim_params {
+    const zigma_optim_row_t *table;
+    const zigma_multi_cast_chunk_t *chunk_map;
+    int64_t n_entries, n_chunks;
+    float *partials;
+    zigma_optim_state_t *state;
+    const float *grad_scale;
+    const float *found_inf;
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_grad_norm;   /* <= 0: no clipping */
+    double ema_decay;
+    int32_t shadow_dtype;   /* ZIGMA_BF16, ZIGMA_F16, or -1: no row has a shadow (the column is ignored) */
+    int32_t chunk;          /* elements per workgroup */
+    int32_t flags;          /* reserved, must be 0 */
+    int32_t pad_;
+} zigma_optim_params_t;
+int zigma_optim_grad_sumsq(const zigma_optim_params_t *p, void *stream);
+int zigma_optim_prepare(const zigma_optim_params_t *p, void *stream);
+int zigma_optim_adamw(const zigma_optim_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-only plan queries of the Mamba inner's five forward entry points (ABI 11): what the launch would do with this parameter block,

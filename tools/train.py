@@ -4,6 +4,11 @@ model — synthetic latents, no dataloader / EMA / wandb.  Forward AND backward 
 (LayerNormFn, MambaInnerTokFn); the projections, attention and optimizer are torch.
 
     python tools/train.py --config '{...}' --batch 32 --steps 20
+    python tools/train.py --config '{...}' --amp bf16 --fused-step --max-grad-norm 2.0      # the step's tail on the own kernels
+
+--fused-step: the reference's `opt.step()` / `grad_clip` / `update_ema` (train_acc.py:443-448) as zigma_amd.optim.FusedAdamW — AdamW, global-norm
+clipping (before the update), an EMA copy of the model and, under --amp, the 16-bit shadows in one pass, three launches, no host sync.  Without the flag
+the loop is what it was: torch.optim.AdamW(fused=True), no EMA, no clipping.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py ...   # data parallel
 
 Multi-GPU = plain data parallelism: one process per GPU, `--batch` samples per rank, gradients averaged by
@@ -29,6 +34,11 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--amp", default="off", choices=["off", "bf16", "fp16"],
                     help="mixed precision: the model is fp32 (whatever --dtype says) and the step runs under torch.autocast in this type; fp16 with a GradScaler")
+    ap.add_argument("--fused-step", action="store_true", help="AdamW + clip + EMA + shadow refresh on zigma_amd.optim.FusedAdamW (needs an fp32 model: --amp or --dtype fp32)")
+    ap.add_argument("--wd", type=float, default=None, help="weight decay (default: the optimizer's own, 1e-2)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="--fused-step: clip the global gradient norm to this before the update")
+    ap.add_argument("--ema-decay", type=float, default=0.9999, help="--fused-step: decay of the EMA copy")
+    ap.add_argument("--time-tail", action="store_true", help="--fused-step: HIP events around every optimizer step (adds no sync inside the loop)")
     ap.add_argument("--bucket-mb", type=int, default=100, help="DDP bucket size: xGMI rings are per-link bound, few large buckets")
     args = ap.parse_args()
 
@@ -52,7 +62,18 @@ def main():
     if world > 1:
         net = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], bucket_cap_mb=args.bucket_mb,
                                                         gradient_as_bucket_view=True)
-    opt = torch.optim.AdamW(model.parameters(), lr=args.lr, fused=True)
+    wd = {} if args.wd is None else dict(weight_decay=args.wd)
+    ema = None
+    if args.fused_step:
+        import copy
+        from zigma_amd import optim
+        ema = copy.deepcopy(model).requires_grad_(False)
+        opt = optim.FusedAdamW(model.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm, ema_params=ema, ema_decay=args.ema_decay,
+                               shadows=(model, torch.float16 if args.amp == "fp16" else torch.bfloat16) if args.amp != "off" else None, **wd)
+    else:
+        if args.max_grad_norm is not None or args.time_tail:
+            raise SystemExit("tools/train.py: --max-grad-norm and --time-tail go with --fused-step")
+        opt = torch.optim.AdamW(model.parameters(), lr=args.lr, fused=True, **wd)
     tr = create_transport()
     g = torch.Generator(device="cpu").manual_seed(1234 + rank)
     frames = cfg.get("video_frames", 0)
@@ -64,12 +85,19 @@ def main():
     elif cfg.get("num_classes", -1) > 0:
         kw["y"] = torch.randint(0, cfg["num_classes"], (args.batch,), generator=g).to(device)
 
+    tail_events = []
+
     def step():
-        opt.zero_grad(set_to_none=True)
+        opt.zero_grad(set_to_none=not args.fused_step)      # (FusedAdamW keeps its device table while the gradients stay where they are)
         with cast:
             loss = tr.training_losses(net, x1, kw)["loss"].mean()
         scaler.scale(loss).backward()          # (a disabled scaler passes the loss and the step through)
+        if args.time_tail:
+            tail_events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            tail_events[-1][0].record()
         scaler.step(opt)
+        if args.time_tail:
+            tail_events[-1][1].record()
         scaler.update()
         return loss
 
@@ -77,16 +105,24 @@ def main():
     for _ in range(args.warmup):
         step()
     ss.fence(device, world)
+    del tail_events[:]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         losses.append(step().detach())
     ss.fence(device, world)
     dt = (time.perf_counter() - t0) / args.steps
+    tail = {}
+    if args.fused_step:
+        from zigma_amd import optim
+        tail = dict(fused_step=True, step_tail_launches_per_step=optim.STATS["launches"] / max(optim.STATS["steps"], 1), step_tail_table_builds=optim.STATS["table_builds"],
+                    last_step_skipped=int(opt.skipped), last_grad_norm=float(opt.grad_norm) if args.max_grad_norm is not None else None, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
+        if tail_events:
+            tail["step_tail_ms"] = round(sum(a.elapsed_time(b) for a, b in tail_events) / len(tail_events), 4)
     if rank == 0:
         print(json.dumps(dict(world=world, per_gpu_batch=args.batch, ms_per_step=round(dt * 1e3, 2),
                               samples_per_s=round(world * args.batch / dt, 1), first_loss=round(float(losses[0]), 4),
                               last_loss=round(float(losses[-1]), 4), max_mem_GB=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
-                              amp=args.amp, amp_stats=dict(amp.STATS), use_shadows=amp.USE_SHADOWS)))
+                              amp=args.amp, amp_stats=dict(amp.STATS), use_shadows=amp.USE_SHADOWS, **tail)))
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("ZIGMA_AMD_LIB") or os.path.join(_HERE, "lib", "libzig
 F32, F16, BF16 = 0, 1, 2
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
-i32, i64, vp, f32 = C.c_int32, C.c_int64, C.c_void_p, C.c_float
+i32, i64, vp, f32, f64 = C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_double
 
 
 class ScanParams(C.Structure):
@@ -189,7 +189,21 @@ class MultiCastParams(C.Structure):
     _fields_ = [("table", vp), ("chunk_map", vp), ("n_entries", i64), ("n_chunks", i64), ("out_dtype", i32), ("chunk", i32), ("flags", i32), ("pad_", i32)]
 
 
-EXPORTS = ("zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
+class OptimRow(C.Structure):            # one row of the device table (zigma_amd/optim.py writes the rows as eight int64)
+    _fields_ = [(n, vp) for n in ("p", "g", "m", "v", "ema", "shadow")] + [("numel", i64), ("pad_", i64)]
+
+
+class OptimState(C.Structure):          # the device state block (eight 4-byte words)
+    _fields_ = [("step", f32), ("skipped", i32), ("grad_norm", f32), ("grad_mult", f32), ("step_size", f32), ("bc2_sqrt", f32), ("pad_", i32 * 2)]
+
+
+class OptimParams(C.Structure):
+    _fields_ = ([("table", vp), ("chunk_map", vp), ("n_entries", i64), ("n_chunks", i64), ("partials", vp), ("state", vp), ("grad_scale", vp), ("found_inf", vp)]
+                + [(n, f64) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm", "ema_decay")]
+                + [("shadow_dtype", i32), ("chunk", i32), ("flags", i32), ("pad_", i32)])
+
+
+EXPORTS = ("zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw", "zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
            "zigma_selective_scan_bwd_workspace_bytes", "zigma_causal_conv1d_bwd",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
@@ -217,7 +231,8 @@ def lib():
                          ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_skinny_linear_fwd", SkinnyParams), ("zigma_x_proj_fwd", XProjParams),
                          ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
                          ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams),
-                         ("zigma_multi_cast_fwd", MultiCastParams)):
+                         ("zigma_multi_cast_fwd", MultiCastParams), ("zigma_optim_grad_sumsq", OptimParams), ("zigma_optim_prepare", OptimParams),
+                         ("zigma_optim_adamw", OptimParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st), vp]
             fn.restype = C.c_int

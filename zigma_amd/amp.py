@@ -10,7 +10,8 @@ read matrix operands of ONE 16-bit type, so an fp32 model under autocast needs 1
                      zigma_multi_cast_fwd launch when a registered parameter's (_version, data_ptr()) has moved since the last refresh, or an
                      optimizer has stepped since (torch's fused optimizers update parameters WITHOUT moving _version, so the package installs
                      a global optimizer-step hook at import that counts steps: step_count()) — once per optimizer step; two forwards without a step in between, or a
-                     step that a GradScaler skipped, cast nothing.  An unregistered fp32 parameter gets a one-entry launch of
+                     step that a GradScaler skipped, cast nothing; nor does a forward after a step of zigma_amd.optim.FusedAdamW, which writes the
+                     shadows in its own pass (written_by_step).  An unregistered fp32 parameter gets a one-entry launch of
                      the same kernel; what the kernel does not take (non-contiguous, not fp32, not on a GPU) takes `.to()`
   operands(x, w, b)  what a projection under autocast reads: the shadows of (w, b) if x is already in the autocast type and w is fp32, else (w, b)
 
@@ -162,6 +163,18 @@ class _Group:
         multi_cast(a["table"], a["cmap"], len(self.params), len(self.cmap_rows), dtype, a["arena"].device)
         a["keys"] = [(_EPOCH[0], p._version, q) for p, q in zip(self.params, ptrs)]
         STATS["refresh_launches"] += 1
+
+    def fresh(self, dtype):
+        """does the `dtype` arena hold the parameters as they are now — would get() hand out every shadow without a refresh?"""
+        a = self.arenas.get(dtype)
+        return a is not None and all(k == (_EPOCH[0], p._version, p.data_ptr()) for k, p in zip(a["keys"], self.params))
+
+    def written_by_step(self, dtype):
+        """an optimizer that writes the shadows itself (zigma_amd.optim.FusedAdamW) records, inside its step(), that the arena holds the parameters
+        as of the step BEING taken: the keys carry the count the optimizer-step hook is about to reach, so the next forward refreshes nothing.
+        Only for an arena that was fresh() before the step: a step the device skipped then leaves parameters and arena alike untouched."""
+        a = self._arena(dtype)
+        a["keys"] = [(_EPOCH[0] + 1, p._version, p.data_ptr()) for p in self.params]
 
 
 def matrix_parameters(module):

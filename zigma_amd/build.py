@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libzigma_hip.so")
 SOURCES = ["api.hip", "selective_scan.hip", "scan_tok_bf16.hip", "scan_tok_f16.hip", "scan_tok_f32.hip",
-           "causal_conv1d.hip", "add_norm.hip", "dt_proj.hip", "scan_bwd.hip", "conv_bwd.hip", "norm_bwd.hip", "cross_attn.hip", "cross_attn_bwd.hip", "x_proj.hip", "linear.hip", "linear4w.hip", "linear_ws.hip", "linear_sm.hip", "conv_x_proj.hip", "glue_bwd.hip", "embed.hip", "skinny_linear.hip", "calib.hip", "wgrad.hip", "linear_split.hip", "norm_linear.hip", "multi_cast.hip"]
+           "causal_conv1d.hip", "add_norm.hip", "dt_proj.hip", "scan_bwd.hip", "conv_bwd.hip", "norm_bwd.hip", "cross_attn.hip", "cross_attn_bwd.hip", "x_proj.hip", "linear.hip", "linear4w.hip", "linear_ws.hip", "linear_sm.hip", "conv_x_proj.hip", "glue_bwd.hip", "embed.hip", "skinny_linear.hip", "calib.hip", "wgrad.hip", "linear_split.hip", "norm_linear.hip", "multi_cast.hip", "optim_step.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-fno-slp-vectorize",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
@@ -32,8 +32,10 @@ _RES = ["-Rpass-analysis=kernel-resource-usage"]
 # norm_linear_kernel (csrc/norm_linear.hip) holds its 32 rows as MFMA fragments (up to 192 registers) next to the accumulators of a pass at two waves per SIMD:
 # a silent spill would decide its speed, so the same check.
 # multi_cast_kernel (csrc/multi_cast.hip) is a pure stream of 16-byte accesses: scratch traffic would come straight off its copy rate, so the same check.
-SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES, "linear_split.hip": _RES, "norm_linear.hip": _RES, "multi_cast.hip": _RES}
-NO_SCRATCH_KERNELS = ("scan_tok2_kernel", "wgrad_kernel", "wgrad_reduce_kernel", "linear_split_kernel", "norm_linear_kernel", "multi_cast_kernel")
+# multi_sumsq_kernel and multi_adamw_kernel (csrc/optim_step.hip) stream up to ten 16-byte accesses per lane and iteration and hold 40 values between them: the same check.
+SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES, "linear_split.hip": _RES, "norm_linear.hip": _RES, "multi_cast.hip": _RES, "optim_step.hip": _RES}
+NO_SCRATCH_KERNELS = ("scan_tok2_kernel", "wgrad_kernel", "wgrad_reduce_kernel", "linear_split_kernel", "norm_linear_kernel", "multi_cast_kernel", "multi_sumsq_kernel",
+                      "multi_adamw_kernel")
 
 
 def check_no_scratch(remarks, src):

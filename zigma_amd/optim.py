@@ -1,0 +1,296 @@
+"""The tail of a training step on the own kernels: global-norm gradient clipping, AdamW, the parameters' moving average (EMA) and the refresh of their
+16-bit shadows in ONE pass over the parameters (csrc/optim_step.hip, zigma_optim_* in include/zigma_hip.h).
+
+The reference's step is `opt.step()` -> `grad_clip(...)` -> `update_ema(ema_model, model)` (train_acc.py:443-448, utils/train_utils.py:103-133): a fused
+AdamW, a norm pass plus a scaling pass, two small launches per parameter for the EMA, and — under autocast here — the cast of amp._Group.refresh.  Here a
+device table names every parameter's (p, grad, exp_avg, exp_avg_sq, ema, shadow) and a chunk map names each workgroup's piece, as zigma_multi_cast_fwd
+does, and a step is three launches: the gradients' sum of squares, one workgroup that turns it into the step's scalars ON THE DEVICE (norm, clip
+coefficient, skip-on-overflow, the step counter, the bias corrections), and the update.  Nothing comes back to the host, so a step never waits for the
+device and can be captured in a graph.
+
+Two deliberate differences from the reference loop, both stated in DESIGN.md §6.3:
+  * the clip comes BEFORE the update (the reference clips after `opt.step()`, which scales gradients that the next `zero_grad` throws away);
+  * a non-finite gradient norm SKIPS the step — parameters, both moments, the EMA, the shadows and the step counter keep their bits — where
+    `clip_grad_norm_` would multiply every gradient by NaN and poison the parameters.  `opt.skipped` reports it.
+
+There is no fallback: parameters that are not contiguous fp32 tensors on one GPU are refused at construction."""
+import torch
+
+from . import _lib, amp
+
+CHUNK = amp.CHUNK         # elements per workgroup (256 lanes x 8 elements x 2 rounds), the cast kernel's
+STATS = {"steps": 0, "launches": 0, "table_builds": 0}
+
+
+def _device_ok(t):
+    return t.is_cuda
+
+
+def _check_tensor(t, what, device=None, shape=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"FusedAdamW: {what} is not a tensor")
+    if t.layout != torch.strided:
+        raise ValueError(f"FusedAdamW: {what} is sparse; the kernel takes dense tensors only")
+    if t.dtype != torch.float32:
+        raise ValueError(f"FusedAdamW: {what} is {t.dtype}; the kernel takes float32 only (keep fp32 master parameters and train under torch.autocast)")
+    if not _device_ok(t):
+        raise ValueError(f"FusedAdamW: {what} is on {t.device}; the kernel needs a GPU (there is no CPU fallback)")
+    if device is not None and t.device != device:
+        raise ValueError(f"FusedAdamW: {what} is on {t.device}, the parameters are on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"FusedAdamW: {what} is not contiguous")
+    if shape is not None and t.shape != shape:
+        raise ValueError(f"FusedAdamW: {what} has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
+
+
+def arena_views(like, device):
+    """one zero-filled fp32 arena with a 256-byte slot per tensor of `like` (amp.arena_layout) -> (arena, [view shaped like each tensor])"""
+    numels = [t.numel() for t in like]
+    offsets, nbytes = amp.arena_layout(numels, itemsize=4)
+    arena = torch.zeros(max(nbytes, amp.SLOT_ALIGN) + amp.SLOT_ALIGN, device=device, dtype=torch.uint8)
+    arena = arena[(-arena.data_ptr()) % amp.SLOT_ALIGN:][:max(nbytes, amp.SLOT_ALIGN)]
+    return arena, [arena[o:o + 4 * n].view(torch.float32).view(t.shape) for t, o, n in zip(like, offsets, numels)]
+
+
+def step_rows(params, grads, ms, vs, emas, shadows):
+    """the table's rows, one per parameter that has a gradient (torch's optimizers skip the others too): eight int64 each, zigma_optim_row_t.
+    Anything with data_ptr() and numel() will do."""
+    rows = []
+    for i, (p, g) in enumerate(zip(params, grads)):
+        if g is None:
+            continue
+        ema, sh = (emas[i] if emas else None), (shadows[i] if shadows else None)
+        rows.append((p.data_ptr(), g.data_ptr(), ms[i].data_ptr(), vs[i].data_ptr(), 0 if ema is None else ema.data_ptr(), 0 if sh is None else sh.data_ptr(),
+                     p.numel(), 0))
+    return rows
+
+
+class StepTables:
+    """the device table, chunk map and partial-sum buffer of a step, rebuilt and uploaded only when the host list of rows has moved (compared every
+    step; `zero_grad(set_to_none=False)` keeps the gradients' addresses, so in a steady loop nothing is uploaded or allocated)"""
+
+    def __init__(self, chunk=CHUNK):
+        self.chunk, self.rows, self.numels = chunk, None, None
+        self.table = self.cmap = self.partials = None
+        self.n_chunks = self.builds = 0
+
+    def update(self, rows, device):
+        """-> True if anything was uploaded"""
+        if rows == self.rows:
+            return False
+        numels = [r[6] for r in rows]
+        if numels != self.numels:
+            cmap = amp.build_chunk_map(numels, self.chunk)
+            self.cmap = torch.tensor(cmap or [(0, 0)], dtype=torch.int64).to(device)
+            self.partials = torch.zeros(max(len(cmap), 1), dtype=torch.float32, device=device)
+            self.n_chunks, self.numels = len(cmap), numels
+        self.table = torch.tensor(rows or [(0,) * 8], dtype=torch.int64).to(device)       # (the old table stays alive until here, past its last launch)
+        self.rows = rows
+        self.builds += 1
+        return True
+
+
+class FusedAdamW(torch.optim.Optimizer):
+    """AdamW (decoupled weight decay, torch.optim.AdamW's formulas) with global-norm clipping, an EMA of the parameters and the 16-bit shadows of
+    zigma_amd.amp in one pass, three launches per step (two without clipping), no host synchronisation.
+
+      max_grad_norm  None: no norm pass, no clipping.  Else the gradients are scaled by min(1, max_grad_norm / (norm + 1e-6)), the formula of
+                     `clip_grad_norm_`, BEFORE the update (the reference clips after its step); the gradients themselves are never written.
+      ema_params     tensors parallel to `params`, or a module whose parameters() are (`copy.deepcopy(model)`): ema += (p_new - ema) * (1 - ema_decay),
+                     in place where they live.
+      shadows        a module that carries (or can carry) a zigma_amd.amp group, or (module, torch.bfloat16 / torch.float16); a bare module means
+                     bf16.  The step writes the registered parameters' shadows itself, and the next autocast forward casts nothing.
+
+    A step whose gradient norm is not finite, or for which a GradScaler found an inf, is SKIPPED on the device: nothing is written and the step counter
+    stays (where `clip_grad_norm_` would have poisoned the parameters).  `opt.grad_norm` and `opt.skipped` are device tensors of the last step
+    (`grad_norm` is NaN without clipping); reading them is the caller's synchronisation, the step has none.
+
+    One parameter group; contiguous fp32 parameters on one GPU; no amsgrad, no maximize, no sparse gradients — anything else raises.  `lr` and the other
+    hyperparameters are host values handed to each launch: a captured graph (torch.cuda.graph) bakes them in, and a schedule needs a re-capture.
+    Capture after one eager step, with `zero_grad(set_to_none=False)` (this class's default), so that the tables exist and the addresses stay.
+
+    state[p] has torch's keys: "exp_avg" / "exp_avg_sq" are views of two fp32 arenas, "step" is ONE device scalar shared by all parameters.
+    state_dict() hands out copies with a step per parameter and loads into torch.optim.AdamW(fused=True); load_state_dict() takes that one's, and
+    raises if its per-parameter steps disagree."""
+
+    _step_supports_amp_scaling = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_params=None, ema_decay=0.9999,
+                 shadows=None, *, amsgrad=False, maximize=False):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("FusedAdamW: lr is a host value per launch, not a tensor")
+        if not 0.0 <= lr < float("inf"):
+            raise ValueError(f"FusedAdamW: invalid lr {lr}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdamW: betas {betas} outside [0, 1)")
+        if not 0.0 < eps < float("inf"):
+            raise ValueError(f"FusedAdamW: eps must be positive, got {eps}")
+        if not 0.0 <= weight_decay < float("inf"):
+            raise ValueError(f"FusedAdamW: invalid weight_decay {weight_decay}")
+        if max_grad_norm is not None and not 0.0 < max_grad_norm < float("inf"):
+            raise ValueError(f"FusedAdamW: max_grad_norm must be positive or None, got {max_grad_norm}")
+        if not 0.0 <= ema_decay <= 1.0:
+            raise ValueError(f"FusedAdamW: ema_decay {ema_decay} outside [0, 1]")
+        # (the keys torch.optim.AdamW's groups carry, so that a state_dict travels both ways)
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
+                        differentiable=False, fused=True, decoupled_weight_decay=True)
+        super().__init__(params, defaults)
+        self._check_group()
+        ps = self.param_groups[0]["params"]
+        for i, p in enumerate(ps):
+            _check_tensor(p, f"parameter {i}", ps[0].device)
+        self.device = ps[0].device
+        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
+        self._ema = None
+        if ema_params is not None:
+            ema = list(ema_params.parameters()) if isinstance(ema_params, torch.nn.Module) else list(ema_params)
+            if len(ema) != len(ps):
+                raise ValueError(f"FusedAdamW: {len(ema)} ema tensors for {len(ps)} parameters")
+            for i, (e, p) in enumerate(zip(ema, ps)):
+                _check_tensor(e, f"ema tensor {i}", self.device, p.shape)
+                if e.data_ptr() == p.data_ptr() and p.numel():
+                    raise ValueError(f"FusedAdamW: ema tensor {i} IS parameter {i}; pass a copy (copy.deepcopy(model))")
+            self._ema = ema
+        self._shadow_module, self._shadow_dtype, self._grp, self._shadow_list = None, None, None, None
+        if shadows is not None:
+            mod, dt = shadows if isinstance(shadows, (tuple, list)) else (shadows, torch.bfloat16)
+            if not isinstance(mod, torch.nn.Module) or dt not in (torch.bfloat16, torch.float16):
+                raise ValueError("FusedAdamW: shadows is a module or (module, torch.bfloat16 / torch.float16)")
+            self._shadow_module, self._shadow_dtype = mod, dt
+        self._m_arena, self._m = arena_views(ps, self.device)
+        self._v_arena, self._v = arena_views(ps, self.device)
+        self._block = torch.zeros(8, dtype=torch.float32, device=self.device)             # zigma_optim_state_t
+        self._tables = StepTables()
+        self._install_state()
+
+    # ---- one group, torch's state keys ------------------------------------------------------------------------------------------------------------
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError("FusedAdamW: one parameter group only (the gradient norm is global; the reference trains with one group)")
+        super().add_param_group(param_group)
+
+    def _check_group(self):
+        g = self.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("FusedAdamW: amsgrad and maximize are not implemented by the kernel")
+        if g.get("decoupled_weight_decay") is False:
+            raise ValueError("FusedAdamW: the kernel's weight decay is decoupled (AdamW); this group asks for Adam's L2 form")
+        if isinstance(g["lr"], torch.Tensor):
+            raise ValueError("FusedAdamW: lr is a host value per launch, not a tensor")
+
+    @property
+    def step_count(self):
+        """the shared device step counter (fp32 scalar, like the steps of torch's fused / capturable optimizers)"""
+        return self._block[0]
+
+    @property
+    def skipped(self):
+        """device int32 scalar: 1 if the last step changed nothing (non-finite norm or GradScaler's found_inf)"""
+        return self._block.view(torch.int32)[1]
+
+    @property
+    def grad_norm(self):
+        """device fp32 scalar: the last step's global gradient norm before clipping, unscaled (NaN when max_grad_norm is None)"""
+        return self._block[2]
+
+    def _install_state(self):
+        for p, m, v in zip(self.param_groups[0]["params"], self._m, self._v):
+            self.state[p] = {"step": self._block[0], "exp_avg": m, "exp_avg_sq": v}
+
+    def state_dict(self):
+        """torch's layout.  Every tensor is a COPY (the live ones are views of the arenas and one shared step, which another optimizer must not
+        alias), and each parameter gets a step of its own, as torch.optim.AdamW keeps them."""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (t.clone() if isinstance(t, torch.Tensor) else t) for n, t in st.items()} for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        if len(self.param_groups) != 1:
+            raise ValueError("FusedAdamW: one parameter group only")
+        self._check_group()
+        ps = self.param_groups[0]["params"]
+        loaded = [self.state[p] if p in self.state and len(self.state[p]) else None for p in ps]
+        steps = [torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()) for st in loaded if st is not None]
+        steps = torch.stack(steps).tolist() if steps else []
+        if len(set(steps)) > 1 or (steps and steps[0] != 0 and len(steps) != len(ps)):
+            raise ValueError("FusedAdamW: the loaded per-parameter steps disagree (or some parameters have none); this optimizer keeps ONE step counter: "
+                             f"{sorted(set(steps))}, {len(steps)} of {len(ps)} parameters")
+        for st, m, v in zip(loaded, self._m, self._v):
+            if st is None:
+                m.zero_()
+                v.zero_()
+            else:
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+        self._block.zero_()
+        self._block[0] = steps[0] if steps else 0.0
+        self.state.clear()
+        self._install_state()
+
+    def zero_grad(self, set_to_none=False):
+        """zeroes the gradients in place by default, so that their addresses — and with them the device table — stay put"""
+        super().zero_grad(set_to_none=set_to_none)
+
+    # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
+    def _shadows_now(self):
+        """per parameter, its slot in the module's shadow arena (or None), and that arena's group"""
+        mod = self._shadow_module
+        if mod is None:
+            return None, None
+        if not amp.attached(mod):
+            amp.attach(mod)
+        grp = mod.__dict__["_amp_group"]
+        if grp is not self._grp:
+            slot = {id(q): s for q, s in zip(grp.params, grp._arena(self._shadow_dtype)["shadows"])}
+            self._grp, self._shadow_list = grp, [slot.get(id(p)) for p in self.param_groups[0]["params"]]
+        return self._shadow_list, grp
+
+    def _scaler_scalar(self, name):
+        t = getattr(self, name, None)               # (set by torch.amp.GradScaler.step around the call, grad_scaler.py: `optimizer.grad_scale = ...`)
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.numel() == 1 and t.device == self.device):
+            raise RuntimeError(f"FusedAdamW: {name} must be a one-element float32 tensor on {self.device}")
+        return t
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        self._check_group()
+        ps = g["params"]
+        grads = [p.grad for p in ps]
+        for i, (p, gr) in enumerate(zip(ps, grads)):
+            if gr is not None and (gr.dtype != torch.float32 or gr.layout != torch.strided or gr.device != p.device or gr.shape != p.shape or not gr.is_contiguous()
+                                   or not p.is_contiguous()):
+                raise RuntimeError(f"FusedAdamW: parameter {i} or its gradient is not a dense contiguous float32 tensor on {self.device}")
+        shadows, grp = self._shadows_now()
+        rows = step_rows(ps, grads, self._m, self._v, self._ema, shadows)
+        if not rows:
+            return loss
+        T = self._tables
+        STATS["table_builds"] += T.update(rows, self.device)
+        grad_scale, found_inf = self._scaler_scalar("grad_scale"), self._scaler_scalar("found_inf")
+        P = _lib.OptimParams()
+        P.table, P.chunk_map, P.n_entries, P.n_chunks = T.table.data_ptr(), T.cmap.data_ptr(), len(rows), T.n_chunks
+        P.state, P.grad_scale, P.found_inf = self._block.data_ptr(), _lib.ptr(grad_scale), _lib.ptr(found_inf)
+        P.lr, (P.beta1, P.beta2), P.eps, P.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        P.max_grad_norm, P.ema_decay = self.max_grad_norm or 0.0, self.ema_decay
+        P.shadow_dtype, P.chunk, P.flags = (_lib._DT[self._shadow_dtype] if shadows else -1), T.chunk, 0
+        # were the shadows current before this step?  Then they are current after it: written by the kernel, or — a skipped step — as unchanged as the
+        # parameters.  If they were stale, a skipped step would leave them stale, so nothing is recorded and the next forward refreshes as ever.
+        fresh = grp is not None and grp.fresh(self._shadow_dtype)
+        if self.max_grad_norm is not None:
+            P.partials = T.partials.data_ptr()
+            _lib.call("zigma_optim_grad_sumsq", P, self.device)
+        _lib.call("zigma_optim_prepare", P, self.device)
+        _lib.call("zigma_optim_adamw", P, self.device)
+        if fresh:
+            grp.written_by_step(self._shadow_dtype)
+        STATS["steps"] += 1
+        STATS["launches"] += 3 if self.max_grad_norm is not None else 2
+        return loss
