@@ -42,7 +42,8 @@ extern "C" {
                                * (10, no block changed): zigma_norm_linear_fwd / zigma_norm_linear_params_t added
                                * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added
                                * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added
-                               * (11, no block changed): zigma_optim_* added */
+                               * (11, no block changed): zigma_optim_* added
+                               * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -688,6 +689,49 @@ int zigma_patch_embed_fwd(const zigma_patch_embed_params_t *p, void *stream);
 int zigma_timestep_embed_fwd(const zigma_timestep_embed_params_t *p, void *stream);
 int zigma_final_layer_fwd(const zigma_final_layer_params_t *p, void *stream);
 int zigma_skinny_linear_fwd(const zigma_skinny_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The final layer of a GUIDED evaluation (classifier-free guidance; csrc/embed.hip).  (ABI 11, no block changed.)  The reference has no such
+ * entry: its forward_with_cfg is a stub (model_zigma.py:992-993).  For every row pair (x_cond[r], x_uncond[r]), r < rows:
+ *
+ *   y_c, y_u = bf16(LayerNorm(x, no affine, eps))                      statistics, rounding and dot product exactly as zigma_final_layer_fwd
+ *   vc = w y_c + bias,  vu = w y_u + bias                              fp32 accumulators
+ *   out = round_to(out_dtype, fma(scale[n], vc - vu, vu))              ONE rounding; n = r / rows_per_sample
+ *
+ * stored in the unpatchified latent layout (the index map of unpatchify / unpatchify_video, model_zigma.py:585-598): row r is token (h, w) of
+ * frame f of sample n (f = (r % rows_per_sample) / tokens_per_frame, h = token / grid_w, w = token % grid_w), and its output
+ * o = (i * patch + j) * chans + c goes to out[n * out_sample_stride + f * out_frame_stride + c * out_chan_stride + (h * patch + i) * out_row_stride
+ * + w * patch + j] (element strides, 64-bit offsets; images are one frame).  Neither a 16-bit velocity tensor, nor the permuting copy, the cast, the
+ * split or the combination exist as launches.
+ *   x_cond, x_uncond  bf16 (rows, cols), rows of pitch x_row_stride: the two halves of one (2B, L, E) tensor; the same pointer twice is legal
+ *   weight, bias      bf16 (n_out, cols) contiguous, (n_out) or NULL
+ *   scale             DEVICE pointer, fp32, rows / rows_per_sample values (one per sample): a captured graph follows a value changed in place
+ *   out               out_dtype: ZIGMA_F32 or ZIGMA_BF16
+ *   y_out             NULL, or bf16 (2 rows, cols) contiguous, 16-byte aligned: receives the bf16 LayerNorm rows, cond rows first (a test hook)
+ * Limits: those of zigma_final_layer_fwd (cols % 8 == 0, cols <= 2048, n_out <= 16, x rows and weight 16-byte aligned).
+ * Checked in this order, before any launch: NULL block ZIGMA_ERR_NULL; rows < 0, cols < 8, n_out < 1 ZIGMA_ERR_SHAPE; flags != 0
+ * ZIGMA_ERR_UNSUPPORTED; dtype other than ZIGMA_BF16, out_dtype other than ZIGMA_F32 / ZIGMA_BF16 ZIGMA_ERR_DTYPE; cols % 8, cols > 2048,
+ * n_out > 16, a geometry field < 1, n_out != patch^2 chans, rows % rows_per_sample, rows_per_sample % tokens_per_frame, tokens_per_frame % grid_w
+ * ZIGMA_ERR_SHAPE; rows == 0 ZIGMA_OK, nothing touched; NULL x_cond / x_uncond / weight / scale / out ZIGMA_ERR_NULL; alignment ZIGMA_ERR_STRIDE.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct zigma_final_layer_cfg_params {
+    int64_t rows;            /* rows of EACH half */
+    int32_t cols, n_out;
+    int32_t dtype;           /* ZIGMA_BF16: x_cond, x_uncond, weight, bias, y_out */
+    int32_t out_dtype;       /* ZIGMA_F32 or ZIGMA_BF16 */
+    int32_t flags;           /* reserved, must be 0 */
+    float eps;
+    int32_t rows_per_sample, tokens_per_frame, grid_w, patch, chans;
+    int32_t pad_;
+    int64_t x_row_stride;
+    int64_t out_sample_stride, out_frame_stride, out_chan_stride, out_row_stride;   /* the pixel column stride is 1 */
+    const void *x_cond, *x_uncond, *weight, *bias;
+    const float *scale;
+    void *out;
+    void *y_out;
+} zigma_final_layer_cfg_params_t;
+
+int zigma_final_layer_cfg_fwd(const zigma_final_layer_cfg_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Box calibration (bench.py `box_calib`; csrc/calib.hip).  NOT part of the drop-in surface: no reference interface maps to it.  Two fixed

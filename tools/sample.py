@@ -5,10 +5,13 @@
     python tools/sample.py --config '{"in_channels":4,"img_dim":32,"embed_dim":640,"depth":18,"scan_type":"zigzagN8","use_pe":2}' \
         [--ckpt model.pt] --num-samples 256 --batch 64 --steps 50 --method euler --out samples.pt
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/sample.py ...   # batch-sharded
+    python tools/sample.py --config '{..., "num_classes": 1000, "class_dropout_prob": 0.1}' --class-label 207 --cfg-scale 4   # classifier-free guidance
 
 One process per GPU, the global batch split over the ranks, per-rank seed = seed + rank, no collective inside the ODE loop,
 one all_gather of the finished latents per batch (zigma_amd/sharded_sampling.py).  `--graph` replays the denoiser as a
-hipGraph (worth it for small per-GPU batches, where eager launches are host-bound).  Checkpoints of the reference load
+hipGraph (worth it for small per-GPU batches, where eager launches are host-bound).  `--cfg-scale S` samples with classifier-free guidance
+(zigma_amd.guidance.Guided over ZigMa.forward_guided: both halves in one pass through the blocks, combined inside the final-layer kernel); the null
+condition is the model's null class (class_dropout_prob > 0 in --config) or --null-label.  Checkpoints of the reference load
 unchanged ("ema" / "model" / plain state_dict)."""
 import argparse
 import json
@@ -37,6 +40,9 @@ def main():
                     help="--dtype fp32 only: the block projections as three (high) or one (medium) bf16 matrix-core products instead of the "
                          "library's fp32 GEMM (zigma_amd.set_float32_matmul_precision); a bf16 model does not read it")
     ap.add_argument("--class-label", type=int, default=None, help="class-conditional models: the label to sample")
+    ap.add_argument("--cfg-scale", type=float, default=None, metavar="S",
+                    help="with --class-label: classifier-free guidance, v_u + S (v_c - v_u); 2 x the per-GPU batch goes through the blocks")
+    ap.add_argument("--null-label", type=int, default=None, help="--cfg-scale: the label that stands for 'no class' (default: the model's null class)")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--decode", default="none", choices=["none", "standin"],
                     help="standin: decode -> uint8 on the device inside the timed path (zigma_amd.postprocess; a 4->3 channel 8x "
@@ -71,9 +77,16 @@ def main():
         kw["y"] = torch.full((nb,), args.class_label, device=device, dtype=torch.long)
     sample_fn = Sampler(create_transport(args.path, args.prediction)).sample_ode(sampling_method=args.method, num_steps=args.steps)
     model_fn = model.forward
+    if args.cfg_scale is not None:
+        if args.class_label is None:
+            raise SystemExit("tools/sample.py: --cfg-scale needs --class-label")
+        from zigma_amd.guidance import Guided
+        model_fn = Guided(model, args.cfg_scale, y_null=args.null_label)
+    elif args.null_label is not None:
+        raise SystemExit("tools/sample.py: --null-label goes with --cfg-scale")
     if args.graph:
         z0 = torch.zeros((nb,) + shape, device=device)
-        model_fn = GraphedForward(model, z0, torch.zeros(nb, device=device), kw.get("y"))
+        model_fn = GraphedForward(model_fn, z0, torch.zeros(nb, device=device), kw.get("y"))
     dec = None
     if args.decode == "standin":
         from zigma_amd import postprocess as pp
@@ -92,7 +105,7 @@ def main():
     if rank == 0:
         x = torch.cat(outs)[:args.num_samples]
         print(json.dumps(dict(samples=int(x.shape[0]), shape=list(x.shape[1:]), seconds=round(dt, 3),
-                              samples_per_s=round(x.shape[0] / dt, 2), world=world, decode=args.decode,
+                              samples_per_s=round(x.shape[0] / dt, 2), world=world, decode=args.decode, cfg_scale=args.cfg_scale,
                               finite=bool(torch.isfinite(x.float()).all()))))
         if args.out:
             torch.save(x, args.out)

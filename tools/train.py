@@ -5,6 +5,7 @@ model — synthetic latents, no dataloader / EMA / wandb.  Forward AND backward 
 
     python tools/train.py --config '{...}' --batch 32 --steps 20
     python tools/train.py --config '{...}' --amp bf16 --fused-step --max-grad-norm 2.0      # the step's tail on the own kernels
+    python tools/train.py --config '{..., "num_classes": 1000}' --class-dropout 0.1          # label dropout: a model that can be guided
 
 --fused-step: the reference's `opt.step()` / `grad_clip` / `update_ema` (train_acc.py:443-448) as zigma_amd.optim.FusedAdamW — AdamW, global-norm
 clipping (before the update), an EMA copy of the model and, under --amp, the 16-bit shadows in one pass, three launches, no host sync.  Without the flag
@@ -39,6 +40,9 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None, help="--fused-step: clip the global gradient norm to this before the update")
     ap.add_argument("--ema-decay", type=float, default=0.9999, help="--fused-step: decay of the EMA copy")
     ap.add_argument("--time-tail", action="store_true", help="--fused-step: HIP events around every optimizer step (adds no sync inside the loop)")
+    ap.add_argument("--class-dropout", type=float, default=None, metavar="P",
+                    help="class-conditional models: drop the label to the null class with probability P (ZigMa class_dropout_prob; the model can then be guided: "
+                         "tools/sample.py --cfg-scale)")
     ap.add_argument("--bucket-mb", type=int, default=100, help="DDP bucket size: xGMI rings are per-link bound, few large buckets")
     args = ap.parse_args()
 
@@ -53,6 +57,10 @@ def main():
     device = torch.device("cuda", local_rank)
     rank, world, _ = ss.init_from_env(backend="nccl", device=device)
     cfg = json.loads(args.config)
+    if args.class_dropout is not None:
+        if not cfg.get("num_classes", -1) > 0:
+            raise SystemExit("tools/train.py: --class-dropout needs a class-conditional model (num_classes in --config)")
+        cfg["class_dropout_prob"] = args.class_dropout
     torch.manual_seed(0)
     mdtype = torch.float32 if args.amp != "off" else torch.bfloat16 if args.dtype == "bf16" else torch.float32
     model = ZigMa(device=device, dtype=mdtype, **cfg).train()

@@ -1,10 +1,10 @@
 """ONE environment switch for the A/B tools instead of one per threshold: ZIGMA_KNOBS="module.NAME=value,module.NAME=value" overrides module-level
-routing constants of this package at import (module = routing | mamba_simple | model_zigma | selective_scan_interface | wgrad | fp32_matmul | amp: MODULES).  Only these
+routing constants of this package at import (module = routing | mamba_simple | model_zigma | selective_scan_interface | wgrad | fp32_matmul | amp | embed: MODULES).  Only these
 modules and names that already exist can be set (a typo raises), values are parsed as int, float, True / False or left as strings.  The
 shipped defaults are the constants in the modules; nothing in the product path reads any other new environment variable (the older per-feature switches are listed in DESIGN.md §3.5)."""
 import os
 
-MODULES = ("routing", "mamba_simple", "model_zigma", "selective_scan_interface", "wgrad", "fp32_matmul", "amp")      # the modules that call apply()
+MODULES = ("routing", "mamba_simple", "model_zigma", "selective_scan_interface", "wgrad", "fp32_matmul", "amp", "embed")      # the modules that call apply()
 
 
 def _parse(v):

@@ -135,6 +135,13 @@ class FinalLayerParams(C.Structure):
                  ("x_row_stride", i64), ("out_row_stride", i64)] + [(n, vp) for n in ("x", "weight", "bias", "out")])
 
 
+class FinalLayerCfgParams(C.Structure):
+    _fields_ = ([("rows", i64), ("cols", i32), ("n_out", i32), ("dtype", i32), ("out_dtype", i32), ("flags", i32), ("eps", f32)]
+                + [(n, i32) for n in ("rows_per_sample", "tokens_per_frame", "grid_w", "patch", "chans", "pad_")]
+                + [(n, i64) for n in ("x_row_stride", "out_sample_stride", "out_frame_stride", "out_chan_stride", "out_row_stride")]
+                + [(n, vp) for n in ("x_cond", "x_uncond", "weight", "bias", "scale", "out", "y_out")])
+
+
 class SkinnyParams(C.Structure):
     _fields_ = ([(n, i32) for n in ("m", "n", "k", "dtype", "flags", "pad_")] + [(n, i64) for n in ("x_row_stride", "w_row_stride", "out_row_stride")]
                 + [(n, vp) for n in ("x", "w", "bias", "out")])
@@ -208,7 +215,7 @@ EXPORTS = ("zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
            "zigma_cross_attn_bwd", "zigma_cross_attn_bwd_chunks", "zigma_patch_embed_fwd", "zigma_timestep_embed_fwd", "zigma_final_layer_fwd",
-           "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel",
+           "zigma_final_layer_cfg_fwd", "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel",
            "zigma_selective_scan_fwd_plan", "zigma_causal_conv1d_fwd_plan", "zigma_conv_x_proj_fwd_plan", "zigma_x_proj_fwd_plan",
            "zigma_dt_proj_softplus_fwd_plan")
 
@@ -228,7 +235,7 @@ def lib():
                          ("zigma_add_norm_fwd", NormParams), ("zigma_dt_proj_softplus_fwd", DtProjParams),
                          ("zigma_selective_scan_bwd", ScanBwdParams), ("zigma_causal_conv1d_bwd", ConvBwdParams),
                          ("zigma_add_norm_bwd", NormBwdParams), ("zigma_cross_attn_fwd", XAttnParams), ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_patch_embed_fwd", PatchEmbedParams),
-                         ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_skinny_linear_fwd", SkinnyParams), ("zigma_x_proj_fwd", XProjParams),
+                         ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_final_layer_cfg_fwd", FinalLayerCfgParams), ("zigma_skinny_linear_fwd", SkinnyParams), ("zigma_x_proj_fwd", XProjParams),
                          ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
                          ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams),
                          ("zigma_multi_cast_fwd", MultiCastParams), ("zigma_optim_grad_sumsq", OptimParams), ("zigma_optim_prepare", OptimParams),

@@ -32,10 +32,12 @@ _RES = ["-Rpass-analysis=kernel-resource-usage"]
 # norm_linear_kernel (csrc/norm_linear.hip) holds its 32 rows as MFMA fragments (up to 192 registers) next to the accumulators of a pass at two waves per SIMD:
 # a silent spill would decide its speed, so the same check.
 # multi_cast_kernel (csrc/multi_cast.hip) is a pure stream of 16-byte accesses: scratch traffic would come straight off its copy rate, so the same check.
+# final_layer_cfg_kernel (csrc/embed.hip) keeps a row of up to 2048 features (128 registers per lane) through two statistics passes and the dot products, twice per
+# output: the same check.
 # multi_sumsq_kernel and multi_adamw_kernel (csrc/optim_step.hip) stream up to ten 16-byte accesses per lane and iteration and hold 40 values between them: the same check.
-SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES, "linear_split.hip": _RES, "norm_linear.hip": _RES, "multi_cast.hip": _RES, "optim_step.hip": _RES}
+SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES, "linear_split.hip": _RES, "norm_linear.hip": _RES, "multi_cast.hip": _RES, "optim_step.hip": _RES, "embed.hip": _RES}
 NO_SCRATCH_KERNELS = ("scan_tok2_kernel", "wgrad_kernel", "wgrad_reduce_kernel", "linear_split_kernel", "norm_linear_kernel", "multi_cast_kernel", "multi_sumsq_kernel",
-                      "multi_adamw_kernel")
+                      "multi_adamw_kernel", "final_layer_cfg_kernel")
 
 
 def check_no_scratch(remarks, src):

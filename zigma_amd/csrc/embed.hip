@@ -1,5 +1,6 @@
 // The small per-forward operators around the blocks, gfx950: patch embedding (+ bias + position table), sinusoidal timestep
-// features, final LayerNorm + output projection.  C ABI: zigma_patch_embed_fwd, zigma_timestep_embed_fwd, zigma_final_layer_fwd.
+// features, final LayerNorm + output projection (plain, and guided: two rows combined before the one output rounding).  C ABI: zigma_patch_embed_fwd,
+// zigma_timestep_embed_fwd, zigma_final_layer_fwd, zigma_final_layer_cfg_fwd.
 //
 // Reference: PatchEmbed (timm; ZigMa call site model_zigma.py:608-614,924) followed by `+ pos_embed` (:939-940);
 // TimestepEmbedder.timestep_embedding (:247-268); FinalLayer.forward without conditioning (:313-337, built with cond=False :817-821).
@@ -134,7 +135,70 @@ __global__ void timestep_embed_kernel(const zigma_timestep_embed_params_t p) {
 // two statistics passes and the n_out dot products; sums over the 16 lanes are 4 cross-lane steps; w sits in LDS as bf16 and the 4 rows of
 // a wave read the same pieces (broadcast)
 constexpr int kFlMaxPass = 16;      // E <= 16 lanes * 8 * 16
-template <int NP>                   // passes: E <= 128 NP
+
+__device__ __forceinline__ float fl_sum16(float v) {
+#pragma unroll
+    for (int m = 8; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// one row on its 16 lanes: statistics, the bf16-rounded LayerNorm output, the n_out dot products -> lane o of the 16 holds sum_e w[o, e] y[e] (fp32, no bias).
+// Shared by final_layer_kernel and final_layer_cfg_kernel: the same operations in the same order, so both give the same bits per row.
+// YOUT: also store the bf16 LayerNorm row to yrow (the guided kernel's test hook).
+template <int NP, bool YOUT>         // passes: E <= 128 NP
+__device__ __forceinline__ float final_layer_row(const uint16_t *xr, const uint16_t *s_fw, int E, int NO, float eps, float inv_e, int l16, uint16_t *yrow) {
+    float v[NP][8];
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int e0 = q * 128 + l16 * 8;
+        uint4 w = make_uint4(0, 0, 0, 0);
+        if (e0 < E) w = *reinterpret_cast<const uint4 *>(xr + e0);
+        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { v[q][i] = to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))); s += v[q][i]; }
+    }
+    const float mean = fl_sum16(s) * inv_e;
+    float s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        const int e0 = q * 128 + l16 * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const float d = e0 < E ? v[q][i] - mean : 0.f; v[q][i] = d; s2 += d * d; }
+    }
+    const float rstd = rsqrtf(fl_sum16(s2) * inv_e + eps);
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        uint16_t yb[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { yb[i] = from_float<BF16>(v[q][i] * rstd); v[q][i] = to_float<BF16>(yb[i]); }      // the LayerNorm output is a bf16 tensor
+        if constexpr (YOUT) {
+            const int e0 = q * 128 + l16 * 8;
+            if (yrow && e0 < E)
+                *reinterpret_cast<uint4 *>(yrow + e0) = make_uint4(yb[0] | (static_cast<uint32_t>(yb[1]) << 16), yb[2] | (static_cast<uint32_t>(yb[3]) << 16),
+                                                                   yb[4] | (static_cast<uint32_t>(yb[5]) << 16), yb[6] | (static_cast<uint32_t>(yb[7]) << 16));
+        }
+    }
+    float res = 0.f;      // lane o of the row's 16 keeps output o
+    for (int o = 0; o < NO; ++o) {
+        float acc = 0.f;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            const int e0 = q * 128 + l16 * 8;
+            if (e0 < E) {
+                const uint4 w = *reinterpret_cast<const uint4 *>(s_fw + o * E + e0);
+                const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc = __builtin_fmaf(to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))), v[q][i], acc);
+            }
+        }
+        acc = fl_sum16(acc);
+        if (l16 == o) res = acc;
+    }
+    return res;
+}
+
+template <int NP>
 __global__ __launch_bounds__(256) void final_layer_kernel(const zigma_final_layer_params_t p) {
     extern __shared__ __attribute__((aligned(16))) uint16_t s_fw[];     // [n_out][E]
     const int E = p.cols, NO = p.n_out;
@@ -143,58 +207,56 @@ __global__ __launch_bounds__(256) void final_layer_kernel(const zigma_final_laye
     __syncthreads();
     const int l16 = threadIdx.x & 15, rl = threadIdx.x >> 4;
     const float inv_e = 1.f / static_cast<float>(E);
-    auto sum16 = [](float v) {
-#pragma unroll
-        for (int m = 8; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-        return v;
-    };
     for (int64_t r0 = static_cast<int64_t>(blockIdx.x) * 16; r0 < p.rows; r0 += static_cast<int64_t>(gridDim.x) * 16) {
         const int64_t r = r0 + rl;
         const bool live = r < p.rows;
         const uint16_t *xr = reinterpret_cast<const uint16_t *>(p.x) + (live ? r : 0) * p.x_row_stride;
-        float v[NP][8];
-        float s = 0.f;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const int e0 = q * 128 + l16 * 8;
-            uint4 w = make_uint4(0, 0, 0, 0);
-            if (e0 < E) w = *reinterpret_cast<const uint4 *>(xr + e0);
-            const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { v[q][i] = to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))); s += v[q][i]; }
-        }
-        const float mean = sum16(s) * inv_e;
-        float s2 = 0.f;
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const int e0 = q * 128 + l16 * 8;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) { const float d = e0 < E ? v[q][i] - mean : 0.f; v[q][i] = d; s2 += d * d; }
-        }
-        const float rstd = rsqrtf(sum16(s2) * inv_e + p.eps);
-#pragma unroll
-        for (int q = 0; q < NP; ++q)
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[q][i] = to_float<BF16>(from_float<BF16>(v[q][i] * rstd));      // the LayerNorm output is a bf16 tensor
-        float res = 0.f;      // lane o of the row's 16 keeps output o
-        for (int o = 0; o < NO; ++o) {
-            float acc = 0.f;
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                const int e0 = q * 128 + l16 * 8;
-                if (e0 < E) {
-                    const uint4 w = *reinterpret_cast<const uint4 *>(s_fw + o * E + e0);
-                    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) acc = __builtin_fmaf(to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))), v[q][i], acc);
-                }
-            }
-            acc = sum16(acc);
-            if (l16 == o) res = acc;
-        }
+        float res = final_layer_row<NP, false>(xr, s_fw, E, NO, p.eps, inv_e, l16, nullptr);
         if (live && l16 < NO) {
             if (p.bias) res += to_float<BF16>(reinterpret_cast<const uint16_t *>(p.bias)[l16]);
             reinterpret_cast<uint16_t *>(p.out)[r * p.out_row_stride + l16] = from_float<BF16>(res);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// guided final layer (classifier-free guidance): the conditional and the unconditional row of one token go through final_layer_row one after the
+// other on the same 16 lanes (the row registers are reused), then vc = acc_c + bias, vu = acc_u + bias, out = fma(s, vc - vu, vu) on the fp32
+// accumulators, ONE rounding to the output type, stored where unpatchify puts output o = (i patch + j) chans + c of token (f, h, w) of sample n:
+// out[n, f, c, h patch + i, w patch + j].  s = scale[n] from device memory (a captured graph follows a changed scale).
+template <int NP>
+__global__ __launch_bounds__(256) void final_layer_cfg_kernel(const zigma_final_layer_cfg_params_t p) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t s_fw[];     // [n_out][E]
+    const int E = p.cols, NO = p.n_out;
+    for (int i = threadIdx.x; i < NO * E / 8; i += blockDim.x)
+        reinterpret_cast<uint4 *>(s_fw)[i] = reinterpret_cast<const uint4 *>(p.weight)[i];
+    __syncthreads();
+    const int l16 = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    const float inv_e = 1.f / static_cast<float>(E);
+    // lane o -> (i, j, c) of its output, once per thread
+    const int oc = l16 % p.chans, oij = l16 / p.chans, oi = oij / p.patch, oj = oij % p.patch;
+    const float bias = (p.bias && l16 < NO) ? to_float<BF16>(reinterpret_cast<const uint16_t *>(p.bias)[l16]) : 0.f;
+    uint16_t *y = reinterpret_cast<uint16_t *>(p.y_out);
+    for (int64_t r0 = static_cast<int64_t>(blockIdx.x) * 16; r0 < p.rows; r0 += static_cast<int64_t>(gridDim.x) * 16) {
+        const int64_t r = r0 + rl;
+        const bool live = r < p.rows;
+        const int64_t rr = live ? r : 0;
+        const uint16_t *xc = reinterpret_cast<const uint16_t *>(p.x_cond) + rr * p.x_row_stride;
+        const uint16_t *xu = reinterpret_cast<const uint16_t *>(p.x_uncond) + rr * p.x_row_stride;
+        const float ac = final_layer_row<NP, true>(xc, s_fw, E, NO, p.eps, inv_e, l16, (y && live) ? y + r * E : nullptr);
+        const float au = final_layer_row<NP, true>(xu, s_fw, E, NO, p.eps, inv_e, l16, (y && live) ? y + (p.rows + r) * E : nullptr);
+        if (live && l16 < NO) {
+            const int64_t n = r / p.rows_per_sample;
+            const int in_sample = static_cast<int>(r - n * p.rows_per_sample);
+            const int f = in_sample / p.tokens_per_frame, tok = in_sample % p.tokens_per_frame;
+            const int h = tok / p.grid_w, w = tok % p.grid_w;
+            const float s = p.scale[n];
+            const float vc = ac + bias, vu = au + bias;
+            const float v = __builtin_fmaf(s, vc - vu, vu);
+            const int64_t at = n * p.out_sample_stride + f * p.out_frame_stride + oc * p.out_chan_stride
+                               + static_cast<int64_t>(h * p.patch + oi) * p.out_row_stride + (w * p.patch + oj);
+            if (p.out_dtype == ZIGMA_F32) reinterpret_cast<float *>(p.out)[at] = v;
+            else reinterpret_cast<uint16_t *>(p.out)[at] = from_float<BF16>(v);
         }
     }
 }
@@ -271,5 +333,33 @@ extern "C" int zigma_final_layer_fwd(const zigma_final_layer_params_t *pp, void 
     else if (np <= 8) hipLaunchKernelGGL(final_layer_kernel<8>, grid, block, lds, stream, p);
     else hipLaunchKernelGGL(final_layer_kernel<16>, grid, block, lds, stream, p);
     set_last_kernel("final_layer");
+    return check_launch();
+}
+
+extern "C" int zigma_final_layer_cfg_fwd(const zigma_final_layer_cfg_params_t *pp, void *stream_) {
+    if (!pp) return ZIGMA_ERR_NULL;
+    (void)hipGetLastError();
+    const zigma_final_layer_cfg_params_t &p = *pp;
+    if (p.rows < 0 || p.cols < 8 || p.n_out < 1) return ZIGMA_ERR_SHAPE;
+    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
+    if (p.dtype != ZIGMA_BF16 || (p.out_dtype != ZIGMA_F32 && p.out_dtype != ZIGMA_BF16)) return ZIGMA_ERR_DTYPE;
+    if (p.cols % 8 != 0 || p.cols > 128 * kFlMaxPass || p.n_out > 16) return ZIGMA_ERR_SHAPE;
+    if (p.rows_per_sample < 1 || p.tokens_per_frame < 1 || p.grid_w < 1 || p.patch < 1 || p.chans < 1) return ZIGMA_ERR_SHAPE;
+    if (static_cast<int64_t>(p.patch) * p.patch * p.chans != p.n_out) return ZIGMA_ERR_SHAPE;
+    if (p.rows % p.rows_per_sample != 0 || p.rows_per_sample % p.tokens_per_frame != 0 || p.tokens_per_frame % p.grid_w != 0) return ZIGMA_ERR_SHAPE;
+    if (p.rows == 0) return ZIGMA_OK;
+    if (!p.x_cond || !p.x_uncond || !p.weight || !p.scale || !p.out) return ZIGMA_ERR_NULL;
+    if (reinterpret_cast<uintptr_t>(p.x_cond) % 16 != 0 || reinterpret_cast<uintptr_t>(p.x_uncond) % 16 != 0 || p.x_row_stride % 8 != 0
+        || reinterpret_cast<uintptr_t>(p.weight) % 16 != 0 || reinterpret_cast<uintptr_t>(p.y_out) % 16 != 0
+        || reinterpret_cast<uintptr_t>(p.scale) % 4 != 0 || reinterpret_cast<uintptr_t>(p.out) % (p.out_dtype == ZIGMA_F32 ? 4 : 2) != 0) return ZIGMA_ERR_STRIDE;
+    const int64_t want = (p.rows + 15) / 16;
+    const dim3 grid(static_cast<unsigned>(want < 4096 ? want : 4096)), block(256);
+    const size_t lds = static_cast<size_t>(p.n_out) * p.cols * 2;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const int np = (p.cols + 127) / 128;
+    if (np <= 5) hipLaunchKernelGGL(final_layer_cfg_kernel<5>, grid, block, lds, stream, p);
+    else if (np <= 8) hipLaunchKernelGGL(final_layer_cfg_kernel<8>, grid, block, lds, stream, p);
+    else hipLaunchKernelGGL(final_layer_cfg_kernel<16>, grid, block, lds, stream, p);
+    set_last_kernel("final_layer_cfg");
     return check_launch();
 }

@@ -12,6 +12,8 @@ from . import _lib
 
 BF16 = torch.bfloat16
 USE_EMBED_KERNELS = True      # False: the torch composition everywhere (A/B in tests and tools)
+from . import _knobs  # noqa: E402
+_knobs.apply(globals(), "embed")      # ZIGMA_KNOBS="embed.USE_EMBED_KERNELS=False" switches EVERY kernel of this module to torch (A/B tools)
 
 
 def _al(t, n):
@@ -123,3 +125,40 @@ def final_layer(x, weight, bias, eps):
     P.x, P.weight, P.bias, P.out = _lib.ptr(x2), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(out)
     _lib.call("zigma_final_layer_fwd", P, dev)
     return out.view(*x.shape[:-1], n_out)
+
+
+_GUIDED_OUT = {torch.float32: _lib.F32, BF16: _lib.BF16}
+
+
+def final_layer_guided_eligible(x_pair, weight, bias, scale, *, patch, chans, grid, frames=0, out_dtype=torch.float32):
+    """x_pair (2B, L, E): the conditional half first.  What final_layer takes, and: an even batch, L = max(frames, 1) * grid^2 tokens per sample,
+    patch^2 * chans outputs, one fp32 scale per sample on the same device, an fp32 or bf16 result."""
+    if x_pair.dim() != 3 or x_pair.shape[0] % 2 or x_pair.shape[0] == 0 or not final_layer_eligible(x_pair, weight, bias):
+        return False
+    if weight.shape[0] != patch * patch * chans or grid < 1 or x_pair.shape[1] != max(frames, 1) * grid * grid or out_dtype not in _GUIDED_OUT:
+        return False
+    return (torch.is_tensor(scale) and scale.is_cuda and scale.device == x_pair.device and scale.dtype == torch.float32
+            and scale.shape == (x_pair.shape[0] // 2,) and scale.is_contiguous() and not scale.requires_grad)
+
+
+def final_layer_guided(x_pair, weight, bias, eps, scale, *, patch, chans, grid, frames=0, out_dtype=torch.float32):
+    """Classifier-free guidance on the final layer's fp32 accumulators: x_pair (2B, L, E) = [conditional; unconditional] tokens ->
+    v_u + scale * (v_c - v_u) with v = Linear(LayerNorm(x)), rounded ONCE to out_dtype and stored unpatchified:
+    (B, C, H, W), or (B, T, C, H, W) with frames = T > 0.  scale: (B,) fp32 on the device."""
+    dev = _lib.require_device(x_pair, weight, bias, scale)
+    if not final_layer_guided_eligible(x_pair, weight, bias, scale, patch=patch, chans=chans, grid=grid, frames=frames, out_dtype=out_dtype):
+        raise RuntimeError("final_layer_guided: contiguous bf16 (2B, L = frames * grid^2, E % 8 == 0, E <= 2048) input, (patch^2 * chans <= 16, E) weight, "
+                           "(B,) fp32 scale on the device, fp32 or bf16 output, no autograd")
+    Bsz, L, E = x_pair.shape[0] // 2, x_pair.shape[1], x_pair.shape[2]
+    side = grid * patch
+    out = torch.empty((Bsz,) + ((frames,) if frames else ()) + (chans, side, side), device=x_pair.device, dtype=out_dtype)
+    P = _lib.FinalLayerCfgParams()
+    P.rows, P.cols, P.n_out, P.dtype, P.out_dtype, P.flags, P.eps = Bsz * L, E, weight.shape[0], _lib.BF16, _GUIDED_OUT[out_dtype], 0, float(eps)
+    P.rows_per_sample, P.tokens_per_frame, P.grid_w, P.patch, P.chans = L, grid * grid, grid, patch, chans
+    P.x_row_stride = x_pair.stride(1)
+    P.out_sample_stride, P.out_chan_stride, P.out_row_stride = out.stride(0), out.stride(-3), out.stride(-2)
+    P.out_frame_stride = out.stride(1) if frames else 0
+    P.x_cond, P.x_uncond, P.weight, P.bias = _lib.ptr(x_pair[:Bsz]), _lib.ptr(x_pair[Bsz:]), _lib.ptr(weight), _lib.ptr(bias)
+    P.scale, P.out = _lib.ptr(scale), _lib.ptr(out)
+    _lib.call("zigma_final_layer_cfg_fwd", P, dev)
+    return out

@@ -464,7 +464,7 @@ class ZigMa(nn.Module):
                  d_context: int = 0, ssm_cfg=None, norm_epsilon: float = 1e-5, rms_norm: bool = True,
                  fused_add_norm=True, residual_in_fp32=True, initializer_cfg=None, scan_type="v2", video_frames=0,
                  tpe=False, device="cuda", use_pe=0, use_jit=True, m_init=True, use_checkpoint=False,
-                 dtype=torch.float32, verbose=False):
+                 dtype=torch.float32, verbose=False, class_dropout_prob=0.0):
         self.factory_kwargs = factory_kwargs = {"device": device, "dtype": dtype}
         super().__init__()
         self.in_channels = in_channels
@@ -505,7 +505,7 @@ class ZigMa(nn.Module):
         if has_text:
             self.y_embedder = nn.Linear(d_context, embed_dim).to(device).to(dtype)
         elif num_classes > 0:
-            self.y_embedder = LabelEmbedder(num_classes, hidden_size=embed_dim, dropout_prob=0.0).to(device).to(dtype)
+            self.y_embedder = LabelEmbedder(num_classes, hidden_size=embed_dim, dropout_prob=class_dropout_prob).to(device).to(dtype)      # > 0: one more row, the null class of forward_guided
 
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, self.n_layer)]
         inter_dpr = [0.0] + dpr
@@ -599,7 +599,10 @@ class ZigMa(nn.Module):
 
     def forward(self, hidden_states, t, y=None):
         """x: (N, C, H, W) [or (N, T, C, H, W)] latents; t: (N,) diffusion times; y: (N,) labels or (N, n_ctx, d_ctx) text."""
-        in_dtype = hidden_states.dtype
+        return self._head(self._trunk(hidden_states, t, y), hidden_states.dtype)
+
+    def _trunk(self, hidden_states, t, y=None):
+        """embedders, conditioning, the blocks and norm_f: latents -> (N, T, D) tokens, the input of the final layer"""
         pdtype = self.x_embedder.proj.weight.dtype
         # mixed precision (an fp32 model under torch.autocast): the embedders, adaLN, the label embedding and the final layer stay torch ops, which
         # autocast casts; the token stream enters the blocks in the autocast type (the residual stream stays fp32 as always) and the blocks' matrix
@@ -665,7 +668,10 @@ class ZigMa(nn.Module):
                 hidden_states = fn(self.drop_path(hidden_states), self.norm_f.weight, self.norm_f.bias,
                                    eps=self.norm_f.eps, residual=residual, prenorm=False,
                                    residual_in_fp32=self.residual_in_fp32)
+        return hidden_states
 
+    def _head(self, hidden_states, in_dtype):
+        """final layer, unpatchify, cast to the caller's dtype"""
         hidden_states = self.final_layer(hidden_states)
         if self.video_frames > 0:
             hidden_states = self.unpatchify_video(hidden_states, self.video_frames)
@@ -714,3 +720,42 @@ class ZigMa(nn.Module):
 
     def forward_with_cfg(self, x, t, y, cfg_scale):
         raise NotImplementedError
+
+    def forward_guided(self, x, t, y, cfg_scale, y_null=None):
+        """Classifier-free guidance: v_u + cfg_scale * (v_c - v_u) for B latents, in x.dtype.  ONE pass through the blocks with batch 2B (the
+        conditional half first).  cfg_scale: a float or a (B,) tensor (one scale per sample; a device tensor is read when the kernel runs, so a
+        captured graph follows it).  The null condition: labels -> y_null defaults to the null row of a model built with class_dropout_prob > 0;
+        text -> y_null, the caller's features of the empty prompt, is required.  On a bf16 model outside autograd the final layer of both halves, the
+        combination on its fp32 accumulators and unpatchify are one kernel with one rounding (embed.final_layer_guided); otherwise the torch composition
+        final_layer -> unpatchify -> .to(x.dtype) -> combine, which is differentiable.  A Python float of exactly 1.0 is the plain conditional forward."""
+        if not self.has_text and not self.num_classes > 0:
+            raise ValueError("forward_guided: an unconditional model has nothing to guide")
+        if y is None:
+            raise ValueError("forward_guided: the condition y is required")
+        if y_null is None:
+            if self.has_text:
+                raise ValueError("forward_guided: a text-conditional model needs y_null, the features of the empty prompt")
+            if self.y_embedder.embedding_table.num_embeddings <= self.num_classes:
+                raise ValueError("forward_guided: the model has no null class (build it with class_dropout_prob > 0) and no y_null was given")
+            y_null = self.num_classes
+        if isinstance(cfg_scale, (int, float)) and float(cfg_scale) == 1.0:
+            return self.forward(x, t, y)
+        Bsz = x.shape[0]
+        if not torch.is_tensor(y_null):
+            y_null = torch.full_like(y, y_null)
+        y_null = y_null.to(device=y.device, dtype=y.dtype)
+        if y_null.dim() == y.dim() - 1:                  # one null condition for the whole batch
+            y_null = y_null.unsqueeze(0)
+        y_null = y_null.expand_as(y)
+        if torch.is_tensor(cfg_scale):
+            scale = cfg_scale.to(device=x.device, dtype=torch.float32).reshape(-1).expand(Bsz).contiguous()
+        else:
+            scale = torch.full((Bsz,), float(cfg_scale), device=x.device, dtype=torch.float32)
+        h = self._trunk(torch.cat([x, x]), torch.cat([t, t]), torch.cat([y, y_null]))
+        lin, frames = self.final_layer.linear, self.video_frames
+        grid = int((h.shape[1] // max(frames, 1)) ** 0.5)
+        geom = dict(patch=self.x_embedder.patch_size[0], chans=self.out_channels, grid=grid, frames=frames, out_dtype=x.dtype)
+        if _embed.final_layer_guided_eligible(h, lin.weight, lin.bias, scale, **geom):
+            return _embed.final_layer_guided(h, lin.weight, lin.bias, self.final_layer.norm_final.eps, scale, **geom)
+        v_c, v_u = self._head(h, x.dtype).chunk(2)
+        return v_u + scale.view(-1, *([1] * (x.dim() - 1))).to(x.dtype) * (v_c - v_u)
