@@ -43,7 +43,8 @@ extern "C" {
                                * (10, no block changed): zigma_multi_cast_fwd / zigma_multi_cast_params_t added
                                * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added
                                * (11, no block changed): zigma_optim_* added
-                               * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added */
+                               * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added
+                               * (11, no block changed): zigma_sde_step_fwd / zigma_sde_advance and their blocks added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -863,6 +864,89 @@ typedef struct zigma_optim_params {
 int zigma_optim_grad_sumsq(const zigma_optim_params_t *p, void *stream);
 int zigma_optim_prepare(const zigma_optim_params_t *p, void *stream);
 int zigma_optim_adamw(const zigma_optim_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * One launch of an SDE sampler's step on the device (csrc/sde_step.hip).  (ABI 11, no block changed.)  The reference draws every Wiener
+ * increment with the CPU generator and copies it to the device (transport/integrators.py:24,38); here the noise is a counter-based function
+ * of (seed, stream, step, element) evaluated inside the kernel, and every host value of a step lives in device memory, so one captured graph
+ * replays for every step of a trajectory.  Over n contiguous elements:
+ *
+ *   out[i] = c0 a[i] + c1 b[i] + c2 c[i] + cn xi[i]            (c0, c1, c2, cn) = coef[4 r .. 4 r + 3]
+ *
+ * evaluated in fp32 as  acc = +0;  acc = fma(cn, xi, acc);  acc = fma(c2, c, acc);  acc = fma(c1, b, acc);  acc = fma(c0, a, acc)  (a missing
+ * term is skipped; with none present out = 0), rounded once to `dtype` on the store.
+ *   a, b, c     `dtype` (ZIGMA_F32 / ZIGMA_BF16 / ZIGMA_F16), n elements; each may be NULL: its term is skipped, its coefficient is never read
+ *               as a factor and the operand never loaded
+ *   out         `dtype`, n elements.  out == a is legal (the in-place update: every lane loads its own elements before it stores them); any
+ *               OTHER overlap of out with a, b or c is the caller's error and is not detected
+ *   coef        DEVICE table, coef_rows rows of four fp32.  The row r is  state->step * rows_per_step + row,  or `row` itself with
+ *               ZIGMA_SDE_ROW_ABSOLUTE; a relative row past the table is clamped to the last row (a replay too many reads memory that exists)
+ *   state       one zigma_sde_state_t in DEVICE memory: the Philox key (seed_lo, seed_hi), the stream and the step counter.  Read only.
+ *               May be NULL with ZIGMA_SDE_ROW_ABSOLUTE and bits_out == NULL: the caller then promises cn == 0, and the kernel adds no noise
+ *               whatever the row says (NULL is never followed)
+ *   bits_out    NULL, or uint32, 4 * ceil(n / 4) words: receives the raw Philox words of every quad the call touches (a test hook).  Not
+ *               written when cn == 0, since no Philox work is done then
+ *   elem_offset the index of element 0 in the logical noise field: a multiple of 4, >= 0.  Several calls can share one field
+ *
+ * The noise.  Element i belongs to quad q = (elem_offset + i) / 4 and takes normal number (elem_offset + i) % 4 of it.  The quad's four words are
+ *   (r0, r1, r2, r3) = Philox4x32-10(counter = (q & 0xffffffff, q >> 32, step, stream), key = (seed_lo, seed_hi))
+ * (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds).  Words (r0, r1) give normals
+ * 0 and 1, words (r2, r3) normals 2 and 3, each pair by Box-Muller on
+ *   u = ((ra >> 8) + 1) * 2^-24     in (0, 1], never 0, exact in fp32
+ *   x = (rb >> 8) * 2^-23           in [0, 2), exact in fp32: the angle is pi x
+ *   rho = sqrtf(-2 logf(u));   (s, k) = sincospif(x);   normal_even = rho * k,   normal_odd = rho * s
+ * with the accurate library logf / sqrtf / sincospif.  u >= 2^-24 bounds |normal| by sqrt(48 ln 2) = 5.768; u == 1 gives exactly 0.
+ * With cn == 0 in the selected row no Philox work is done.
+ *
+ * Access: every lane owns 8 consecutive elements: one 16-byte access per operand in the 16-bit types, two in fp32; the last n % 8 elements of
+ * a call go one by one.  Nothing is read or written past element n - 1, except that bits_out always receives whole quads.
+ * Checked in this order, before any launch: NULL block ZIGMA_ERR_NULL; n < 0 (or more than 2^31 - 1 workgroups of 2048 elements)
+ * ZIGMA_ERR_SHAPE; elem_offset < 0, elem_offset % 4 or elem_offset + n past 2^63 - 1 ZIGMA_ERR_SHAPE; rows_per_step < 1 ZIGMA_ERR_SHAPE; row < 0 ZIGMA_ERR_SHAPE; coef_rows < 1, or an
+ * absolute row >= coef_rows ZIGMA_ERR_SHAPE; unknown flags ZIGMA_ERR_UNSUPPORTED; a dtype outside the three ZIGMA_ERR_DTYPE; n == 0 ZIGMA_OK,
+ * nothing touched; NULL out or coef ZIGMA_ERR_NULL; NULL state where it is needed (a relative row, or bits_out given) ZIGMA_ERR_NULL; a, b, c,
+ * out, coef, state or bits_out not 16-byte aligned ZIGMA_ERR_STRIDE.
+ *
+ * zigma_sde_advance: one workgroup, stream-ordered after the step's launches.  state->step += 1; then, with r = min(step, n_rows - 1),
+ *   t_out[j * batch + b] = times[r * n_t + j]        j < n_t, b < batch
+ * `times` has one row of n_t fp32 per step (n_t = 1: Euler-Maruyama; 2: Heun's two evaluations) and the last step's time in its last row; a call
+ * past the table keeps writing the last row (the clamp).  Plain vector stores; nothing past t_out[n_t * batch - 1] is written.
+ * Checked in this order: NULL block ZIGMA_ERR_NULL; n_t other than 1 / 2, batch < 1, n_rows < 1 ZIGMA_ERR_SHAPE; flags != 0
+ * ZIGMA_ERR_UNSUPPORTED; NULL state, times or t_out ZIGMA_ERR_NULL; state not 16-byte aligned ZIGMA_ERR_STRIDE.
+ * ------------------------------------------------------------------------------------------ */
+#define ZIGMA_SDE_ROW_ABSOLUTE 1   /* zigma_sde_step_params_t.flags: the coefficient row is `row`, not state->step * rows_per_step + row */
+
+typedef struct zigma_sde_state {
+    uint32_t seed_lo, seed_hi;   /* the Philox key                      */
+    uint32_t stream;             /* counter word 3                      */
+    uint32_t step;               /* counter word 2; zigma_sde_advance increments it */
+} zigma_sde_state_t;
+
+typedef struct zigma_sde_step_params {
+    int64_t n;
+    int64_t elem_offset;
+    int64_t coef_rows;
+    int32_t dtype;               /* zigma_dtype_t of a, b, c and out */
+    int32_t flags;               /* ZIGMA_SDE_ROW_ABSOLUTE */
+    int32_t rows_per_step, row;
+    const void *a, *b, *c;
+    void *out;
+    const float *coef;
+    const zigma_sde_state_t *state;
+    uint32_t *bits_out;
+} zigma_sde_step_params_t;
+
+typedef struct zigma_sde_advance_params {
+    zigma_sde_state_t *state;
+    const float *times;
+    float *t_out;
+    int64_t n_rows;
+    int32_t n_t, batch;
+    int32_t flags;               /* reserved, must be 0 */
+    int32_t pad_;
+} zigma_sde_advance_params_t;
+
+int zigma_sde_step_fwd(const zigma_sde_step_params_t *p, void *stream);
+int zigma_sde_advance(const zigma_sde_advance_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-only plan queries of the Mamba inner's five forward entry points (ABI 11): what the launch would do with this parameter block,

@@ -210,7 +210,22 @@ class OptimParams(C.Structure):
                 + [("shadow_dtype", i32), ("chunk", i32), ("flags", i32), ("pad_", i32)])
 
 
-EXPORTS = ("zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw", "zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
+class SdeState(C.Structure):            # the device state block of a trajectory's noise (four 4-byte words)
+    _fields_ = [(n, C.c_uint32) for n in ("seed_lo", "seed_hi", "stream", "step")]
+
+
+class SdeStepParams(C.Structure):
+    _fields_ = ([(n, i64) for n in ("n", "elem_offset", "coef_rows")] + [(n, i32) for n in ("dtype", "flags", "rows_per_step", "row")]
+                + [(n, vp) for n in ("a", "b", "c", "out", "coef", "state", "bits_out")])
+
+
+class SdeAdvanceParams(C.Structure):
+    _fields_ = [("state", vp), ("times", vp), ("t_out", vp), ("n_rows", i64), ("n_t", i32), ("batch", i32), ("flags", i32), ("pad_", i32)]
+
+
+SDE_ROW_ABSOLUTE = 1                    # zigma_sde_step_params_t.flags
+
+EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw", "zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
            "zigma_selective_scan_bwd_workspace_bytes", "zigma_causal_conv1d_bwd",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
@@ -239,7 +254,7 @@ def lib():
                          ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
                          ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams),
                          ("zigma_multi_cast_fwd", MultiCastParams), ("zigma_optim_grad_sumsq", OptimParams), ("zigma_optim_prepare", OptimParams),
-                         ("zigma_optim_adamw", OptimParams)):
+                         ("zigma_optim_adamw", OptimParams), ("zigma_sde_step_fwd", SdeStepParams), ("zigma_sde_advance", SdeAdvanceParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st), vp]
             fn.restype = C.c_int

@@ -173,10 +173,24 @@ class Sampler:
         raise NotImplementedError()
 
     def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean",
-                   last_step_size=0.04, num_steps=250):
+                   last_step_size=0.04, num_steps=250, noise="reference", seed=0, stream=0, graph=False):
         """returns fn(init_z, model, **model_kwargs) -> list of num_steps states (reference transport.py:309-370):
         num_steps - 1 solver steps on linspace(t0, t1, num_steps) plus the last step ("Mean" | "Tweedie" | "Euler" | None)
-        from t1 = 1 - last_step_size."""
+        from t1 = 1 - last_step_size.
+
+        noise="reference" (the default) is the reference's loop: Wiener increments from torch's CPU generator, copied to the device.
+        noise="device" (sde_device.py) draws them inside a HIP kernel as a counter-based function of (seed, stream, step, element) (seed an
+        integer below 2^64, stream below 2^32: one stream per rank of a sharded run) and keeps every per-step value on the device; init_z must
+        then be a CUDA tensor in fp32, bf16 or fp16.  graph=True (device noise only) captures one step as a graph and replays it."""
+        if noise not in ("reference", "device"):
+            raise ValueError(f"sample_sde: noise is 'reference' or 'device', not {noise!r}")
+        if noise == "device":
+            from . import sde_device
+            plan = sde_device.make_plan(self, sampling_method=sampling_method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm,
+                                        last_step=last_step, last_step_size=last_step_size, num_steps=num_steps)
+            return sde_device.DeviceSdeSampler(plan, seed=seed, stream=stream, graph=graph)
+        if graph:
+            raise ValueError("sample_sde: graph=True needs noise='device' (the reference loop draws on the CPU inside every step)")
         if last_step is None:
             last_step_size = 0.0
         sde_drift, sde_diffusion = self._sde_drift_and_diffusion(diffusion_form=diffusion_form,
