@@ -44,7 +44,8 @@ extern "C" {
                                * 11: the host-only plan queries zigma_*_fwd_plan of the Mamba inner's five forward entry points added
                                * (11, no block changed): zigma_optim_* added
                                * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added
-                               * (11, no block changed): zigma_sde_step_fwd / zigma_sde_advance and their blocks added */
+                               * (11, no block changed): zigma_sde_step_fwd / zigma_sde_advance and their blocks added
+                               * (11, no block changed): the plan queries zigma_linear_fwd_plan, zigma_norm_linear_fwd_plan, zigma_linear_f32_split_plan added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -965,6 +966,11 @@ int zigma_causal_conv1d_fwd_plan(const zigma_conv_params_t *p, const char **kern
 int zigma_conv_x_proj_fwd_plan(const zigma_conv_xproj_params_t *p, const char **kernel);
 int zigma_x_proj_fwd_plan(const zigma_xproj_params_t *p, const char **kernel);
 int zigma_dt_proj_softplus_fwd_plan(const zigma_dtproj_params_t *p, const char **kernel);
+/* ... and of the dense projections (ABI 11, no block changed): plan_linear() / plan_linear_split() of csrc/linear_plan.h, plan_norm_linear() of
+ * csrc/norm_linear_plan.h, under the same rules. */
+int zigma_linear_fwd_plan(const zigma_linear_params_t *p, const char **kernel);
+int zigma_norm_linear_fwd_plan(const zigma_norm_linear_params_t *p, const char **kernel);
+int zigma_linear_f32_split_plan(const zigma_linear_split_params_t *p, const char **kernel);
 
 /* ------------------------------------------------------------------------------------------ */
 const char *zigma_strerror(int status);

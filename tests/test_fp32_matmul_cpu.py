@@ -172,7 +172,7 @@ class Stand:
 ROLE_SHAPES = {"in_proj": (2560, 640), "out_proj": (640, 1280), "to_q": (512, 640), "to_out": (640, 512), "text": (2048, 640), "train": (2560, 640)}
 
 
-def test_plan_routes_fp32_calls_only_when_asked(mode, monkeypatch):
+def test_plan_routes_fp32_calls_only_when_asked(mode, monkeypatch, libpath):
     import zigma_amd.routing as zr
     from zigma_amd import fp32_matmul as fm
     from zigma_amd.linear import plan

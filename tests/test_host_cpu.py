@@ -126,10 +126,10 @@ ROUTING_LIBRARY_CELLS = {
 }
 
 
-def test_routing_table():
+def test_routing_table(libpath):
     """zigma_amd/routing.py: ONE table decides which kernel serves which projection.  Sweep E x tokens x role: (i) a row is chosen, deterministically,
     and its kernel's shape limits hold; (ii) the cells that fall to the library are exactly the reviewed list above; (iii) the shipped shapes land on the
-    rows the profiles were taken with; (iv) the knobs (POLICY, DISABLED) do what they say."""
+    rows the profiles were taken with; (iv) the knobs (POLICY, DISABLED) do what they say.  (The limits are the built library's plan: routing.serves.)"""
     import zigma_amd.routing as zr
     lib_cells = set()
     for E in (512, 640, 768, 1024):
@@ -138,7 +138,7 @@ def test_routing_table():
             for role, (n, k) in shapes.items():
                 r = zr.route(role, tokens, n, k)
                 assert r == zr.route(role, tokens, n, k) and r.kernel in zr.KERNELS and r.row.startswith(role + ".")
-                assert zr._SERVES[r.kernel](tokens, n, k), (role, E, tokens, r)
+                assert zr.serves(r.kernel, tokens, n, k), (role, E, tokens, r)
                 if r.kernel == "library":
                     lib_cells.add((role, E, tokens))
     assert lib_cells == ROUTING_LIBRARY_CELLS, (lib_cells - ROUTING_LIBRARY_CELLS, ROUTING_LIBRARY_CELLS - lib_cells)
@@ -156,7 +156,7 @@ def test_routing_table():
     for E in (512, 640, 768, 1024):
         for tokens in (4096, 8192, 16384, 65536, 4096 + 8, 100):
             for n, k in ((4 * E, E), (E, 4 * E), (E, 2 * E), (2 * E, E), (512, E), (E, 512)):
-                want = ("ws" if zr.serves_ws(tokens, n, k) and zr.ws_panel_width(k) == 256 else "ws128" if zr.serves_ws(tokens, n, k)
+                want = ("ws" if zr.serves_ws(tokens, n, k) and k in (512, 640) else "ws128" if zr.serves_ws(tokens, n, k)
                         else "tiled" if zr.serves_tiled(tokens, n, k) else "library")
                 assert zr.route("train", tokens, n, k) == zr.Route(want, False, "train." + want), (E, tokens, n, k)
     assert zr.route("train", 65536, 2560, 640).row == "train.ws" and zr.route("train", 65536, 640, 1280).row == "train.ws128"
@@ -710,19 +710,11 @@ def test_scan_plan_case_table(name, scan_plan, libpath):
     assert asked == (want.status, want.kernel)
 
 
-class _Dev:
-    """a contiguous GPU tensor as the eligibility predicates read it (shape, strides, dtype, address); nothing is allocated"""
-    def __init__(self, dtype, *shape, ptr=1 << 20):
-        self.is_cuda, self.dtype, self.shape, self._ptr = True, dtype, shape, ptr
-        self._strides = tuple(math.prod(shape[i + 1:]) for i in range(len(shape)))
-    stride, dim, data_ptr = (lambda self, i: self._strides[i]), (lambda self: len(self.shape)), (lambda self: self._ptr)
-    numel, requires_grad = (lambda self: math.prod(self.shape)), False
-    is_contiguous = lambda self: self._strides == tuple(math.prod(self.shape[i + 1:]) for i in range(len(self.shape)))
-
-    def pitched(self, *strides):
-        """the same tensor with these strides (a view of a wider allocation)"""
-        self._strides = strides
-        return self
+def _Dev(dtype, *shape, ptr=1 << 20, pitched=None, cuda=True):
+    """a GPU tensor as the eligibility predicates read it — the package's own descriptor (_lib.Desc: shape, strides, dtype, address): contiguous, or with
+    these strides (a view of a wider allocation); nothing is allocated"""
+    from zigma_amd._lib import Desc
+    return Desc(dtype, shape, tuple(pitched) if pitched else tuple(math.prod(shape[i + 1:]) for i in range(len(shape))), ptr, cuda)
 
 
 def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
@@ -741,7 +733,7 @@ def test_dt_in_scan_eligible_agrees_with_the_plan(scan_plan):
                                 for off in (0, 2):
                                     W, es = R + 2 * N, 2 if dt != torch.float32 else 4
                                     u, x_dbl = _Dev(dt, B, L, Di), _Dev(dt, B, L, W, ptr=(1 << 24) + off * es)
-                                    z = _Dev(dt, B, L, Di).pitched(L * 2 * Di, 2 * Di, 1)
+                                    z = _Dev(dt, B, L, Di, pitched=(L * 2 * Di, 2 * Di, 1))
                                     w = _Dev(dt, Di, R, ptr=1 << 28)
                                     P = _lib.ScanParams()
                                     P.batch, P.dim, P.seqlen, P.dstate, P.n_groups, P.reset_period = B, Di, L, N, 1, rp
@@ -861,8 +853,8 @@ def test_x_proj_eligible_agrees_with_the_plan(front_plan):
                     for x_pitch in (k, k + 4, k + 8):
                         for w_pitch in (k, k + 4, k + 8):
                             for x_off, w_off in ((0, 0), (2, 0), (8, 0), (0, 2), (0, 8)):
-                                u = _Dev(dt, tokens, k, ptr=(1 << 30) + x_off * 2).pitched(x_pitch, 1)
-                                w = _Dev(dt, n, k, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                u = _Dev(dt, tokens, k, ptr=(1 << 30) + x_off * 2, pitched=(x_pitch, 1))
+                                w = _Dev(dt, n, k, ptr=(1 << 36) + w_off * 2, pitched=(w_pitch, 1))
                                 P = _lib.XProjParams()
                                 P.m, P.n, P.k, P.dtype = tokens, n, k, _TORCH_ID[dt]
                                 P.x_row_stride, P.w_row_stride, P.out_row_stride = u.stride(0), w.stride(0), n
@@ -888,7 +880,7 @@ def test_dt_proj_eligible_agrees_with_the_plan(front_plan):
                         for w_pitch in (R, R + 4, R + 8):
                             for x_off, w_off in ((0, 0), (2, 0), (8, 0), (0, 2), (0, 8)):
                                 x_dbl = _Dev(dt, tokens, width, ptr=(1 << 30) + x_off * 2)
-                                w = _Dev(dt, Di, R, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                w = _Dev(dt, Di, R, ptr=(1 << 36) + w_off * 2, pitched=(w_pitch, 1))
                                 P = _lib.DtProjParams()
                                 P.m, P.n, P.k, P.dtype, P.softplus = tokens, Di, R, _TORCH_ID[dt], 1
                                 P.x_row_stride, P.w_row_stride, P.out_row_stride = x_dbl.stride(0), w.stride(0), Di
@@ -914,12 +906,12 @@ def test_conv_x_proj_eligible_agrees_with_the_plan(front_plan):
                         for w_pitch in (Di, Di + 4, Di + 8):
                             for x_off, cw_off, cb_off, w_off in offs:
                                 for loose in ("", "conv_w", "conv_b", "perm") if (x_off, cw_off, cb_off, w_off) == (0, 0, 0, 0) else ("",):
-                                    x = _Dev(dt, Bsz, L, Di, ptr=(1 << 30) + x_off * 2).pitched(L * x_pitch, x_pitch, 1)
+                                    x = _Dev(dt, Bsz, L, Di, ptr=(1 << 30) + x_off * 2, pitched=(L * x_pitch, x_pitch, 1))
                                     cw, cb = _Dev(dt, Di, 4, ptr=(1 << 34) + cw_off * 2), _Dev(dt, Di, ptr=(1 << 35) + cb_off * 2)
-                                    w = _Dev(dt, n, Di, ptr=(1 << 36) + w_off * 2).pitched(w_pitch, 1)
+                                    w = _Dev(dt, n, Di, ptr=(1 << 36) + w_off * 2, pitched=(w_pitch, 1))
                                     perm = _Dev(torch.int32, L, ptr=1 << 38)
                                     if loose:
-                                        {"conv_w": cw, "conv_b": cb, "perm": perm}[loose].pitched(*((8, 1) if loose == "conv_w" else (2,)))
+                                        {"conv_w": cw, "conv_b": cb, "perm": perm}[loose].strides = (8, 1) if loose == "conv_w" else (2,)
                                     P = _lib.ConvXProjParams()
                                     P.batch, P.seqlen, P.dim, P.n, P.dtype = Bsz, L, Di, n, _TORCH_ID[dt]
                                     P.x_batch_stride, P.x_l_stride, P.u_batch_stride, P.u_l_stride = x.stride(0), x.stride(1), L * Di, Di
@@ -1036,37 +1028,66 @@ def test_linear_plan_case_table(name, linear_plan):
     assert (got["status"], got["kernel"]) == tuple(want) and (got["family"] != 0) == (want.kernel is not None)
 
 
-def test_linear_mirrors_agree_with_the_plan(linear_plan):
-    """The Python side's limits of zigma_linear_fwd's kernel families against plan_linear() (compiled), on the edges of every rule: for each of ws / ws128 /
-    sm / tiled, linear_eligible and routing._SERVES[kern] and linear._TENSOR_LIMITS[kern] hold exactly where the plan serves the call flagged for that
-    family (and panel width); routing.kernel_name is a prefix of the plan's kernel on every served cell (all inside serves_4w's stated domain:
-    contiguous out, tokens * n * 2 < 2^32; a bias alone is passed on)."""
+def test_linear_mirrors_agree_with_the_plan(linear_plan, libpath):
+    """The Python side's answers about zigma_linear_fwd's kernel families against plan_linear() compiled with g++ from the header (independent of the built
+    library the predicates ask), on the edges of every rule: for each of ws / ws128 / sm / tiled, the family's public predicate (linear_ws_eligible,
+    linear_sm_eligible, linear_eligible) and routing.serves(kern) hold exactly where the plan serves the call flagged for that family (and panel width); the
+    block linear_block builds for the call is, byte for byte, the block the plan was asked about; routing.kernel_name is a prefix of the plan's kernel on every
+    served cell (contiguous out, tokens * n * 2 < 2^32; a bias alone is passed on).  Then the rules that stay in Python, one by one."""
     from zigma_amd import linear as zl, routing as zr
     bf = torch.bfloat16
     flags = {"ws": zl.LINEAR_WS_FLAG, "ws128": zl.LINEAR_WS_FLAG, "sm": zl.LINEAR_SM_FLAG, "tiled": 0}
+    eligible = {"ws": zl.linear_ws_eligible, "ws128": zl.linear_ws_eligible, "sm": zl.linear_sm_eligible, "tiled": zl.linear_eligible}
     served_by = {"ws": lambda pl: pl["family"] == LIN_WS and pl["pw"] == 256, "ws128": lambda pl: pl["family"] == LIN_WS and pl["pw"] == 128,
                  "sm": lambda pl: pl["family"] == LIN_SM, "tiled": lambda pl: pl["family"] in (LIN_TN, LIN_4W)}
     seen = {kern: set() for kern in flags}
-    for tokens in (8, 104, 128, 256, 512, 8192, 65536 + 8):
-        for n in (128, 384, 640, 4096, 8192, 8320):
-            for k in (64, 128, 192, 640, 768, 1280, 1536):
-                w = _Dev(bf, n, k, ptr=1 << 36)
-                for pitch in (k, k + 4, k + 8, k + 128):
-                    x = _Dev(bf, tokens, k, ptr=1 << 30)
-                    x._strides = (pitch, 1)
-                    for bias_ptr in (0, 1 << 42, (1 << 42) + 4, (1 << 42) + 2):      # absent, or on a 16- / 4- / 2-byte boundary
-                        bias = _Dev(bf, n, ptr=bias_ptr) if bias_ptr else None
-                        assert tokens * n * 2 < 1 << 32
-                        for kern, flag in flags.items():
-                            pl = linear_plan(_linear_params(tokens, n, k, flag, pitch, bias_ptr))
-                            served = pl["status"] == 0 and served_by[kern](pl)
-                            mirror = zl.linear_eligible(x, w, bias) and zr._SERVES[kern](tokens, n, k) and zl._TENSOR_LIMITS[kern](x, bias)
-                            assert mirror == served, (kern, tokens, n, k, pitch, bias_ptr, pl)
-                            seen[kern].add(served)
-                            if served:
-                                name = zr.kernel_name(kern, tokens, n, k, bias=bias is not None, residual=False)
-                                assert pl["kernel"].startswith(name), (kern, tokens, n, k, pitch, bias_ptr, pl, name)
-    assert all(v == {True, False} for v in seen.values()), seen
+    with torch.no_grad():
+        for tokens in (8, 104, 128, 256, 512, 8192, 65536 + 8):
+            for n in (128, 384, 640, 4096, 8192, 8320):
+                for k in (64, 128, 192, 640, 768, 1280, 1536):
+                    w = _Dev(bf, n, k, ptr=1 << 36)
+                    for pitch in (k, k + 4, k + 8, k + 128):
+                        x = _Dev(bf, tokens, k, ptr=1 << 30, pitched=(pitch, 1))
+                        for bias_ptr in (0, 1 << 42, (1 << 42) + 4, (1 << 42) + 2):      # absent, or on a 16- / 4- / 2-byte boundary
+                            bias = _Dev(bf, n, ptr=bias_ptr) if bias_ptr else None
+                            assert tokens * n * 2 < 1 << 32
+                            for kern, flag in flags.items():
+                                P = _linear_params(tokens, n, k, flag, pitch, bias_ptr)
+                                assert bytes(zl.linear_block(x, w, bias, flags=flag)) == bytes(P)
+                                pl = linear_plan(P)
+                                served = pl["status"] == 0 and served_by[kern](pl)
+                                mirror = eligible[kern](x, w, bias) and zr.serves(kern, tokens, n, k)
+                                assert mirror == served, (kern, tokens, n, k, pitch, bias_ptr, pl)
+                                seen[kern].add(served)
+                                if served:
+                                    name = zr.kernel_name(kern, tokens, n, k, bias=bias is not None, residual=False)
+                                    assert pl["kernel"].startswith(name), (kern, tokens, n, k, pitch, bias_ptr, pl, name)
+                                if pitch == k and not bias_ptr:        # the canonical call of the shape: routing.serves is the plan's answer alone
+                                    assert zr.serves(kern, tokens, n, k) == served, (kern, tokens, n, k, pl)
+        assert all(v == {True, False} for v in seen.values()), seen
+        # what a block cannot say: each rule on a call that every predicate accepts without it
+        x, w, b = _Dev(bf, 8, 1024, 640), _Dev(bf, 2560, 640, ptr=1 << 36), _Dev(bf, 2560, ptr=1 << 42)
+        ok = lambda x=x, w=w, b=b: zl.linear_eligible(x, w, b) and zl.linear_ws_eligible(x, w, None) and zl.linear_sm_eligible(x, w, b)
+        assert ok()
+        assert not ok(x=_Dev(bf, 8, 1024, 640, cuda=False))                                                      # the device
+        assert not ok(w=_Dev(torch.float16, 2560, 640, ptr=1 << 36)) and not ok(b=_Dev(torch.float16, 2560, ptr=1 << 42))          # one dtype
+        assert not ok(x=_Dev(bf, 8, 1024, 640, pitched=(1024 * 1280, 1280, 2))) and not ok(w=_Dev(bf, 2560, 640, ptr=1 << 36, pitched=(1280, 2)))   # unit channel stride
+        assert not ok(b=_Dev(bf, 2560, ptr=1 << 42, pitched=(2,)))                                              # bias stride
+        assert not ok(x=_Dev(bf, 8, 1024, 640, pitched=(1024 * 768, 768, 1))) and ok(x=_Dev(bf, 8192, 640, pitched=(768, 1)))       # a > 2-D x must be contiguous
+        assert not ok(w=_Dev(bf, 2560, 768, ptr=1 << 36))                                                       # x and weight share k
+        # ... and of the gated residual: one dtype, residual rows of all samples in one pitch, unit channel strides, (B, rows, k) input
+        res, gate = _Dev(bf, 8, 1024, 2560, ptr=1 << 44), _Dev(bf, 8, 2560, ptr=1 << 45)
+        gated = lambda x=x, res=res, gate=gate: zl.gated_residual_eligible(x, res, gate)
+        assert gated() and not gated(x=_Dev(bf, 8192, 640)) and not gated(res=_Dev(torch.float16, 8, 1024, 2560, ptr=1 << 44))
+        assert not gated(gate=_Dev(torch.float16, 8, 2560, ptr=1 << 45)) and not gated(res=_Dev(bf, 8, 1024, 2560, ptr=1 << 44, pitched=(1025 * 2560, 2560, 1)))
+        assert not gated(res=_Dev(bf, 8, 1024, 2560, ptr=1 << 44, pitched=(1024 * 5120, 5120, 2))) and not gated(gate=_Dev(bf, 8, 2560, ptr=1 << 45, pitched=(5120, 2)))
+        assert gated(res=_Dev(bf, 8, 1024, 2560, ptr=1 << 44, pitched=(1024 * 2568, 2568, 1))) and not gated(res=_Dev(bf, 8, 1024, 2560, ptr=(1 << 44) + 8))
+    grad = _Dev(bf, 8, 1024, 640)
+    grad.requires_grad = True
+    with torch.enable_grad():
+        assert ok() and not ok(x=grad)                                                                           # the autograd rule
+    with torch.no_grad():
+        assert ok(x=grad)
 
 
 @pytest.mark.parametrize("m,n", [(65536, 2560), (65536, 512), (32768, 2560), (4096, 8192), (5632, 1024), (512 * 43, 256), (16384, 1280)])

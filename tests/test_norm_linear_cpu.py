@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from test_host_cpu import libpath  # noqa: F401  (the module-scoped fixture: builds the library when it is not there — the predicates ask its plan query)
 from norm_linear_cases import BASE, BF16, CASES, F16, F32, OK, POINTERS, make_params
 
 _DRIVER = r"""
@@ -64,9 +65,9 @@ def test_case_table_covers_every_status_and_pointer():
     assert {c[3] for c in CASES if c[3]} == {"norm_linear_k512", "norm_linear_k640", "norm_linear_k768"}
 
 
-def test_tile_constants(plan):
-    from zigma_amd import norm_linear as nl
-    assert plan.tile == nl.TILE == 128
+def test_tile_constants(plan, libpath):  # noqa: F811
+    from zigma_amd.norm_linear import norm_linear_shape_ok
+    assert plan.tile == 128 and norm_linear_shape_ok(plan.tile, 512, 640, plan.tile) and not norm_linear_shape_ok(plan.tile // 2, 512, 640, plan.tile // 2)
     assert plan.lds_bytes == 67584 and 2 * plan.lds_bytes <= 160 * 1024          # two workgroups per CU
 
 
@@ -144,10 +145,12 @@ EDGES = [
 
 
 @pytest.mark.parametrize("kw,ok", EDGES)
-def test_python_predicate_agrees_with_the_plan(plan, kw, ok):
-    """norm_linear_eligible (tensors) and norm_linear_shape_ok (shapes) on the edges of each rule: True exactly where plan_norm_linear serves the call"""
-    from zigma_amd.norm_linear import norm_linear_eligible, norm_linear_shape_ok
+def test_python_predicate_agrees_with_the_plan(plan, kw, ok, libpath):  # noqa: F811
+    """norm_linear_eligible (tensors) and norm_linear_shape_ok (shapes) on the edges of each rule: True exactly where plan_norm_linear (compiled here with
+    g++, independent of the built library the predicates ask) serves the call; the block norm_linear_block builds is the block that plan was asked about"""
+    from zigma_amd.norm_linear import norm_linear_block, norm_linear_eligible, norm_linear_shape_ok
     x, w, shift, scale = _operands(**kw)
+    assert plan(norm_linear_block(x, w, shift, scale, 1e-6, Stand((x.shape[0] * x.shape[1], w.shape[0]), ptr=0x40000))) == _plan_of(plan, x, w, shift, scale)
     with torch.no_grad():
         got = norm_linear_eligible(x, w, shift, scale)
     served = _plan_of(plan, x, w, shift, scale)["kernel"] is not None
@@ -157,7 +160,7 @@ def test_python_predicate_agrees_with_the_plan(plan, kw, ok):
         assert norm_linear_shape_ok(m, w.shape[0], x.shape[2], L) == ok
 
 
-def test_predicate_refuses_what_the_plan_cannot_see():
+def test_predicate_refuses_what_the_plan_cannot_see(libpath):  # noqa: F811
     """mixed dtypes, a bias, CPU tensors, samples in different pitches, shift / scale in different pitches, autograd"""
     from zigma_amd.norm_linear import norm_linear_eligible as el
     with torch.no_grad():
@@ -179,7 +182,7 @@ class _ToQ:
         self.weight, self.bias = w, bias
 
 
-def test_block_engagement_rule(monkeypatch):
+def test_block_engagement_rule(monkeypatch, libpath):  # noqa: F811
     """model_zigma.fuse_norm_to_q on stand-ins: on at 65 536 tokens with no pending branch; off under routing.POLICY == "off", off below 65 536 tokens, off
     with a pending branch, under autograd, with the knob off; the new kernel is no row of the to_q role"""
     import zigma_amd.model_zigma as mz

@@ -7,6 +7,7 @@ HIP stream so that stream semantics (and graph capture) match the reference's ex
 (`at::cuda::getCurrentCUDAStream()`, selective_scan.cpp:326-327).
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -174,6 +175,9 @@ class LinearParams(C.Structure):
                 + [("residual", vp), ("gate", vp), ("res_row_stride", i64), ("gate_batch_stride", i64), ("rows_per_batch", i32), ("pad2_", i32)])
 
 
+LINEAR_WS, LINEAR_SM = 0x4000, 0x8000            # zigma_linear_params_t.flags: ZIGMA_LINEAR_WS (csrc/linear_ws.hip), ZIGMA_LINEAR_SM (csrc/linear_sm.hip)
+
+
 class LinearWgradParams(C.Structure):
     _fields_ = ([("m", i64), ("n", i32), ("k", i32), ("dtype", i32), ("out_dtype", i32), ("slabs", i32), ("flags", i32)]
                 + [(n, i64) for n in ("dy_row_stride", "x_row_stride", "out_row_stride")] + [(n, vp) for n in ("dy", "x", "out", "workspace")]
@@ -232,7 +236,7 @@ EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", 
            "zigma_cross_attn_bwd", "zigma_cross_attn_bwd_chunks", "zigma_patch_embed_fwd", "zigma_timestep_embed_fwd", "zigma_final_layer_fwd",
            "zigma_final_layer_cfg_fwd", "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel",
            "zigma_selective_scan_fwd_plan", "zigma_causal_conv1d_fwd_plan", "zigma_conv_x_proj_fwd_plan", "zigma_x_proj_fwd_plan",
-           "zigma_dt_proj_softplus_fwd_plan")
+           "zigma_dt_proj_softplus_fwd_plan", "zigma_linear_fwd_plan", "zigma_norm_linear_fwd_plan", "zigma_linear_f32_split_plan")
 
 _lib = None
 
@@ -266,7 +270,8 @@ def lib():
             fn.argtypes = [C.POINTER(st)]
             fn.restype = C.c_int64
         for name, st in (("zigma_selective_scan_fwd", ScanParams), ("zigma_causal_conv1d_fwd", ConvParams), ("zigma_conv_x_proj_fwd", ConvXProjParams),
-                         ("zigma_x_proj_fwd", XProjParams), ("zigma_dt_proj_softplus_fwd", DtProjParams)):
+                         ("zigma_x_proj_fwd", XProjParams), ("zigma_dt_proj_softplus_fwd", DtProjParams), ("zigma_linear_fwd", LinearParams),
+                         ("zigma_norm_linear_fwd", NormLinearParams), ("zigma_linear_f32_split", LinearSplitParams)):
             fn = getattr(L, name + "_plan")
             fn.argtypes = [C.POINTER(st), C.POINTER(C.c_char_p)]
             fn.restype = C.c_int
@@ -312,6 +317,68 @@ def require_device(*tensors):
     return dev
 
 
+FRESH_ADDRESS = 1 << 40     # placeholder address of a tensor that is yet to be allocated (the k-th stand-in of a block: k times this)
+
+
+class Desc:
+    """What the block builders read of a tensor (shape, strides, dtype, address), for the plan queries: of a tensor that exists (`of`), or of
+    contiguous rows the front is yet to allocate (`fresh`), with the views mamba_inner_tok takes of u and x_dbl.  A fresh tensor's address is a
+    placeholder — non-zero, on a page boundary (the caching allocator hands out blocks on 512-byte boundaries, the plans ask for 16 bytes at
+    most) and 1 TiB from the next one, so no two overlap.  A block built on placeholders is asked about; before one is launched, every address
+    in it is set from the real tensors (scan_planned, linear_planned).  The ONE stand-in type of the package: the shadows of amp.py (amp.Like) and the
+    transposed weight of wgrad.py are `fresh` descriptors too, and read like a tensor that requires no grad."""
+    __slots__ = ("dtype", "shape", "strides", "address", "is_cuda", "requires_grad")
+
+    def __init__(self, dtype, shape, strides, address, is_cuda=True, requires_grad=False):
+        self.dtype, self.shape, self.strides, self.address, self.is_cuda, self.requires_grad = dtype, shape, strides, address, is_cuda, requires_grad
+
+    @classmethod
+    def of(cls, t):
+        if isinstance(t, cls):
+            return t
+        return cls(t.dtype, tuple(t.shape), tuple([t.stride(i) for i in range(t.dim())]), t.data_ptr(), t.is_cuda)
+
+    @classmethod
+    def fresh(cls, like, shape, k, dtype=None):
+        """contiguous rows of this shape in like's dtype and on its device (like None: dtype, on the device) at the k-th placeholder address"""
+        strides, n = [], 1
+        for d in reversed(shape):
+            strides.append(n)
+            n *= d
+        return cls(dtype or like.dtype, tuple(shape), tuple(reversed(strides)), k * FRESH_ADDRESS, like is None or like.is_cuda)
+
+    def stride(self, i=None):
+        return self.strides if i is None else self.strides[i]
+
+    def dim(self):
+        return len(self.shape)
+
+    def data_ptr(self):
+        return self.address
+
+    def numel(self):
+        return math.prod(self.shape)
+
+    def is_contiguous(self):
+        n = 1
+        for d, st in zip(reversed(self.shape), reversed(self.strides)):
+            if d != 1 and st != n:
+                return False
+            n *= d
+        return True
+
+    def scan_view(self):
+        """(B, L, C) rows as the scan's (batch, dim, seqlen) operand: t.transpose(1, 2)"""
+        (B, L, C), (sb, sl, sc) = self.shape, self.strides
+        return Desc(self.dtype, (B, C, L), (sb, sc, sl), self.address, self.is_cuda)
+
+    def columns(self, first, n):
+        """columns [first, first + n) of (B, L, C) rows as the scan's (batch, 1, dstate, seqlen) B / C operand:
+        t[:, :, first:first + n].transpose(1, 2).unsqueeze(1)"""
+        (B, L, _), (sb, sl, sc) = self.shape, self.strides
+        return Desc(self.dtype, (B, 1, n, L), (sb, n * sc, sc, sl), self.address + first * sc * self.dtype.itemsize, self.is_cuda)
+
+
 def workspace(fn_name, params, device):
     """Allocate the caller-owned scratch buffer a backward entry point asks for and attach it to the parameter block."""
     nbytes = getattr(lib(), fn_name + "_workspace_bytes")(C.byref(params))
@@ -320,14 +387,22 @@ def workspace(fn_name, params, device):
     return ws
 
 
+_PLAN_FNS = {}
+
+
 def plan(fn_name, params):
     """Ask the library what the entry point `fn_name` would do with this parameter block -> (status, kernel name or None): the status the launch
     would return and what zigma_last_kernel() would report after it (None: a refusal or an empty call).  The five forward entry points of the Mamba
-    inner answer (plan_scan() of csrc/scan_plan.h, the plans of csrc/front_plan.h).  Host only: nothing is launched or dereferenced, so the block
+    inner answer (plan_scan() of csrc/scan_plan.h, the plans of csrc/front_plan.h) and the three of the dense projections (plan_linear() and
+    plan_linear_split() of csrc/linear_plan.h, plan_norm_linear() of csrc/norm_linear_plan.h).  Host only: nothing is launched or dereferenced, so the block
     may describe tensors that are yet to be allocated."""
+    fn = _PLAN_FNS.get(fn_name)
+    if fn is None:
+        fn = _PLAN_FNS[fn_name] = getattr(lib(), fn_name + "_plan")
     kernel = C.c_char_p()
-    rc = getattr(lib(), fn_name + "_plan")(C.byref(params), C.byref(kernel))
-    return rc, kernel.value.decode() if kernel.value else None
+    rc = fn(C.byref(params), C.byref(kernel))
+    name = kernel.value
+    return rc, name.decode() if name else None
 
 
 TRACE = None        # tests / tools: set to a list to receive (entry point, kernel that served it, parameter block) per call

@@ -55,28 +55,10 @@ def _watch_optimizers():
 _watch_optimizers()
 
 
-class Like:
+def Like(p, dtype, k=2):
     """What a shadow of parameter p WILL look like, as the planning predicates read a tensor (device, dtype, shape, contiguous strides, an aligned address,
-    no grad): arena slots start on 256-byte boundaries and a fresh `.to()` is an aligned allocation, so a plan needs no cast."""
-
-    def __init__(self, p, dtype):
-        self.is_cuda, self.device, self.dtype, self.requires_grad, self.shape = p.is_cuda, p.device, dtype, False, p.shape
-        self._strides = tuple(torch.empty(p.shape, device="meta").stride())
-
-    def stride(self, i=None):
-        return self._strides if i is None else self._strides[i]
-
-    def dim(self):
-        return len(self.shape)
-
-    def numel(self):
-        return self.shape.numel()
-
-    def data_ptr(self):
-        return 0
-
-    def is_contiguous(self):
-        return True
+    no grad): arena slots start on 256-byte boundaries and a fresh `.to()` is an aligned allocation, so a plan needs no cast.  The k-th placeholder of its block."""
+    return _lib.Desc.fresh(p, tuple(p.shape), k, dtype)
 
 
 def autocast_dtype():
@@ -263,7 +245,7 @@ def planned(x, weight, bias=None):
     d = autocast_dtype()
     if d not in _DTYPES or x.dtype != d or weight.dtype != torch.float32 or not weight.is_cuda:
         return weight, bias
-    return Like(weight, d), (Like(bias, d) if bias is not None and bias.dtype == torch.float32 else bias)
+    return Like(weight, d), (Like(bias, d, 3) if bias is not None and bias.dtype == torch.float32 else bias)
 
 
 def mixed(x, weight):

@@ -392,3 +392,7 @@ extern "C" int zigma_linear_fwd(const zigma_linear_params_t *pp, void *stream_) 
     set_last_kernel(plan.kernel);
     return check_launch();
 }
+
+extern "C" int zigma_linear_fwd_plan(const zigma_linear_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_linear(*pp, kernel) : ZIGMA_ERR_NULL;
+}

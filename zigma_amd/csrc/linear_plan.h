@@ -1,4 +1,5 @@
-// The plan of a zigma_linear_fwd call: its refusal, or the kernel family, template switches and launch geometry that serve it.
+// The plans of a zigma_linear_fwd call and of a zigma_linear_f32_split call: the refusal, or the kernel family, template switches and launch geometry that
+// serve it.
 // Plain C++ without HIP, so the CPU tests compile it on its own; the launchers only map a plan to template instantiations.
 #pragma once
 #include <stdint.h>
@@ -153,6 +154,49 @@ inline LinearPlan plan_linear(const zigma_linear_params_t &p) {
     s.stages = (s.wide || (p.flags & 0x800)) ? 2 : 3;                              // 0x800: two stages on the 256 x 128 tile (probe)
     s.bias = p.bias != nullptr; s.res = p.residual && s.stages == 3;
     return serve(kLinTn, s.wide ? "linear_tn_256x256" : "linear_tn_256x128");
+}
+
+// zigma_linear_fwd_plan: the launch's status and the kernel it would report (null: a refusal or an empty call)
+inline int query_linear(const zigma_linear_params_t &p, const char **kernel) {
+    const LinearPlan s = plan_linear(p);
+    *kernel = s.family == kLinNone ? nullptr : s.kernel;
+    return s.status;
+}
+
+// The plan of a zigma_linear_f32_split call (csrc/linear_split.hip): its refusal, or the instantiation (one pass or three) and the grid of
+// 128-token x 128-feature tiles that serve it.
+constexpr int kSplitBM = 128, kSplitBN = 128;
+
+struct LinearSplitPlan {
+    int status = ZIGMA_OK;          // returned when kernel is null: a refusal, or ZIGMA_OK (empty call)
+    const char *kernel = nullptr;   // zigma_last_kernel()
+    bool lo = false;                // three passes: the w_lo plane is read
+    int64_t tiles = 0;
+};
+
+inline LinearSplitPlan plan_linear_split(const zigma_linear_split_params_t &p) {
+    LinearSplitPlan s;
+    auto refuse = [&s](int status) { s.status = status; return s; };
+    if (!p.x || !p.w_hi || !p.out || (p.passes == 3 && !p.w_lo)) return refuse(ZIGMA_ERR_NULL);
+    if (p.flags != 0 || (p.passes != 1 && p.passes != 3)) return refuse(ZIGMA_ERR_UNSUPPORTED);
+    s.lo = p.passes == 3;
+    if (p.m < 0 || p.m % 8 != 0 || p.n < 128 || p.n % 128 != 0 || p.n > 65536 || p.k < 64 || p.k % 64 != 0 || p.k > 65536) return refuse(ZIGMA_ERR_SHAPE);
+    if (p.x_row_stride < p.k || p.w_hi_row_stride < p.k || (s.lo && p.w_lo_row_stride < p.k) || p.out_row_stride < p.n) return refuse(ZIGMA_ERR_SHAPE);
+    s.tiles = (p.m + kSplitBM - 1) / kSplitBM * (p.n / kSplitBN);
+    if (s.tiles > 0x7fffffff) return refuse(ZIGMA_ERR_SHAPE);
+    const auto misaligned = [](const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 != 0; };
+    if (misaligned(p.x) || misaligned(p.w_hi) || (s.lo && misaligned(p.w_lo)) || misaligned(p.out) || (p.bias && misaligned(p.bias)) ||
+        p.x_row_stride % 4 != 0 || p.out_row_stride % 4 != 0 || p.w_hi_row_stride % 8 != 0 || (s.lo && p.w_lo_row_stride % 8 != 0))
+        return refuse(ZIGMA_ERR_STRIDE);
+    if (p.m == 0) return s;         // empty: nothing to launch
+    s.kernel = s.lo ? "linear_split3_128x128" : "linear_split1_128x128";
+    return s;
+}
+
+inline int query_linear_split(const zigma_linear_split_params_t &p, const char **kernel) {
+    const LinearSplitPlan s = plan_linear_split(p);
+    *kernel = s.kernel;
+    return s.status;
 }
 
 }  // namespace zigma

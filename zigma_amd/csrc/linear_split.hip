@@ -21,11 +21,12 @@
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; the build fails on scratch or a spill in either instantiation): DESIGN.md §3.4.
 #include "zigma_common.h"
+#include "linear_plan.h"
 
 namespace zigma {
 namespace lsp {
 
-constexpr int kBM = 128, kBN = 128, kBK = 64, kThreads = 256;
+constexpr int kBM = kSplitBM, kBN = kSplitBN, kBK = 64, kThreads = 256;      // (the tile plan_linear_split() counts the grid in)
 constexpr int kPlane = 128 * 128;                       // bytes of one LDS plane: 128 rows x 64 bf16
 constexpr int kEpiPitch = 64 * 4 + 16;                  // epilogue tile: bytes per token row (64 fp32 features, padded)
 constexpr uint32_t kMaxBf16Bits = 0x7f7f0000u;          // the largest finite bf16 as an fp32 pattern
@@ -230,18 +231,9 @@ using namespace zigma;
 extern "C" int zigma_linear_f32_split(const zigma_linear_split_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     const zigma_linear_split_params_t &p = *pp;
-    if (!p.x || !p.w_hi || !p.out || (p.passes == 3 && !p.w_lo)) return ZIGMA_ERR_NULL;
-    if (p.flags != 0 || (p.passes != 1 && p.passes != 3)) return ZIGMA_ERR_UNSUPPORTED;
-    const bool lo = p.passes == 3;
-    if (p.m < 0 || p.m % 8 != 0 || p.n < 128 || p.n % 128 != 0 || p.n > 65536 || p.k < 64 || p.k % 64 != 0 || p.k > 65536) return ZIGMA_ERR_SHAPE;
-    if (p.x_row_stride < p.k || p.w_hi_row_stride < p.k || (lo && p.w_lo_row_stride < p.k) || p.out_row_stride < p.n) return ZIGMA_ERR_SHAPE;
-    const int64_t tiles = (p.m + lsp::kBM - 1) / lsp::kBM * (p.n / lsp::kBN);
-    if (tiles > 0x7fffffff) return ZIGMA_ERR_SHAPE;
-    const auto misaligned = [](const void *q) { return reinterpret_cast<uintptr_t>(q) % 16 != 0; };
-    if (misaligned(p.x) || misaligned(p.w_hi) || (lo && misaligned(p.w_lo)) || misaligned(p.out) || (p.bias && misaligned(p.bias)) ||
-        p.x_row_stride % 4 != 0 || p.out_row_stride % 4 != 0 || p.w_hi_row_stride % 8 != 0 || (lo && p.w_lo_row_stride % 8 != 0))
-        return ZIGMA_ERR_STRIDE;
-    if (p.m == 0) return ZIGMA_OK;
+    const LinearSplitPlan plan = plan_linear_split(p);         // every refusal: csrc/linear_plan.h
+    if (!plan.kernel) return plan.status;
+    const bool lo = plan.lo;
 
     (void)hipGetLastError();                                  // (after the refusals: a refused block never touches the device)
     lsp::args_t a;
@@ -252,10 +244,14 @@ extern "C" int zigma_linear_f32_split(const zigma_linear_split_params_t *pp, voi
     a.out = static_cast<float *>(p.out);
     a.x_pitch = p.x_row_stride, a.wh_pitch = p.w_hi_row_stride, a.wl_pitch = lo ? p.w_lo_row_stride : 0, a.o_pitch = p.out_row_stride;
     a.m = p.m, a.n = p.n, a.k = p.k, a.tiles_n = p.n / lsp::kBN;
-    const dim3 grid(static_cast<unsigned>(tiles)), block(lsp::kThreads);
+    const dim3 grid(static_cast<unsigned>(plan.tiles)), block(lsp::kThreads);
     const hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (lo) hipLaunchKernelGGL(lsp::linear_split_kernel<3>, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(lsp::linear_split_kernel<1>, grid, block, 0, stream, a);
-    set_last_kernel(lo ? "linear_split3_128x128" : "linear_split1_128x128");
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+extern "C" int zigma_linear_f32_split_plan(const zigma_linear_split_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_linear_split(*pp, kernel) : ZIGMA_ERR_NULL;
 }

@@ -246,3 +246,7 @@ extern "C" int zigma_norm_linear_fwd(const zigma_norm_linear_params_t *pp, void 
     set_last_kernel(plan.kernel);
     return check_launch();
 }
+
+extern "C" int zigma_norm_linear_fwd_plan(const zigma_norm_linear_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_norm_linear(*pp, kernel) : ZIGMA_ERR_NULL;
+}

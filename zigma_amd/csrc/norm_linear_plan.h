@@ -46,4 +46,11 @@ inline NormLinearPlan plan_norm_linear(const zigma_norm_linear_params_t &p) {
     return s;
 }
 
+// zigma_norm_linear_fwd_plan: the launch's status and the kernel it would report (null: a refusal or an empty call)
+inline int query_norm_linear(const zigma_norm_linear_params_t &p, const char **kernel) {
+    const NormLinearPlan s = plan_norm_linear(p);
+    *kernel = s.kernel;
+    return s.status;
+}
+
 }  // namespace zigma

@@ -98,29 +98,37 @@ def clear_cache():
 
 
 # ---- the call ----------------------------------------------------------------------------------------------------------------------------------
+def linear_split_block(x, w_hi, w_lo, bias, out, passes):
+    """The parameter block of zigma_linear_f32_split: x (m, k) fp32 rows one pitch apart or contiguous (..., k), the weight's bf16 planes (one pass reads
+    w_hi only), out (m, n) fp32 rows (None: fresh contiguous rows, a placeholder address — a block to ask about).  Reads shapes, strides and
+    addresses only, so descriptors (_lib.Desc) serve as well as tensors."""
+    n, k = w_hi.shape[0], x.shape[-1]
+    m = x.numel() // k
+    if out is None:
+        out = _lib.Desc.fresh(x, (m, n), 1)
+    P = _lib.LinearSplitParams()
+    P.m, P.n, P.k, P.passes, P.flags = m, n, k, passes, 0
+    P.x_row_stride, P.w_hi_row_stride, P.w_lo_row_stride, P.out_row_stride = x.stride(-2), w_hi.stride(0), w_lo.stride(0), out.stride(-2)
+    P.x, P.w_hi, P.w_lo, P.bias, P.out = _lib.ptr(x), _lib.ptr(w_hi), _lib.ptr(w_lo) if passes == 3 else None, _lib.ptr(bias), _lib.ptr(out)
+    return P
+
+
 def split_eligible(x, weight, bias=None):
-    """LIMITS of zigma_linear_f32_split on these tensors (the shape classes of linear.linear_eligible, so routing shapes carry over): fp32
-    throughout, on the device, k % 64 == 0, n % 128 == 0, tokens % 8 == 0, 16-byte aligned rows (x may be a 2-D view of wider rows), no autograd"""
+    """zigma_linear_f32_split takes x @ weight.T (+ bias) on these tensors: what plan_linear_split() (csrc/linear_plan.h) serves with three passes on fresh
+    contiguous planes of the weight (nothing is split or cached for the question), and what the block cannot say — fp32 throughout, on the device, a 2-D
+    weight, unit channel strides, a > 2-D x that is one sequence of rows, no autograd"""
     f32 = torch.float32
-    if not (x.is_cuda and weight.is_cuda and x.dtype == f32 and weight.dtype == f32):
+    if not (x.is_cuda and weight.is_cuda and x.dtype == f32 and weight.dtype == f32 and len(weight.shape) == 2 and x.dim() >= 2):
         return False
-    if bias is not None and not (bias.is_cuda and bias.dtype == f32 and bias.stride(0) == 1 and bias.data_ptr() % 16 == 0):
+    if bias is not None and not (bias.is_cuda and bias.dtype == f32 and bias.stride(0) == 1):
         return False
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         return False
-    if len(weight.shape) != 2:
+    if x.shape[-1] != weight.shape[1] or x.stride(-1) != 1 or (x.dim() > 2 and not x.is_contiguous()):
         return False
-    n, k = weight.shape
-    if k < 64 or k % 64 or n < 128 or n % 128 or n > 65536 or k > 65536 or x.shape[-1] != k or x.stride(-1) != 1:
-        return False
-    m = x.numel() // k
-    if m % 8 or m == 0 or -(-m // 128) * (n // 128) >= 2 ** 31:
-        return False
-    if x.dim() > 2 and not x.is_contiguous():
-        return False
-    if x.dim() >= 2 and (x.stride(-2) % 4 or x.stride(-2) < k):
-        return False
-    return x.data_ptr() % 16 == 0
+    w_hi, w_lo = (_lib.Desc.fresh(x, tuple(weight.shape), i, torch.bfloat16) for i in (2, 3))
+    status, kernel = _lib.plan("zigma_linear_f32_split", linear_split_block(x, w_hi, w_lo, bias, None, 3))
+    return status == 0 and kernel is not None
 
 
 def linear_split(x, weight, bias=None, mode=None, out=None):
@@ -145,11 +153,7 @@ def linear_split(x, weight, bias=None, mode=None, out=None):
         raise RuntimeError("linear_split: out must be (..., n) float32 rows with channel stride 1")
     o2 = out if out.dim() == 2 else out.view(-1, n)
     w_hi, w_lo = split_weight(weight)
-    P = _lib.LinearSplitParams()
-    P.m, P.n, P.k, P.passes, P.flags = x2.shape[0], n, k, _PASSES[mode], 0
-    P.x_row_stride, P.w_hi_row_stride, P.w_lo_row_stride, P.out_row_stride = x2.stride(0), w_hi.stride(0), w_lo.stride(0), o2.stride(0)
-    P.x, P.w_hi, P.w_lo, P.bias, P.out = _lib.ptr(x2), _lib.ptr(w_hi), _lib.ptr(w_lo) if mode == "high" else None, _lib.ptr(bias), _lib.ptr(o2)
-    _lib.call("zigma_linear_f32_split", P, dev)
+    _lib.call("zigma_linear_f32_split", linear_split_block(x2, w_hi, w_lo, bias, o2, _PASSES[mode]), dev)
     return out if out.dim() == len(lead) + 1 and out.shape[:-1] == lead else out.view(*lead, n)
 
 

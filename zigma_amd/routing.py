@@ -14,21 +14,23 @@ kernel = which kernel family of zigma_linear_fwd serves it (KERNELS below), or "
          E x tokens and compares the library cells with a reviewed list.
 fuse_add = the caller hands the gated residual to the kernel's epilogue (True) or leaves it to the next norm kernel (False).
 
-The table holds POLICY (what is fastest where, with the measurement that decided it); the shape LIMITS of each kernel family are the
-`serves_*` functions: the shape part of plan_linear() (csrc/linear_plan.h, where every refusal and kernel choice of zigma_linear_fwd lives), restated here
-because the table is consulted before a parameter block exists and on machines without the library; tests/test_host_cpu.py compiles the header and pins
-them to it (test_linear_mirrors_agree_with_the_plan) — a row never returns a kernel whose limits the shape does not meet.  linear.plan walks candidates() and
-checks each kernel's limits on the tensors (pointer / stride alignment, bias); a row the tensors refuse is counted in REFUSED and the walk goes on
-to the next row (never silent: tests assert REFUSED stays empty on the shipped shapes).
+The table holds POLICY (what is fastest where, with the measurement that decided it).  The shape LIMITS of each kernel family are the library's:
+serves(kernel, tokens, n, k) asks plan_linear() (csrc/linear_plan.h, where every refusal and kernel choice of zigma_linear_fwd lives; zigma_linear_fwd_plan)
+about the canonical call of that shape — aligned contiguous bf16 operands, no bias, a fresh output — with that family's selector set, and reads the family
+and panel width off the kernel it names.  So the table needs the built library, as the Mamba inner's plan does: without it route() raises _lib.lib()'s
+"not built" error.  A row never returns a kernel whose limits the shape does not meet.  linear.plan walks candidates() and asks the library about the
+call's own block (pointer / stride alignment, bias); a row it refuses there is counted in REFUSED and the walk goes on to the next row (never silent:
+tests assert REFUSED stays empty on the shipped shapes).
 
 Knobs (tools / tests; no environment variable of their own — ZIGMA_KNOBS="routing.POLICY=off,routing.DISABLED=in_proj.ws+to_q.sm"):
   POLICY    "auto" the table;  "all" every block projection the tiled kernels can serve runs on them (fused epilogues on; "text" and "train"
             as under "auto");  "off" library only, every role
   DISABLED  row ids skipped ("+"-separated string or a set): A/B of one row against what the table holds below it
 """
+import functools
 from collections import namedtuple
 
-from . import _knobs
+from . import _knobs, _lib
 
 Route = namedtuple("Route", "kernel fuse_add row")
 Row = namedtuple("Row", "id role k n tokens kernel fuse_add why")
@@ -50,44 +52,45 @@ INF = 1 << 40
 REFUSED = []          # (role, tokens, n, k, kernel) of rows a call matched and the tensor-level check of linear.py turned down (the last 64 of them)
 
 
-# ---- shape limits of the kernel families (plan_linear's, pinned by test) ---------------------------------------------------------------------------------
-def serves_tiled(tokens, n, k):
-    return tokens > 0 and tokens % 8 == 0 and n % 128 == 0 and k % 64 == 0
+# ---- shape limits of the kernel families: the library's plan on the canonical call of a shape ----------------------------------------------------------
+SELECTOR = {"ws": _lib.LINEAR_WS, "ws128": _lib.LINEAR_WS, "sm": _lib.LINEAR_SM, "tiled": 0}          # zigma_linear_params_t.flags of the one-launch families
 
 
-def tiles_4w(tokens, n):
-    return (tokens // 256) * -(-n // 256)
+@functools.lru_cache(maxsize=None)
+def _canonical(flags, tokens, n, k, bias=False, residual=False):
+    """the kernel plan_linear() serves the canonical call of this shape with (None: refused, or nothing to launch): bf16 rows at placeholder addresses, x
+    and weight contiguous, a fresh output; bias / residual: the epilogue operands, the gated residual in the output's pitch on samples of the largest power
+    of two of rows that divides the tokens.  Memoised: a pure function of its arguments, and the table is walked on every projection call."""
+    P = _lib.LinearParams()
+    P.m, P.n, P.k, P.dtype, P.flags, P.silu_from_col = tokens, n, k, _lib.BF16, flags, n
+    P.x_row_stride, P.w_row_stride, P.out_row_stride = k, k, n
+    P.x, P.w, P.out, P.bias = (i * _lib.FRESH_ADDRESS if i else None for i in (1, 2, 3, 4 if bias else 0))
+    if residual:
+        P.residual, P.gate, P.res_row_stride, P.gate_batch_stride, P.rows_per_batch = 5 * _lib.FRESH_ADDRESS, 6 * _lib.FRESH_ADDRESS, n, n, tokens & -tokens
+    status, kernel = _lib.plan("zigma_linear_fwd", P)
+    return kernel if status == 0 else None
 
 
-def serves_4w(tokens, n, k):
-    """the generated one-wave-per-SIMD kernel takes the call: whole 256-token tiles, k >= 192, at least one tile per CU.  Equals plan_linear()'s choice
-    between the 4-wave and the 8-wave kernel (linear4w_variant in csrc/linear_plan.h) on this domain: a call without flags or SiLU range, no bias alone
-    (a bias without the gated residual runs on the 8-wave kernel), contiguous 16-byte aligned out, tokens * n * 2 < 2^32; with the gated residual
-    also samples of 2^i rows and residual rows in the output's pitch, a multiple of 128 elements."""
-    return tokens % 256 == 0 and n % 128 == 0 and k % 64 == 0 and k >= 192 and tiles_4w(tokens, n) >= 256
+def family(kernel):
+    """the table's name (KERNELS) of the family a kernel that zigma_linear_fwd's plan names belongs to; None for None"""
+    if kernel is None:
+        return None
+    return "ws128" if kernel == "linear_ws_128" else "ws" if kernel.startswith("linear_ws") else "sm" if kernel.startswith("linear_sm_") else "tiled"
 
 
-def ws_panel_width(k):
-    return 256 if k in (512, 640) else 128 if k in (1280, 1536) else 0
+def serves(kernel, tokens, n, k):
+    """the kernel family `kernel` (KERNELS, or "4w": the generated 4-wave kernel within "tiled") takes the canonical call of this shape"""
+    if kernel == "library":
+        return True
+    if kernel == "tiled_halves":        # (policy: each half is whole 256-feature tiles)
+        return n % 512 == 0 and serves("tiled", tokens, n // 2, k)
+    got = _canonical(SELECTOR.get(kernel, 0), tokens, n, k)
+    return got is not None and got.startswith("linear4w") if kernel == "4w" else family(got) == kernel
 
 
-def serves_ws(tokens, n, k):
-    """linear_ws_panel (csrc/linear_plan.h): instantiated k, whole panels, at most 32 of them, every workgroup of an XCD owns a 512-token tile"""
-    pw = ws_panel_width(k)
-    if not pw or n % pw or n > 8192 or n // pw > 32 or tokens % 512:
-        return False
-    return tokens // 512 >= 32 // (n // pw)
-
-
-def serves_sm(tokens, n, k):
-    return k % 64 == 0 and k >= 128 and tokens % 128 == 0 and tokens >= 128 and n % 128 == 0
-
-
-_SERVES = {"ws": lambda t, n, k: serves_ws(t, n, k) and ws_panel_width(k) == 256,
-           "ws128": lambda t, n, k: serves_ws(t, n, k) and ws_panel_width(k) == 128,
-           "sm": serves_sm, "tiled": serves_tiled,
-           "tiled_halves": lambda t, n, k: n % 512 == 0 and serves_tiled(t, n // 2, k),
-           "library": lambda t, n, k: True}
+serves_tiled, serves_sm = functools.partial(serves, "tiled"), functools.partial(serves, "sm")
+serves_4w = functools.partial(serves, "4w")          # the generated one-wave-per-SIMD kernel takes the call (linear4w_variant; smaller calls: the 8-wave kernel)
+serves_ws = lambda tokens, n, k: serves("ws", tokens, n, k) or serves("ws128", tokens, n, k)          # in either panel width (linear_ws_panel)
 
 
 # ---- the table: first matching enabled row whose kernel serves the shape wins ----------------------------------------------------------------
@@ -161,7 +164,7 @@ def candidates(role, tokens, n, k):
         yield Route("library", False, "policy.off")
         return
     if POLICY == "all" and role in BLOCK_ROLES:
-        if serves_tiled(tokens, n, k):
+        if serves("tiled", tokens, n, k):
             yield Route("tiled", role in ("out_proj", "to_out"), "policy.all")
         yield Route("library", False, "policy.all")
         return
@@ -169,9 +172,9 @@ def candidates(role, tokens, n, k):
     for row in TABLE:
         if row.role != role or row.id in off or not (_in(k, row.k) and _in(n, row.n) and _in(tokens, row.tokens)):
             continue
-        if not _SERVES[row.kernel](tokens, n, k):
+        if not serves(row.kernel, tokens, n, k):
             continue
-        if row.id in ("in_proj.tiled_wide_k", "in_proj.tiled_narrow", "out_proj.tiled") and not serves_4w(tokens, n, k):
+        if row.id in ("in_proj.tiled_wide_k", "in_proj.tiled_narrow", "out_proj.tiled") and not serves("4w", tokens, n, k):
             continue              # (these rows are only faster than what follows them on the 4-wave kernel)
         yield Route(row.kernel, row.fuse_add, row.id)
         if row.kernel == "library":
@@ -186,11 +189,11 @@ def route(role, tokens, n, k):
 
 def kernel_name(route_or_kernel, tokens=None, n=None, k=None, bias=False, residual=False):
     """what zigma_last_kernel() reports for a call served by this route (prefix for the families with several tile shapes); bias / residual: the
-    epilogue operands of the call — a bias without the gated residual runs on the 8-wave kernel (serves_4w's domain)"""
+    epilogue operands of the call — the 4-wave or the 8-wave kernel is the plan's answer for the canonical call of the shape with them attached"""
     kern = route_or_kernel.kernel if isinstance(route_or_kernel, Route) else route_or_kernel
     if kern in ("tiled", "tiled_halves"):
         if tokens is None:
             return "linear"
-        nn = n // 2 if kern == "tiled_halves" else n
-        return ("linear4w_256x256+128" if nn % 256 else "linear4w_256x256") if serves_4w(tokens, nn, k) and (residual or not bias) else "linear_tn_"
+        got = _canonical(0, tokens, n // 2 if kern == "tiled_halves" else n, k, bool(bias), bool(residual))
+        return got if got is not None and got.startswith("linear4w") else "linear_tn_"
     return {"ws": "linear_ws", "ws128": "linear_ws_128", "sm": "linear_sm_", "split3": "linear_split3_", "split1": "linear_split1_", "library": "library"}[kern]

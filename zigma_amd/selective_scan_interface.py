@@ -65,61 +65,7 @@ def split_chunk_len(batch, d_inner, seqlen, reset_period=0):
     return chunk if -(-seqlen // chunk) >= 2 else 0
 
 
-FRESH_ADDRESS = 1 << 40     # placeholder address of a tensor that is yet to be allocated (the k-th stand-in of a block: k times this)
-
-
-class _Desc:
-    """What the block builders read of a tensor (shape, strides, dtype, address), for the plan queries: of a tensor that exists (`of`), or of
-    contiguous rows the front is yet to allocate (`fresh`), with the views mamba_inner_tok takes of u and x_dbl.  A fresh tensor's address is a
-    placeholder — non-zero, on a page boundary (the caching allocator hands out blocks on 512-byte boundaries, the plans ask for 16 bytes at
-    most) and 1 TiB from the next one, so no two overlap.  A block built on placeholders is asked about; before one is launched, every address
-    in it is set from the real tensors (scan_planned)."""
-    __slots__ = ("dtype", "shape", "strides", "address", "is_cuda")
-
-    def __init__(self, dtype, shape, strides, address, is_cuda=True):
-        self.dtype, self.shape, self.strides, self.address, self.is_cuda = dtype, shape, strides, address, is_cuda
-
-    @classmethod
-    def of(cls, t):
-        if isinstance(t, cls):
-            return t
-        return cls(t.dtype, tuple(t.shape), tuple([t.stride(i) for i in range(t.dim())]), t.data_ptr(), t.is_cuda)
-
-    @classmethod
-    def fresh(cls, like, shape, k, dtype=None):
-        strides, n = [], 1
-        for d in reversed(shape):
-            strides.append(n)
-            n *= d
-        return cls(dtype or like.dtype, shape, tuple(reversed(strides)), k * FRESH_ADDRESS, like.is_cuda)
-
-    def stride(self, i):
-        return self.strides[i]
-
-    def dim(self):
-        return len(self.shape)
-
-    def data_ptr(self):
-        return self.address
-
-    def is_contiguous(self):
-        n = 1
-        for d, st in zip(reversed(self.shape), reversed(self.strides)):
-            if d != 1 and st != n:
-                return False
-            n *= d
-        return True
-
-    def scan_view(self):
-        """(B, L, C) rows as the scan's (batch, dim, seqlen) operand: t.transpose(1, 2)"""
-        (B, L, C), (sb, sl, sc) = self.shape, self.strides
-        return _Desc(self.dtype, (B, C, L), (sb, sc, sl), self.address, self.is_cuda)
-
-    def columns(self, first, n):
-        """columns [first, first + n) of (B, L, C) rows as the scan's (batch, 1, dstate, seqlen) B / C operand:
-        t[:, :, first:first + n].transpose(1, 2).unsqueeze(1)"""
-        (B, L, _), (sb, sl, sc) = self.shape, self.strides
-        return _Desc(self.dtype, (B, 1, n, L), (sb, n * sc, sc, sl), self.address + first * sc * self.dtype.itemsize, self.is_cuda)
+_Desc = _lib.Desc          # what the block builders read of a tensor, for the plan queries (of / fresh / scan_view / columns)
 
 
 def _as_bgnl(M, name):

@@ -49,26 +49,10 @@ def _bmm_takes_out_dtype(x):
     return hit
 
 
-class _ContiguousLike:
-    """Stand-in for `weight.t().contiguous()` in linear.plan, whose limits read device, dtype, shape, strides and the 16-byte alignment of
-    data_ptr (a fresh allocation is aligned) — so the kernel is chosen before the copy is made, and the copy is only made for a kernel."""
-
-    def __init__(self, weight):
-        self.is_cuda, self.dtype, self.device, self.requires_grad = weight.is_cuda, weight.dtype, weight.device, False
-        self.shape = torch.Size((weight.shape[1], weight.shape[0]))
-
-    def stride(self, i=None):
-        st = (self.shape[1], 1)
-        return st if i is None else st[i]
-
-    def dim(self):
-        return 2
-
-    def data_ptr(self):
-        return 0
-
-    def is_contiguous(self):
-        return True
+def _ContiguousLike(weight):
+    """Stand-in for `weight.t().contiguous()` in linear.plan, which reads device, dtype, shape, strides and the address's alignment (a fresh allocation is
+    aligned: a placeholder address) — so the kernel is chosen before the copy is made, and the copy is only made for a kernel."""
+    return _lib.Desc.fresh(weight, (weight.shape[1], weight.shape[0]), 2)
 
 
 def _slabs(m, n, k):
