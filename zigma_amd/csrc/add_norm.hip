@@ -6,79 +6,9 @@
 // (model_zigma.py:53-54,441-458): the gate*branch residual of the previous sub-layer on the way in,
 // the adaLN modulate on the way out.  Pure HBM streaming: one wave owns one row, the row lives in
 // registers between the statistics and the normalisation, so every operand is read or written once.
-#include "zigma_common.h"
+#include "vec_io.h"
 
 namespace zigma {
-
-// sum over the LPR lanes that share a row (LPR = 64: the whole wave)
-template <int LPR> __device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int s = LPR / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
-template <typename T> struct V4;  // 4 consecutive elements
-template <> struct V4<F32> { using type = uint4; };
-template <> struct V4<F16> { using type = uint2; };
-template <> struct V4<BF16> { using type = uint2; };
-
-template <typename T> __device__ __forceinline__ void load4(const void *base, int64_t idx, float (&f)[4]) {
-    if constexpr (T::id == ZIGMA_F32) {
-        const uint4 r = *reinterpret_cast<const uint4 *>(reinterpret_cast<const float *>(base) + idx);
-        f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y); f[2] = __uint_as_float(r.z); f[3] = __uint_as_float(r.w);
-    } else {
-        const uint2 r = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(base) + idx);
-        f[0] = to_float<T>(r.x & 0xffffu); f[1] = to_float<T>(r.x >> 16);
-        f[2] = to_float<T>(r.y & 0xffffu); f[3] = to_float<T>(r.y >> 16);
-    }
-}
-template <typename T> __device__ __forceinline__ void store4(void *base, int64_t idx, const float (&f)[4]) {
-    if constexpr (T::id == ZIGMA_F32) {
-        *reinterpret_cast<uint4 *>(reinterpret_cast<float *>(base) + idx) =
-            make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-    } else {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(base) + idx) =
-            make_uint2(from_float<T>(f[0]) | (uint32_t(from_float<T>(f[1])) << 16),
-                       from_float<T>(f[2]) | (uint32_t(from_float<T>(f[3])) << 16));
-    }
-}
-// VEC consecutive elements: 1 (scalar), 4, or 8 (two float4 / one 16-byte piece of 16-bit elements)
-template <typename T, int VEC> __device__ __forceinline__ void loadv(const void *base, int64_t idx, float (&f)[VEC]) {
-    if constexpr (VEC == 1) {
-        f[0] = ld<T>(base, idx);
-    } else if constexpr (VEC == 4) {
-        load4<T>(base, idx, f);
-    } else if constexpr (T::id == ZIGMA_F32) {
-        float a[4], b[4];
-        load4<T>(base, idx, a);
-        load4<T>(base, idx + 4, b);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { f[i] = a[i]; f[4 + i] = b[i]; }
-    } else {
-        const uint4 r = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint16_t *>(base) + idx);
-        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { f[2 * i] = to_float<T>(w[i] & 0xffffu); f[2 * i + 1] = to_float<T>(w[i] >> 16); }
-    }
-}
-template <typename T, int VEC> __device__ __forceinline__ void storev(void *base, int64_t idx, const float (&f)[VEC]) {
-    if constexpr (VEC == 1) {
-        st<T>(base, idx, f[0]);
-    } else if constexpr (VEC == 4) {
-        store4<T>(base, idx, f);
-    } else if constexpr (T::id == ZIGMA_F32) {
-        const float a[4] = {f[0], f[1], f[2], f[3]}, b[4] = {f[4], f[5], f[6], f[7]};
-        store4<T>(base, idx, a);
-        store4<T>(base, idx + 4, b);
-    } else {
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = from_float<T>(f[2 * i]) | (uint32_t(from_float<T>(f[2 * i + 1])) << 16);
-        *reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(base) + idx) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-}
-// value the tensor would hold after being stored in dtype T (the reference materialises these tensors)
-template <typename T> __device__ __forceinline__ float rnd(float v) { return to_float<T>(from_float<T>(v)); }
 
 // VEC = 8 / 4 (vector paths) or 1 (scalar path, any alignment); a row is shared by LPR lanes (64 / LPR rows per wave) that walk it in
 // ITERS chunks of LPR * VEC columns.  LPR = 16 is for rows of a few hundred 16-bit elements (E = 640: 5 x 16 bytes per lane, every

@@ -9,7 +9,7 @@
 //      in registers; the zigzag gather (x_row_index) picks whole rows, so it costs nothing.
 //  conv_generic_kernel — any strides (channel-first views of the reference, channel-last, ...): one
 //      output element per thread, threads run along the contiguous dimension.
-#include "conv_helpers.h"
+#include "buffer_io.h"
 #include "front_plan.h"
 
 namespace zigma {

@@ -10,7 +10,7 @@
 // its partial dw / db in registers; one partial per (sample, segment) goes to the workspace and a finishing kernel
 // adds them in a fixed order (the reference uses float atomics: not reproducible).
 // dx is scattered through the same row table the forward gathered with (a permutation): dx[row[k]] = dx'[k].
-#include "conv_helpers.h"
+#include "buffer_io.h"
 
 namespace zigma {
 

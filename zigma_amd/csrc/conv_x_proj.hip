@@ -24,15 +24,11 @@
 // (tools/conv_xproj_ab.py); loads + MFMA alone 35 us, + conv 64 us, + stores 64 us (probe flags).
 // bf16 or fp16 (template parameter T: the dot products of the conv, the packs, the MFMA); width 4; bias required; seqlen % 32 == 0; d_inner % 64 == 0; n <= 96, n % 8 == 0.
 #include "front_plan.h"
-#include "zigma_common.h"
+#include "lds_pipe.h"
 
 namespace zigma {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
 
 constexpr int kCxHalo = 3;                                         // kCxTok, kCxBK: front_plan.h
 constexpr int kCxXBytes = 40 * 128;                                  // per wave and stage: 35 rows used, 5 load instructions
@@ -50,18 +46,14 @@ template <> __device__ __forceinline__ float dot2<BF16>(unsigned a, unsigned b, 
 template <> __device__ __forceinline__ float dot2<F16>(unsigned a, unsigned b, float c) {
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), c, false);
 }
-// LDS reads are inline assembly on purpose: hipcc makes a ds_read it can see wait for EVERY direct-to-LDS load in flight
-// (s_waitcnt vmcnt(0)), the younger stages included, which would serialise the pipeline.  Landing is tracked by hand (counted
-// s_waitcnt vmcnt + s_barrier at the top of a stage); the reads of one k-step are issued as a group and settled by an explicit
-// s_waitcnt lgkmcnt that names the destination registers (so that no use can be scheduled above it).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// LDS accesses are hand-issued (csrc/lds_pipe.h); the reads of one k-step are issued as a group and settled by an explicit
+// s_waitcnt lgkmcnt that names the destination registers
 struct KStep {
     u32x4 X[4];      // input rows k-3 .. k, this lane's 8 channels
     u32x4 Wc[4];     // conv taps: [r] = channels 2r, 2r+1 as (tap0 tap1)(tap2 tap3) pairs
     u32x4 Bc;        // conv bias of the 8 channels
     u32x4 Bf[3];     // W_x fragments (rows nb * 32 + j)
 };
-__device__ __forceinline__ void lds_rd(u32x4 &d, unsigned addr) { asm volatile("ds_read_b128 %0, %1" : "=v"(d) : "v"(addr)); }
 template <int N>
 __device__ __forceinline__ void settle(KStep &k) {
     static_assert(N == 0 || N == 12, "");
@@ -76,12 +68,12 @@ __device__ __forceinline__ void settle(KStep &k) {
 // s_waitcnt vmcnt(n), n a run-time (wave-uniform) value: the instruction takes an immediate
 __device__ __forceinline__ void wait_vm_n(int n) {
     switch (n) {
-#define ZIGMA_VM_CASE(N_) case N_: asm volatile("s_waitcnt vmcnt(" #N_ ")" ::: "memory"); break;
+#define ZIGMA_VM_CASE(N_) case N_: wait_vm<N_>(); break;
         ZIGMA_VM_CASE(1) ZIGMA_VM_CASE(2) ZIGMA_VM_CASE(3) ZIGMA_VM_CASE(4) ZIGMA_VM_CASE(5) ZIGMA_VM_CASE(6) ZIGMA_VM_CASE(7)
         ZIGMA_VM_CASE(8) ZIGMA_VM_CASE(9) ZIGMA_VM_CASE(10) ZIGMA_VM_CASE(11) ZIGMA_VM_CASE(12) ZIGMA_VM_CASE(13) ZIGMA_VM_CASE(14)
         ZIGMA_VM_CASE(15) ZIGMA_VM_CASE(16)
 #undef ZIGMA_VM_CASE
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        default: wait_vm<0>(); break;
     }
 }
 
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
             int pos = t0 - kCxHalo + rr;
             pos = pos < 0 ? 0 : pos;                                   // left padding: fetched from a valid row, zeroed when read
             const int row = p.x_row_index ? p.x_row_index[pos] : pos;
-            xsrc[i] = xb + static_cast<int64_t>(row) * p.x_l_stride * 2 + (((lane & 7) ^ ((rr >> 1) & 7)) << 4);
+            xsrc[i] = xb + static_cast<int64_t>(row) * p.x_l_stride * 2 + (((lane & 7) ^ swz_slot(rr)) << 4);
         }
     }
     // W_x slab: 8 rows per load instruction, instruction q = wave + NW i (wave-uniform: skipped when its rows are all beyond n)
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
     for (int i = 0; i < NWI; ++i) {
         int row = (wave + NW * i) * 8 + (lane >> 3);
         row = row < p.n ? row : p.n - 1;
-        wsrc[i] = reinterpret_cast<const unsigned char *>(p.w) + static_cast<int64_t>(row) * p.w_row_stride * 2 + (((lane & 7) ^ ((row >> 1) & 7)) << 4);
+        wsrc[i] = reinterpret_cast<const unsigned char *>(p.w) + static_cast<int64_t>(row) * p.w_row_stride * 2 + (((lane & 7) ^ swz_slot(row)) << 4);
         n_w += (wave + NW * i) * 8 < p.n ? 1 : 0;
     }
     // conv taps / bias slab (wave 1): lanes 0..31 taps of 2 channels each, lanes 32..39 bias of 8 channels each
@@ -143,20 +135,20 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
 
     const int nld = 5 + n_w + (wave == 1 ? 1 : 0);                      // load instructions this wave issues per stage
 
-    f32x16 acc[3];
+    mfma_f32x16 acc[3];
 #pragma unroll
-    for (int nb = 0; nb < 3; ++nb) acc[nb] = f32x16{};
+    for (int nb = 0; nb < 3; ++nb) acc[nb] = mfma_f32x16{};
 
     // u stores: lane -> (row lane >> 3 of every group of 8, 16-byte piece lane & 7) of the transposed tile
     const int64_t u_pitch = p.u_l_stride * 2;
     unsigned char *ust = reinterpret_cast<unsigned char *>(p.u) + static_cast<int64_t>(b) * p.u_batch_stride * 2 + (t0 + (lane >> 3)) * u_pitch + (lane & 7) * 16;
-    const unsigned u_wr = wave * kCxXBytes + j * 128 + ((kh ^ ((j >> 1) & 7)) << 4);                     // row j, slot ((ks << 1) | kh) ^ swizzle
-    // read back rows i * 8 + (lane >> 3), piece lane & 7: (row >> 1) & 7 == (lane >> 4) ^ ((i & 1) << 2), the i part is applied at the read
+    const unsigned u_wr = wave * kCxXBytes + j * 128 + ((kh ^ swz_slot(j)) << 4);                     // row j, slot ((ks << 1) | kh) ^ swizzle
+    // read back rows i * 8 + (lane >> 3), piece lane & 7: swz_slot(row) == (lane >> 4) ^ ((i & 1) << 2), the i part is applied at the read
     const unsigned u_rd = wave * kCxXBytes + (lane >> 3) * 128 + (((lane & 7) ^ (lane >> 4)) << 4);
     unsigned x_off[4];                                                 // this wave's rows j .. j+3, piece kh, swizzled
 #pragma unroll
-    for (int s = 0; s < 4; ++s) x_off[s] = wave * kCxXBytes + (j + s) * 128 + ((kh ^ (((j + s) >> 1) & 7)) << 4);
-    const unsigned w_off = kCxWOff + j * 128 + ((kh ^ ((j >> 1) & 7)) << 4);      // rows nb * 32 + j: (row >> 1) & 7 == (j >> 1) & 7
+    for (int s = 0; s < 4; ++s) x_off[s] = wave * kCxXBytes + (j + s) * 128 + ((kh ^ swz_slot(j + s)) << 4);
+    const unsigned w_off = kCxWOff + swz(j, kh);      // rows nb * 32 + j: swz_slot(row) == swz_slot(j)
     const bool first_tile = t0 == 0;                                   // wave-uniform: the causal window starts inside this tile
 
 #pragma unroll
@@ -254,9 +246,8 @@ __global__ __launch_bounds__(64 * NW) void conv_x_proj_kernel(const zigma_conv_x
     for (int nb = 0; nb < 3; ++nb)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             const u32x2 pk = {pack2_pk<T>(acc[nb][q * 4], acc[nb][q * 4 + 1]), pack2_pk<T>(acc[nb][q * 4 + 2], acc[nb][q * 4 + 3])};
-            asm volatile("ds_write_b64 %0, %1" ::"v"(tile + j * kPitch + nb * 64 + q * 16 + kh * 8), "v"(pk) : "memory");
+            lds_wr8(tile + j * kPitch + nb * 64 + q * 16 + kh * 8, pk);
         }
     {
         const int pc = lane & 15, r4 = lane >> 4;                     // 4 rows x 16 pieces per instruction

@@ -17,15 +17,12 @@
 
 namespace zigma {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kXaD = 64;                 // head dim
 constexpr int kXaWaves = 4, kXaTok = 16; // tokens per wave (MFMA M)
 constexpr int kXaKPitch = (kXaD + 8) * 2;   // bytes per K row in LDS (16 B skew)
 
 // 16-token tiles per wave = how many query tokens share one staging of K_h / V_h^T (20 KB): 8 (512 tokens per workgroup) where the
 // sequence has them — 35.5 us against 38.0 with 4 and 40.2 with 16 at the headline shape (tools/attn_probe.py) —, 4 for short ones
-
 
 // NKB 16-key blocks: n_ctx <= 16 * NKB; MASK_ALL = false: n_ctx > 16 (NKB - 1), padded keys only in the last block
 template <int NKB, bool MASK_ALL, typename T>
@@ -92,13 +89,13 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
         const frag8_t<T> qa[2] = {qn[0], qn[1]};
         if (it + 1 < kXaTiles && t0 + kXaWaves * kXaTok < L) load_q(t0 + kXaWaves * kXaTok, qn);
         // ---- S^T = K Q^T : lane -> token column i16, key rows 16 nb + 4 g + r -----------------------------------------
-        f32x4 s[NKB];
+        mfma_f32x4 s[NKB];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {                 // (k-step outermost: consecutive MFMAs on different accumulators; the first on a literal zero)
 #pragma unroll
             for (int nb = 0; nb < NKB; ++nb) {
                 const frag8_t<T> kf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXaKPitch + ks * 64 + g * 16));
-                s[nb] = ks == 0 ? mfma_16x16x32<T>(kf, qa[ks], f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(kf, qa[ks], s[nb]);
+                s[nb] = ks == 0 ? mfma_16x16x32<T>(kf, qa[ks], mfma_f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(kf, qa[ks], s[nb]);
             }
         }
         // ---- softmax over the keys of this lane's token: 4 NKB values in the lane, the rest in lanes i16 + 16 g' ----------
@@ -130,14 +127,14 @@ __global__ __launch_bounds__(64 * kXaWaves) void cross_attn_kernel(const zigma_x
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // ---- O^T = V^T P^T : lane -> token column i16, dims 16 db + 4 g + r ---------------------------------------------------
-        f32x4 o[4];
+        mfma_f32x4 o[4];
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const frag8_t<T> pf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(pt + i16 * VPitch + ks * 64 + g * 16));
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 const frag8_t<T> vf = __builtin_bit_cast(frag8_t<T>, *reinterpret_cast<const uint4 *>(s_vt + (db * 16 + i16) * VPitch + ks * 64 + g * 16));
-                o[db] = ks == 0 ? mfma_16x16x32<T>(vf, pf, f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(vf, pf, o[db]);
+                o[db] = ks == 0 ? mfma_16x16x32<T>(vf, pf, mfma_f32x4{0.f, 0.f, 0.f, 0.f}) : mfma_16x16x32<T>(vf, pf, o[db]);
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -21,21 +21,16 @@
 
 namespace zigma {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kXbD = 64, kXbWaves = 4, kXbTok = 16;
 constexpr int kXbRowPitch = (kXbD + 8) * 2;      // bytes per K / V row and per dQ-tile row in LDS (16 B skew)
 constexpr int kXbRedPitch = (kXbD + 4) * 4;      // bytes per key row of the fp32 dK / dV reduction tiles
 
-__device__ __forceinline__ uint32_t xb_pack(float lo, float hi) {
-    return static_cast<uint32_t>(from_float<BF16>(lo)) | (static_cast<uint32_t>(from_float<BF16>(hi)) << 16);
+__device__ __forceinline__ s16x4 xb_pack4(const mfma_f32x4 v) {
+    return __builtin_bit_cast(s16x4, make_uint2(pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])));
 }
-__device__ __forceinline__ s16x4 xb_pack4(const f32x4 v) {
-    return __builtin_bit_cast(s16x4, make_uint2(xb_pack(v[0], v[1]), xb_pack(v[2], v[3])));
-}
-__device__ __forceinline__ f32x4 mfma16(s16x4 a, s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ mfma_f32x4 mfma16(s16x4 a, s16x4 b, mfma_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
 
 constexpr int xb_max(int a, int b) { return a > b ? a : b; }
 
@@ -94,11 +89,11 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
 #pragma unroll
     for (int e = 0; e < 4; ++e) ident[e] = (4 * g + e == i16) ? static_cast<short>(0x3f80) : static_cast<short>(0);
 
-    f32x4 dvt[4][NKB], dkt[4][NKB];      // [feature block (ks, half)][key block]: lane -> key 16 nb + i16, features 32 ks + 8 g + 4 half + r
+    mfma_f32x4 dvt[4][NKB], dkt[4][NKB];      // [feature block (ks, half)][key block]: lane -> key 16 nb + i16, features 32 ks + 8 g + 4 half + r
 #pragma unroll
     for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
-        for (int nb = 0; nb < NKB; ++nb) dvt[blk][nb] = dkt[blk][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nb = 0; nb < NKB; ++nb) dvt[blk][nb] = dkt[blk][nb] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int tile0 = blockIdx.x * tiles * kXbWaves + wave;          // this wave's tiles: tile0, tile0 + 4, ...
     auto load_rows = [&](const uint16_t *base, int64_t row_stride, int t0, uint4 (&xa)[2]) {
@@ -115,25 +110,25 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
         if (t0 >= L) break;                                          // wave-uniform; no workgroup barriers inside the loop
         if (!PF) { load_rows(qb, p.q_row_stride, t0, qn); load_rows(gb, p.do_row_stride, t0, dn); }
         const bool tail = t0 + i16 >= L;                             // dO = 0 for tokens past the end: no contribution to dK / dV
-        const bf16x8 qa[2] = {__builtin_bit_cast(bf16x8, qn[0]), __builtin_bit_cast(bf16x8, qn[1])};
-        const bf16x8 da[2] = {__builtin_bit_cast(bf16x8, tail ? make_uint4(0, 0, 0, 0) : dn[0]),
-                              __builtin_bit_cast(bf16x8, tail ? make_uint4(0, 0, 0, 0) : dn[1])};
+        const mfma_bf16x8 qa[2] = {__builtin_bit_cast(mfma_bf16x8, qn[0]), __builtin_bit_cast(mfma_bf16x8, qn[1])};
+        const mfma_bf16x8 da[2] = {__builtin_bit_cast(mfma_bf16x8, tail ? make_uint4(0, 0, 0, 0) : dn[0]),
+                              __builtin_bit_cast(mfma_bf16x8, tail ? make_uint4(0, 0, 0, 0) : dn[1])};
         if (PF && it + 1 < tiles && t0 + kXbWaves * kXbTok < L) {
             load_rows(qb, p.q_row_stride, t0 + kXbWaves * kXbTok, qn);
             load_rows(gb, p.do_row_stride, t0 + kXbWaves * kXbTok, dn);
         }
         // ======== token in the lane: S^T, dP^T -> statistics, dS^T, dQ^T ========
         float m = -INFINITY, inv, delta = 0.f;
-        f32x4 dq[4];
+        mfma_f32x4 dq[4];
         {
-            f32x4 s[NKB], dpt[NKB];
+            mfma_f32x4 s[NKB], dpt[NKB];
 #pragma unroll
             for (int nb = 0; nb < NKB; ++nb) {
-                s[nb] = dpt[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+                s[nb] = dpt[nb] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    const bf16x8 kf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
-                    const bf16x8 vf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_v + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
+                    const mfma_bf16x8 kf = __builtin_bit_cast(mfma_bf16x8, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
+                    const mfma_bf16x8 vf = __builtin_bit_cast(mfma_bf16x8, *reinterpret_cast<const uint4 *>(s_v + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
                     s[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qa[ks], s[nb], 0, 0, 0);
                     dpt[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, da[ks], dpt[nb], 0, 0, 0);
                 }
@@ -164,10 +159,10 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
             delta += __shfl_xor(delta, 32, 64);
             // dQ^T = K^T dS^T : lane -> token column i16, features 16 db + 4 g + r
 #pragma unroll
-            for (int db = 0; db < 4; ++db) dq[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int db = 0; db < 4; ++db) dq[db] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int nb = 0; nb < NKB; ++nb) {
-                f32x4 ds;
+                mfma_f32x4 ds;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ds[r] = s[nb][r] * (dpt[nb][r] - delta);      // dS / scale
                 const s16x4 dsb = xb_pack4(ds);
@@ -181,7 +176,7 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
 #pragma unroll
         for (int db = 0; db < 4; ++db)
             *reinterpret_cast<uint2 *>(tile + i16 * kXbRowPitch + (db * 16 + 4 * g) * 2) =
-                make_uint2(xb_pack(dq[db][0] * scale, dq[db][1] * scale), xb_pack(dq[db][2] * scale, dq[db][3] * scale));
+                make_uint2(pack2<BF16>(dq[db][0] * scale, dq[db][1] * scale), pack2<BF16>(dq[db][2] * scale, dq[db][3] * scale));
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -212,21 +207,21 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
                 const uint4 qw = __builtin_bit_cast(uint4, qa[ks]), dw = __builtin_bit_cast(uint4, da[ks]);
                 const s16x4 qp = __builtin_bit_cast(s16x4, hf ? make_uint2(qw.z, qw.w) : make_uint2(qw.x, qw.y));
                 const s16x4 dp = __builtin_bit_cast(s16x4, hf ? make_uint2(dw.z, dw.w) : make_uint2(dw.x, dw.y));
-                qT[ks * 2 + hf] = xb_pack4(mfma16(qp, ident, f32x4{0.f, 0.f, 0.f, 0.f}));
-                dT[ks * 2 + hf] = xb_pack4(mfma16(dp, ident, f32x4{0.f, 0.f, 0.f, 0.f}));
+                qT[ks * 2 + hf] = xb_pack4(mfma16(qp, ident, mfma_f32x4{0.f, 0.f, 0.f, 0.f}));
+                dT[ks * 2 + hf] = xb_pack4(mfma16(dp, ident, mfma_f32x4{0.f, 0.f, 0.f, 0.f}));
             }
 #pragma unroll
         for (int nb = 0; nb < NKB; ++nb) {
-            f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f}, dp = s;
+            mfma_f32x4 s = mfma_f32x4{0.f, 0.f, 0.f, 0.f}, dp = s;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const bf16x8 kf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
-                const bf16x8 vf = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(s_v + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
+                const mfma_bf16x8 kf = __builtin_bit_cast(mfma_bf16x8, *reinterpret_cast<const uint4 *>(s_k + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
+                const mfma_bf16x8 vf = __builtin_bit_cast(mfma_bf16x8, *reinterpret_cast<const uint4 *>(s_v + (nb * 16 + i16) * kXbRowPitch + ks * 64 + g * 16));
                 s = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[ks], kf, s, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[ks], vf, dp, 0, 0, 0);
             }
             const bool live = nb * 16 + i16 < NC;
-            f32x4 pr, ds;
+            mfma_f32x4 pr, ds;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 pr[r] = live ? fast_exp2(s[r] * sc2 - mB[r]) * invB[r] : 0.f;
@@ -252,13 +247,13 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
 #pragma unroll
                 for (int nb = 0; nb < NKB; ++nb) {
                     const int off = (nb * 16 + i16) * (kXbRedPitch / 4) + 32 * (blk >> 1) + 8 * g + 4 * (blk & 1);
-                    f32x4 ak = dkt[blk][nb] * scale, av = dvt[blk][nb];
+                    mfma_f32x4 ak = dkt[blk][nb] * scale, av = dvt[blk][nb];
                     if (w > 0) {
-                        ak += *reinterpret_cast<const f32x4 *>(red_k + off);
-                        av += *reinterpret_cast<const f32x4 *>(red_v + off);
+                        ak += *reinterpret_cast<const mfma_f32x4 *>(red_k + off);
+                        av += *reinterpret_cast<const mfma_f32x4 *>(red_v + off);
                     }
-                    *reinterpret_cast<f32x4 *>(red_k + off) = ak;
-                    *reinterpret_cast<f32x4 *>(red_v + off) = av;
+                    *reinterpret_cast<mfma_f32x4 *>(red_k + off) = ak;
+                    *reinterpret_cast<mfma_f32x4 *>(red_v + off) = av;
                 }
         }
         __syncthreads();
@@ -268,8 +263,8 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
     float *dkp = reinterpret_cast<float *>(p.dk_part) + part, *dvp = reinterpret_cast<float *>(p.dv_part) + part;
     for (int piece = tid; piece < NC * 16; piece += 64 * kXbWaves) {
         const int key = piece >> 4, pc = piece & 15;
-        *reinterpret_cast<f32x4 *>(dkp + key * C + pc * 4) = *reinterpret_cast<const f32x4 *>(red_k + key * (kXbRedPitch / 4) + pc * 4);
-        *reinterpret_cast<f32x4 *>(dvp + key * C + pc * 4) = *reinterpret_cast<const f32x4 *>(red_v + key * (kXbRedPitch / 4) + pc * 4);
+        *reinterpret_cast<mfma_f32x4 *>(dkp + key * C + pc * 4) = *reinterpret_cast<const mfma_f32x4 *>(red_k + key * (kXbRedPitch / 4) + pc * 4);
+        *reinterpret_cast<mfma_f32x4 *>(dvp + key * C + pc * 4) = *reinterpret_cast<const mfma_f32x4 *>(red_v + key * (kXbRedPitch / 4) + pc * 4);
     }
 }
 

@@ -19,8 +19,6 @@
 
 namespace zigma {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 template <typename T>
 __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(const zigma_dtproj_params_t p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_tile[kDtWaves * kDtTokPerWave * 144];
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(64 * kDtWaves, 5) void dt_proj_softplus_kernel(cons
         const int64_t m0 = m_blk + (static_cast<int64_t>(it) * kDtWaves + wave) * kDtTokPerWave;
         if (m0 >= p.m) break;
         if (it + 1 < kDtIters) a_frags(it + 1, a_nxt);
-        f32x16 ce = {}, co = {};
+        mfma_f32x16 ce = {}, co = {};
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
             // (the builtins spelled out: through the mfma_32x32x16<T> wrapper hipcc allocates this loop's registers differently)

@@ -136,12 +136,6 @@ __global__ void timestep_embed_kernel(const zigma_timestep_embed_params_t p) {
 // a wave read the same pieces (broadcast)
 constexpr int kFlMaxPass = 16;      // E <= 16 lanes * 8 * 16
 
-__device__ __forceinline__ float fl_sum16(float v) {
-#pragma unroll
-    for (int m = 8; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // one row on its 16 lanes: statistics, the bf16-rounded LayerNorm output, the n_out dot products -> lane o of the 16 holds sum_e w[o, e] y[e] (fp32, no bias).
 // Shared by final_layer_kernel and final_layer_cfg_kernel: the same operations in the same order, so both give the same bits per row.
 // YOUT: also store the bf16 LayerNorm row to yrow (the guided kernel's test hook).
@@ -158,7 +152,7 @@ __device__ __forceinline__ float final_layer_row(const uint16_t *xr, const uint1
 #pragma unroll
         for (int i = 0; i < 8; ++i) { v[q][i] = to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))); s += v[q][i]; }
     }
-    const float mean = fl_sum16(s) * inv_e;
+    const float mean = wave_sum<16>(s) * inv_e;
     float s2 = 0.f;
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -166,7 +160,7 @@ __device__ __forceinline__ float final_layer_row(const uint16_t *xr, const uint1
 #pragma unroll
         for (int i = 0; i < 8; ++i) { const float d = e0 < E ? v[q][i] - mean : 0.f; v[q][i] = d; s2 += d * d; }
     }
-    const float rstd = rsqrtf(fl_sum16(s2) * inv_e + eps);
+    const float rstd = rsqrtf(wave_sum<16>(s2) * inv_e + eps);
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
         uint16_t yb[8];
@@ -192,7 +186,7 @@ __device__ __forceinline__ float final_layer_row(const uint16_t *xr, const uint1
                 for (int i = 0; i < 8; ++i) acc = __builtin_fmaf(to_float<BF16>(static_cast<uint16_t>(ww[i >> 1] >> ((i & 1) * 16))), v[q][i], acc);
             }
         }
-        acc = fl_sum16(acc);
+        acc = wave_sum<16>(acc);
         if (l16 == o) res = acc;
     }
     return res;

@@ -18,21 +18,16 @@
 //     the current tile stores.
 //   * operands reach LDS by direct-to-LDS loads (global_load_lds_dwordx4, 1 KB per wave instruction, no VGPR round trip,
 //     no ds_write), two stages of (BN + 256) rows x 128 B; ONE barrier per k-step.  The LDS image is lane-linear, so the
-//     bank swizzle (16-byte slot ^= (row >> 1) & 7: conflict-free ds_read_b128 for 32 consecutive rows) is applied to the
-//     per-lane SOURCE address and again on the fragment reads (cdna_hip_programming.md T2 / rule 21).
+//     bank swizzle (swz_slot, csrc/lds_pipe.h) is applied to the per-lane SOURCE address and again on the fragment reads.
 //   * tile order is XCD-aware: the 32 workgroups of an XCD (blockIdx % 8) work at any time on ~32 consecutive tiles of the
 //     (m-tile, n-tile) raster, i.e. a few 256-token activation panels x all weight panels: both stay in that XCD's 4 MB L2.
 //   * epilogue in registers: + bias, SiLU on output columns >= silu_from_col (in_proj emits silu(z) for the gate half:
 //     the scan then multiplies instead of evaluating exp + rcp per element, ZIGMA_SCAN_Z_PREACTIVATED), bf16 pack.
-#include "scan_helpers.h"
+#include "buffer_io.h"
+#include "lds_pipe.h"
 #include "linear_plan.h"
 
 namespace zigma {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
 
 constexpr int kLinBM = 256, kLinBK = 64;
 
@@ -41,24 +36,23 @@ constexpr int kLinBM = 256, kLinBK = 64;
 // 32 different output rows, and storing them as they lie costs one memory request per row per instruction (measured: the
 // scattered form made the stores the longest phase of the kernel).  So the wave transposes its tile through a private 4 KB
 // of LDS, 32 tokens x 64 features at a time: + bias (fp32, before the single rounding), SiLU on whole 32-feature blocks,
-// packed 8-byte writes (16-byte slot ^= (token >> 1) & 7: conflict-free), 16-byte reads; every global store instruction then
+// packed 8-byte writes (16-byte slot ^= swz_slot(token): conflict-free), 16-byte reads; every global store instruction then
 // covers 8 tokens x 128 contiguous bytes.  `s_bias`: the bias vector staged in LDS as bf16 (or nullptr).
 // RES: out = residual + gate * bf16(value) (CrossAttention's `hidden + gate_msa * to_out(...)`, reference model_zigma.py:447-449; the
 // projection result is rounded to bf16 first, as the reference's bf16 tensor is): the residual rows are fetched with the store
 // pattern (16 bytes per lane, 8 tokens x 128 B per instruction), `gate8` = this lane's 8 gate values (bf16).
 template <int MB, int NB, bool RES = false, typename T = BF16>
-__device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], unsigned char *scr, const uint16_t *s_bias,
+__device__ __forceinline__ void linear_epilogue(const mfma_f32x16 (&acc)[NB][MB], unsigned char *scr, const uint16_t *s_bias,
                                                 const rsrc_t o_rs, const int64_t o_pitch, const int n_wave0, const int silu_from_col,
                                                 const int lane, const rsrc_t r_rs, const int64_t r_pitch, const uint4 gate8) {
     const int j = lane & 31, kh = lane >> 5;
-    const int wr_off = j * 128 + kh * 8, wr_sw = (j >> 1) & 7;                               // this lane's row in the scratch tile
-    const int rd_tok = lane >> 3, rd_slot = (lane & 7) ^ (rd_tok >> 1);                      // row = i * 8 + rd_tok: swizzle (row >> 1) & 7
+    const int wr_off = j * 128 + kh * 8, wr_sw = swz_slot(j);                               // this lane's row in the scratch tile
+    const int rd_tok = lane >> 3, rd_slot = (lane & 7) ^ (rd_tok >> 1);                      // row = i * 8 + rd_tok: swizzle swz_slot(row)
     const unsigned st_off = static_cast<unsigned>(rd_tok * o_pitch + (lane & 7) * 16);
     const unsigned scr_lds = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)(scr)));      // LDS byte address
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        u4 res[4];
+        u32x4 res[4];
         if constexpr (RES) {                          // requested first: the latency runs under the conversion / transposition below
             const unsigned rs_off = static_cast<unsigned>(rd_tok * r_pitch + (lane & 7) * 16);
 #pragma unroll
@@ -71,10 +65,9 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
 #pragma unroll
             for (int r = 0; r < 16; ++r) v[r] = acc[nb][mb][r];
             if (s_bias) {
-                // (inline asm like the writes below: a visible ds_read would make hipcc drain the load ring first)
-                typedef unsigned u2 __attribute__((ext_vector_type(2)));
+                // (hand-issued, csrc/lds_pipe.h: a visible ds_read would make hipcc drain the load ring first)
                 const unsigned b_lds = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)(const_cast<uint16_t *>(s_bias))));
-                u2 bq[4];
+                u32x2 bq[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) asm volatile("ds_read_b64 %0, %1" : "=v"(bq[q]) : "v"(b_lds + (n0 + 4 * kh + q * 8) * 2));
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]));
@@ -95,19 +88,17 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
                 uint2 pk;
                 pk.x = pack2<T>(v[q * 4], v[q * 4 + 1]);
                 pk.y = pack2<T>(v[q * 4 + 2], v[q * 4 + 3]);
-                // (inline asm: a ds_write the compiler can see makes it drain vmcnt — i.e. the whole load ring — first,
-                // because an LDS-DMA in flight might target the same bytes; it cannot: the scratch is outside the ring)
-                typedef unsigned u2 __attribute__((ext_vector_type(2)));
-                const u2 pkv = {pk.x, pk.y};
-                asm volatile("ds_write_b64 %0, %1" ::"v"(scr_lds + wr_off + (((nb * 4 + q) ^ wr_sw) << 4)), "v"(pkv) : "memory");
+                // (hand-issued: the scratch is outside the load ring, which a ds_write the compiler can see would drain all the same)
+                const u32x2 pkv = {pk.x, pk.y};                                                 // (a named value: as a temporary it changes the register allocation)
+                lds_wr8(scr_lds + wr_off + (((nb * 4 + q) ^ wr_sw) << 4), pkv);
             }
         }
         // wave-private scratch: writes and reads of one wave execute in order in the LDS queue; the reads' data is waited for
-        // explicitly (inline asm again: no drain of the load ring in front of them)
-        u4 row[4];
+        // explicitly
+        u32x4 row[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            asm volatile("ds_read_b128 %0, %1" : "=v"(row[i]) : "v"(scr_lds + i * 1024 + rd_tok * 128 + ((rd_slot ^ ((i & 1) << 2)) << 4)));
+            lds_rd(row[i], scr_lds + i * 1024 + rd_tok * 128 + ((rd_slot ^ ((i & 1) << 2)) << 4));
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(row[0]), "+v"(row[1]), "+v"(row[2]), "+v"(row[3]));
         if constexpr (RES) {
             const unsigned gq[4] = {gate8.x, gate8.y, gate8.z, gate8.w};
@@ -131,14 +122,14 @@ __device__ __forceinline__ void linear_epilogue(const f32x16 (&acc)[NB][MB], uns
 }
 
 // s_waitcnt vmcnt(n) for the handful of counts the pipeline uses (the instruction takes an immediate)
-__device__ __forceinline__ void wait_vm(int n) {
+__device__ __forceinline__ void wait_vm_n(int n) {
     switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+        case 0: wait_vm<0>(); break;
+        case 6: wait_vm<6>(); break;
+        case 8: wait_vm<8>(); break;
+        case 14: wait_vm<14>(); break;
+        case 16: wait_vm<16>(); break;
+        default: wait_vm<0>(); break;
     }
 }
 
@@ -186,10 +177,10 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
     // [0, BN) are W rows, [BN, BN + 256) token rows, so the operand of instruction i is known at compile time (i < BN / 64).
     // Per lane the source address is
     //   operand base (SGPR) + [tile row0 + i' * 64] * pitch + kt * 128                     (wave-uniform: scalar unit)
-    //   + (w * 8 + (lane >> 3)) * pitch + piece * 16,  piece = (lane & 7) ^ ((row >> 1) & 7)  (per lane, ONE value per operand)
+    //   + (w * 8 + (lane >> 3)) * pitch + piece * 16,  piece = (lane & 7) ^ swz_slot(row)  (per lane, ONE value per operand)
     // with row = w * 8 + (lane >> 3) (mod 16): the swizzle term does not depend on i.
     const int srow = wave * 8 + (lane >> 3);
-    const unsigned piece = ((lane & 7) ^ ((srow >> 1) & 7)) << 4;
+    const unsigned piece = ((lane & 7) ^ swz_slot(srow)) << 4;
     const unsigned lane_off_w = static_cast<unsigned>(srow * w_pitch) + piece, lane_off_x = static_cast<unsigned>(srow * x_pitch) + piece;
     int is_tile = tile0, is_kt = 0, is_g = 0;                      // issue cursor: next (tile, k-step) to fetch, stage is_g % NST
     auto issue = [&]() {
@@ -238,14 +229,14 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src), (lds_ptr_t)(ip_dst) + (i * 8 + wave) * 1024, 16, 0, 0);
     };
 
-    // fragment read offsets: row * 128 + (((ks << 1) | kh) ^ ((row >> 1) & 7)) * 16, row = base (multiple of 32) + j
-    const int sw = (j >> 1) & 7;
+    // fragment read offsets: row * 128 + (((ks << 1) | kh) ^ swz_slot(row)) * 16, row = base (multiple of 32) + j
+    const int sw = swz_slot(j);
     const int a_row0 = (wn * 64 + j) * 128, b_row0 = (BN + wm * (BM / WM_) + j) * 128;
 
     if (HAS_BIAS) {                                                // plain loads + LDS writes, retired before the pipeline starts counting
         for (int i = tid; i < p.n / 2; i += 512)
             reinterpret_cast<uint32_t *>(smem + NST * STAGE)[i] = reinterpret_cast<const uint32_t *>(p.bias)[i];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
     }
 #pragma unroll 1
     for (int g0 = 0; g0 < NST - 1 && g0 < g_total; ++g0) issue();
@@ -253,17 +244,17 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
     int g = 0, tile = tile0;
 #pragma unroll 1
     for (int ti = 0; ti < my_tiles; ++ti, tile += wg_per_xcd) {
-        f32x16 acc[NB][MB];
+        mfma_f32x16 acc[NB][MB];
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-            for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = f32x16{};
+            for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = mfma_f32x16{};
 #pragma unroll 1
         for (int kt = 0; kt < nk; ++kt, ++g) {
             // batch g has landed when only what was issued after it is still outstanding: the younger batches (NST - 2 of
             // them, fewer at the very end) and, right after an epilogue, its stores
             const int younger = (g_total - 1 - g) < (NST - 2) ? (g_total - 1 - g) : (NST - 2);
-            wait_vm(NLD * younger + ((ti > 0 && kt < NST - 1 && !(dbg & 0x400)) ? NSTORE : 0));
+            wait_vm_n(NLD * younger + ((ti > 0 && kt < NST - 1 && !(dbg & 0x400)) ? NSTORE : 0));
             __builtin_amdgcn_s_barrier();                       // ... for every wave; and every wave is done with stage (g - 1) % NST
             const bool do_issue = g + NST - 1 < g_total && !(dbg & 0x200);
             // SPREAD (the 256 x 128 tile: three stages, loads two k-steps ahead): the pieces of the batch go out between the MFMAs of
@@ -322,7 +313,7 @@ __global__ __launch_bounds__(512, 2) void linear_tn_kernel(const zigma_linear_pa
         // ---- epilogue: transposed through the stage the main loop has just finished with (the next issue into it happens
         // behind the next k-step's barrier) ---------------------------------------------------------------------------------
         if (!(dbg & 0x400)) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm<0>();
             __builtin_amdgcn_s_barrier();                                                     // every wave is done with the fragments of this stage
             const int mt = tile / tiles_n, nt = tile - mt * tiles_n;
             const int64_t m_tile = static_cast<int64_t>(mt) * BM + wm * (BM / WM_);           // first token of this wave's tile

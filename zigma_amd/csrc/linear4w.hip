@@ -15,14 +15,12 @@
 // computes the statement's operands.  Limits (zigma_linear_fwd falls back to linear_tn_kernel otherwise): m % 256 == 0,
 // n % 128 == 0, k % 64 == 0, k >= 192, at least 256 tiles; gated residual: residual rows in the output's pitch (a multiple of 128
 // elements), samples of 2^i >= 128 rows; a bias only together with the gated residual (to_out), n <= 8192.
-#include "zigma_common.h"
+#include "lds_pipe.h"
 #include "linear_plan.h"
 #include "linear4w_body.inc"
 #include "linear4w_body_f16.inc"      // the same loops for fp16 operands (generator cfg f16=True; written by zigma_amd/build.py, not committed): bodies only
 
 namespace zigma {
-
-typedef __attribute__((address_space(3))) unsigned char *lds4w_ptr_t;
 
 // EPI: 0 = 256-wide tiles only, no epilogue operands (in_proj, to_q); 1 = + narrow tiles; 2 = + gated residual; 3 = + bias.
 // VARIANT > 0: timing probes of tools/linear4w_probe.py (only in a library built with -DZIGMA_LINEAR4W_PROBES, EPI 0)
@@ -45,7 +43,7 @@ void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int
     // start skew (probe): every CU finishes its tiles — and fires its 128 KB of stores — at the same moment otherwise
     for (int i = 0, n = (static_cast<int>(blockIdx.x) * ((p.flags >> 20) & 15)) >> 3; i < n; ++i) __builtin_amdgcn_s_sleep(16);
 #endif
-    const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds4w_ptr_t)(smem)));
+    const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)(smem)));
     const unsigned w_pitch = static_cast<unsigned>(p.w_row_stride * 2), x_pitch = static_cast<unsigned>(p.x_row_stride * 2),
                    o_pitch = static_cast<unsigned>(p.out_row_stride * 2);
     // scalars that never change, packed (an asm statement takes at most 30 operands)
@@ -57,7 +55,7 @@ void linear4w_kernel(const zigma_linear_params_t p, const int tiles_n, const int
     const unsigned j = lane & 31, kh = lane >> 5, wn = wave & 1, wm = wave >> 1;
     const unsigned piece = (lane & 7) ^ (((wave & 1) << 2) | (lane >> 4));
     const unsigned srow = wave * 8 + (lane >> 3);
-    const unsigned sw = (j >> 1) & 7, u = lane & 7, t8 = lane >> 3;
+    const unsigned sw = swz_slot(j), u = lane & 7, t8 = lane >> 3;
     const unsigned voffw0 = srow * w_pitch + piece * 16, voffx0 = srow * x_pitch + piece * 16;
     const unsigned a_base = lds_base + (wn * 128 + j) * 128, b_base = lds_base + (256 + wm * 128 + j) * 128;
     const unsigned t_xor = kh ^ sw;

@@ -11,25 +11,18 @@
 //   v_mfma_f32_32x32x16_bf16, evaluated transposed like the other projection kernels (D[n][m]: W rows are the A operand, tokens the B
 //   operand), so a lane ends up with 4 consecutive features of ONE token per accumulator quad.
 //   BK = 64, four LDS stages of (32 NBLK + 128) rows x 128 B filled by global_load_lds_dwordx4 three k-steps ahead (the bank swizzle
-//   — 16-byte slot ^= (row >> 1) & 7 — is applied to the per-lane SOURCE address and again on the fragment reads); ONE raw s_barrier
+//   — swz_slot, csrc/lds_pipe.h — is applied to the per-lane SOURCE address and again on the fragment reads); ONE raw s_barrier
 //   per k-step behind a counted s_waitcnt vmcnt.
 //   Epilogue: accumulators -> bf16 -> the wave's LDS tile (32 tokens x 32 NBLK features, 16-byte padded pitch) -> 16-byte stores along
 //   the token rows.
 // Limits: bf16 or fp16 (template parameter T), no activation (bias and the gated residual: template flag EPI), k % 64 == 0 and k >= 128, m % 128 == 0, n % (32 NBLK) == 0 for NBLK = 5, 6 or 4 (tried in that order).
-#include "scan_helpers.h"
+#include "lds_pipe.h"
 #include "linear_plan.h"
 
 namespace zigma {
 namespace lsm {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
 constexpr int kBM = 128, kBK = 64, kNST = 4;       // four stages: loads three k-steps ahead (a direct-to-LDS load lands ~1.1 us after its issue)
-
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // EPI: + bias (fp32, before the single rounding) and / or the block's gated branch add out = residual + gate[sample] * bf16(x W^T + bias) (reference
 // model_zigma.py:441-449) — the arithmetic and rounding points of linear_tn_kernel's epilogue (csrc/linear.hip), so the two agree bit for bit.
@@ -56,7 +49,8 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
     const unsigned char *xb = reinterpret_cast<const unsigned char *>(p.x) + static_cast<int64_t>(mt) * kBM * x_pitch;
 
     // staging: instruction i of wave w fills the 8 rows q * 8 .. q * 8 + 7, q = i * 4 + w, of the stage (lane -> row q * 8 + (lane >> 3),
-    // 16-byte piece lane & 7).  The source piece is swizzled by the row: (lane & 7) ^ ((row >> 1) & 7), row & 15 = (w & 1) * 8 + (lane >> 3).
+    // 16-byte piece lane & 7).  The source piece is swizzled by the row: (lane & 7) ^ swz_slot(row), row & 15 = (w & 1) * 8 + (lane >> 3).
+    // (swz_slot(srow) written out: as a call it is folded with srow's two terms only after inlining, and the kernel's schedule changes)
     const int srow = (wave & 1) * 8 + (lane >> 3);
     const unsigned piece = static_cast<unsigned>(((lane & 7) ^ ((srow >> 1) & 7)) << 4);
     // one direct-to-LDS instruction: piece i of the batch of k-step kt -> its stage.  k-steps past the end are clamped to the last one: a harmless
@@ -68,13 +62,13 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
         const unsigned char *src = row < BN ? wb + static_cast<int64_t>(row) * w_pitch : xb + static_cast<int64_t>(row - BN) * x_pitch;
         __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src + ks_src * (kBK * 2) + piece), (lds_ptr_t)(dst) + q * 1024, 16, 0, 0);
     };
-    // fragment reads: row * 128 + (((ks << 1) | kh) ^ ((row >> 1) & 7)) * 16; every row base used here is a multiple of 32, so (row >> 1) & 7 = (j >> 1) & 7
-    const int sw = (j >> 1) & 7;
+    // fragment reads: row * 128 + (((ks << 1) | kh) ^ swz_slot(row)) * 16; every row base used here is a multiple of 32, so swz_slot(row) = swz_slot(j)
+    const int sw = swz_slot(j);
     const int a_row0 = j * 128, b_row0 = (BN + wave * 32 + j) * 128;
 
-    f32x16 acc[NBLK];
+    mfma_f32x16 acc[NBLK];
 #pragma unroll
-    for (int nb = 0; nb < NBLK; ++nb) acc[nb] = f32x16{};
+    for (int nb = 0; nb < NBLK; ++nb) acc[nb] = mfma_f32x16{};
 
 #pragma unroll
     for (int b0 = 0; b0 < kNST - 1; ++b0)
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(256) void linear_sm_kernel(const zigma_linear_param
     wait_vm<0>();                                          // the refills past the end: they must not land in the epilogue's tiles
     // ---- epilogue: D[i][jj], jj = token (lane & 31), i = feature = (r & 3) + 8 (r >> 2) + 4 (lane >> 5): the wave transposes its 32 x BN tile
     // through LDS (the stages are free: barrier) and stores 16-byte pieces along the token rows
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm<0>();
     __builtin_amdgcn_s_barrier();
     unsigned char *scr = smem + wave * (32 * PITCH);
     const uint16_t *biasp = EPI ? reinterpret_cast<const uint16_t *>(p.bias) : nullptr;

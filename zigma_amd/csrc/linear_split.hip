@@ -14,13 +14,13 @@
 //   * the weight planes were split once by the host (they are static at inference); only x is split here: a lane takes 8 consecutive fp32 of a
 //     token row from global memory into registers (the NEXT k-step's loads fly under this step's MFMAs), converts them with v_cvt_pk_bf16_f32,
 //     subtracts, converts the remainder, and writes one 16-byte piece into each of the two LDS planes.  No split activations ever reach HBM.
-//   * LDS: planes of 128 rows x 128 B (w_hi, w_lo, x_hi, x_lo) in linear_sm.hip's layout — 16-byte slot ^= (row >> 1) & 7 on the writes and
+//   * LDS: planes of 128 rows x 128 B (w_hi, w_lo, x_hi, x_lo) in linear_sm.hip's layout — 16-byte slot ^= swz_slot(row) (csrc/lds_pipe.h) on the writes and
 //     again on the fragment reads (conflict-free ds_read_b128 for 32 consecutive rows).
 //   * epilogue: hi x hi + cross (+ bias), fp32, transposed through a wave-private LDS tile (32 tokens x 64 features, 16-byte padded pitch) so
 //     every global store instruction covers 4 token rows x 256 contiguous bytes.  Token rows past m are neither loaded nor stored.
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; the build fails on scratch or a spill in either instantiation): DESIGN.md §3.4.
-#include "zigma_common.h"
+#include "lds_pipe.h"
 #include "linear_plan.h"
 
 namespace zigma {
@@ -31,8 +31,6 @@ constexpr int kPlane = 128 * 128;                       // bytes of one LDS plan
 constexpr int kEpiPitch = 64 * 4 + 16;                  // epilogue tile: bytes per token row (64 fp32 features, padded)
 constexpr uint32_t kMaxBf16Bits = 0x7f7f0000u;          // the largest finite bf16 as an fp32 pattern
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // 16 bytes in registers (an ext vector: HIP's uint4 struct array would live in memory)
-
 struct args_t {
     const float *x;
     const uint16_t *w_hi, *w_lo;
@@ -42,8 +40,6 @@ struct args_t {
     int64_t m;
     int32_t n, k, tiles_n;
 };
-
-__device__ __forceinline__ int swz(const int row, const int piece) { return row * 128 + ((piece ^ ((row >> 1) & 7)) << 4); }
 
 // split of one value outside the fast path's range (|a| >= the largest finite bf16, infinities, NaNs): hi in the low, lo in the high half
 __device__ __forceinline__ uint32_t split_edge(const float a) {
@@ -151,8 +147,8 @@ __global__ __launch_bounds__(kThreads, 2) void linear_split_kernel(const args_t 
                 if constexpr (LO) crs[a][b][r] = 0.f;
             }
 
-    // fragment reads: every row base is a multiple of 32, so (row >> 1) & 7 = (j >> 1) & 7
-    const int sw = (j >> 1) & 7;
+    // fragment reads: every row base is a multiple of 32, so swz_slot(row) = swz_slot(j)
+    const int sw = swz_slot(j);
     const int a_row0 = (wn * 64 + j) * 128, b_row0 = (wm * 64 + j) * 128;
 
     fetch(0);

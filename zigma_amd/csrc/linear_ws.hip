@@ -20,20 +20,13 @@
 // FB is a template parameter: the 128-feature form (FB = 1: one MFMA per fragment read, k up to 1280 — out_proj / to_out shapes) was
 // instantiated, is bit-identical too and does NOT beat the tiled kernel: out_proj shape 102 vs 97 us, to_out shape 48 vs 45 us, its
 // MFMA-only loop 74.5 us against 65 at the FB = 2 rate (profiles/r04_h_linear_ws_probe_128_panels.jsonl) — not shipped.
-#include "zigma_common.h"
+#include "lds_pipe.h"
 #include "linear_plan.h"
 
 #include <utility>
 
 namespace zigma {
 namespace lws {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
 
 #ifdef ZIGMA_WS_NO_NT
 constexpr bool kWsDefaultPolicyStores = true;     // (A/B build of tools/fwd_nt_ab.sh)
@@ -46,27 +39,20 @@ constexpr int kRing = 8;
 constexpr int kScrOff = kRing * kSlice;   // 131072: 4 waves x 8 KB of epilogue tiles (two token blocks)
 constexpr int kLds = kScrOff + 4 * 8192;  // 163840
 
-// every LDS access and every direct-to-LDS load is inline assembly: hipcc must not see them (it would drain vmcnt before each read)
-template <int OFF>
-__device__ __forceinline__ void lds_rd(u32x4 &d, unsigned addr) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF)); }
-template <int OFF>
-__device__ __forceinline__ void lds_wr8(unsigned addr, const u32x2 &v) { asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory"); }
+// every LDS access (csrc/lds_pipe.h) and every direct-to-LDS load is hand-issued: hipcc must not see them
 __device__ __forceinline__ void glds16(const void *base, unsigned voff, unsigned lds) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds) : "memory");
 }
 __device__ __forceinline__ void ld_w_a(u32x4 &d, const void *ptr, const int off) { asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(d) : "v"(ptr), "n"(off)); }
 __device__ __forceinline__ void ld_w_v(u32x4 &d, const void *ptr, const int off) { asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(d) : "v"(ptr), "n"(off)); }
-template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int N> __device__ __forceinline__ void wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void wait_lgkm_n(const int n) {           // n folds to a constant in the unrolled loop
     if (n <= 0) wait_lgkm<0>(); else if (n == 1) wait_lgkm<1>(); else if (n == 2) wait_lgkm<2>(); else if (n == 3) wait_lgkm<3>(); else wait_lgkm<4>();
 }
-__device__ __forceinline__ void barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // D += W . T^T for one 32 x 32 block; FIRST: the accumulator starts at zero (inline constant as srcC)
 // (T picks the mnemonic: v_mfma_f32_32x32x16_bf16 / _f16 — same operands, same lane maps, same rate)
 template <bool FIRST, typename T>
-__device__ __forceinline__ void mfma_wa(f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in AGPRs
+__device__ __forceinline__ void mfma_wa(mfma_f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in AGPRs
     if constexpr (T::id == ZIGMA_F16) {
         if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "a"(w), "v"(b));
         else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "a"(w), "v"(b));
@@ -76,7 +62,7 @@ __device__ __forceinline__ void mfma_wa(f32x16 &acc, const u32x4 &w, const u32x4
     }
 }
 template <bool FIRST, typename T>
-__device__ __forceinline__ void mfma_wv(f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in VGPRs
+__device__ __forceinline__ void mfma_wv(mfma_f32x16 &acc, const u32x4 &w, const u32x4 &b) {           // W fragment in VGPRs
     if constexpr (T::id == ZIGMA_F16) {
         if constexpr (FIRST) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&a"(acc) : "v"(w), "v"(b));
         else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(w), "v"(b));
@@ -95,7 +81,7 @@ struct WFrags {        // fragment f = FB kg + fb; 256 AGPRs = two accumulator s
 
 // (f and first fold to constants in the unrolled loop: one instruction survives)
 template <int KG, int FB, typename T>
-__device__ __forceinline__ void mfma_f(f32x16 &acc, const WFrags<KG, FB> &w, const int f, const bool first, const u32x4 &b) {
+__device__ __forceinline__ void mfma_f(mfma_f32x16 &acc, const WFrags<KG, FB> &w, const int f, const bool first, const u32x4 &b) {
     if (f < WFrags<KG, FB>::NA) { if (first) mfma_wa<true, T>(acc, w.a[f], b); else mfma_wa<false, T>(acc, w.a[f], b); }
     else { if (first) mfma_wv<true, T>(acc, w.v[f - WFrags<KG, FB>::NA], b); else mfma_wv<false, T>(acc, w.v[f - WFrags<KG, FB>::NA], b); }
 }
@@ -184,13 +170,13 @@ void linear_ws_kernel(const zigma_linear_params_t p, const int panels, const int
     u32x4 bf[2][2];
     lds_rd<0>(bf[0][0], a_off);
     lds_rd<8192>(bf[0][1], a_off);
-    f32x16 acc[2][NB];                                   // [tile parity][FB tb + fb]: the epilogue of a tile runs inside the next tile's k-loop
+    mfma_f32x16 acc[2][NB];                                   // [tile parity][FB tb + fb]: the epilogue of a tile runs inside the next tile's k-loop
     // epilogue pieces of the PREVIOUS tile inside k-group qg of this one: write chunk qg - W0 (4 accumulator registers -> 8 bytes of the
     // wave's LDS tile; in two halves so that each fits one MFMA gap — a gap hides about five single-issue instructions), then read-back chunk
     // qg - R0 (16 bytes per lane) whose store (TPR tokens x RB bytes) follows one k-group later
     constexpr int W0 = 1, R0 = W0 + NWC + 2;
     static_assert(R0 + NRC + 1 <= KG, "the epilogue has to fit the k-loop");
-    auto wr_chunk_rd = [&](f32x16 (&pa)[NB], const int c, float (&d)[4]) {      // c = 4 (FB tb + fb) + q4
+    auto wr_chunk_rd = [&](mfma_f32x16 (&pa)[NB], const int c, float (&d)[4]) {      // c = 4 (FB tb + fb) + q4
         const int b = c >> 2, q4 = c & 3;
         asm volatile("" : "+a"(pa[b]));                             // (pins the four register reads below behind this point of the asm stream)
         d[0] = pa[b][4 * q4]; d[1] = pa[b][4 * q4 + 1]; d[2] = pa[b][4 * q4 + 2]; d[3] = pa[b][4 * q4 + 3];

@@ -7,7 +7,6 @@
 namespace zigma {
 
 constexpr int kCastThreads = 256;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 template <typename T>
 __global__ __launch_bounds__(kCastThreads) void multi_cast_kernel(const zigma_multi_cast_entry_t *__restrict__ table,
@@ -32,12 +31,12 @@ __global__ __launch_bounds__(kCastThreads) void multi_cast_kernel(const zigma_mu
         for (int i = tid * 8; i < n8; i += kCastThreads * 8) {
             const v4f a = *(const v4f __attribute__((address_space(1))) *)(src + i);
             const v4f b = *(const v4f __attribute__((address_space(1))) *)(src + i + 4);
-            v4u o;
+            u32x4 o;
             o.x = pack2_pk<T>(a.x, a.y);
             o.y = pack2_pk<T>(a.z, a.w);
             o.z = pack2_pk<T>(b.x, b.y);
             o.w = pack2_pk<T>(b.z, b.w);
-            *(v4u __attribute__((address_space(1))) *)(dst + i) = o;
+            *(u32x4 __attribute__((address_space(1))) *)(dst + i) = o;
         }
         done = n8;
     }

@@ -10,43 +10,11 @@
 // One wave per row at a time, each wave walks rows with a fixed stride and keeps its partial dweight / dbias in
 // registers; the partials go to the workspace and a finishing kernel adds them in a fixed order (the reference
 // does the same with one partial per SM, layernorm.py:330-347).
-#include "zigma_common.h"
+#include "vec_io.h"
 
 namespace zigma {
 
-__device__ __forceinline__ float nb_wave_sum(float v) {
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-    return v;
-}
-
 constexpr int kNbWaves = 4, kNbMaxWg = 512;
-
-// VEC consecutive columns per lane per iteration (8-16 byte accesses when VEC = 4)
-template <typename T, int VEC> __device__ __forceinline__ void nb_load(const void *base, int64_t idx, float (&f)[VEC]) {
-    if constexpr (VEC == 1) {
-        f[0] = ld<T>(base, idx);
-    } else if constexpr (T::id == ZIGMA_F32) {
-        const uint4 r = *reinterpret_cast<const uint4 *>(reinterpret_cast<const float *>(base) + idx);
-        f[0] = __uint_as_float(r.x); f[1] = __uint_as_float(r.y); f[2] = __uint_as_float(r.z); f[3] = __uint_as_float(r.w);
-    } else {
-        const uint2 r = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(base) + idx);
-        f[0] = to_float<T>(r.x & 0xffffu); f[1] = to_float<T>(r.x >> 16);
-        f[2] = to_float<T>(r.y & 0xffffu); f[3] = to_float<T>(r.y >> 16);
-    }
-}
-template <typename T, int VEC> __device__ __forceinline__ void nb_store(void *base, int64_t idx, const float (&f)[VEC]) {
-    if constexpr (VEC == 1) {
-        st<T>(base, idx, f[0]);
-    } else if constexpr (T::id == ZIGMA_F32) {
-        *reinterpret_cast<uint4 *>(reinterpret_cast<float *>(base) + idx) =
-            make_uint4(__float_as_uint(f[0]), __float_as_uint(f[1]), __float_as_uint(f[2]), __float_as_uint(f[3]));
-    } else {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(base) + idx) =
-            make_uint2(from_float<T>(f[0]) | (uint32_t(from_float<T>(f[1])) << 16),
-                       from_float<T>(f[2]) | (uint32_t(from_float<T>(f[3])) << 16));
-    }
-}
 
 template <typename XT, typename RT, typename WT, int VEC, int ITERS>
 __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma_norm_bwd_params_t p, float *ws) {
@@ -59,7 +27,7 @@ __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma
         const int c = (it * 64 + lane) * VEC;
 #pragma unroll
         for (int v = 0; v < VEC; ++v) { dw[it][v] = 0.f; db[it][v] = 0.f; w[it][v] = 1.f; }
-        if (p.weight && c < cols) nb_load<WT, VEC>(p.weight, c, w[it]);
+        if (p.weight && c < cols) loadv<WT, VEC>(p.weight, c, w[it]);
     }
     for (int64_t r = gw; r < p.rows; r += n_gw) {
         float s[ITERS][VEC], dy[ITERS][VEC];
@@ -70,17 +38,17 @@ __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { s[it][v] = 0.f; dy[it][v] = 0.f; }
             if (c < cols) {
-                nb_load<RT, VEC>(p.xsum, r * p.xsum_row_stride + c, s[it]);
-                nb_load<XT, VEC>(p.dy, r * p.dy_row_stride + c, dy[it]);
+                loadv<RT, VEC>(p.xsum, r * p.xsum_row_stride + c, s[it]);
+                loadv<XT, VEC>(p.dy, r * p.dy_row_stride + c, dy[it]);
             }
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { sum += s[it][v]; sq += s[it][v] * s[it][v]; }
         }
         float mean = 0.f, rstd;
         if (p.is_rms) {
-            rstd = rsqrtf(nb_wave_sum(sq) / cols + p.eps);
+            rstd = rsqrtf(wave_sum<64>(sq) / cols + p.eps);
         } else {
-            mean = nb_wave_sum(sum) / cols;
+            mean = wave_sum<64>(sum) / cols;
             float var = 0.f;
 #pragma unroll
             for (int it = 0; it < ITERS; ++it) {
@@ -90,7 +58,7 @@ __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma
                     for (int v = 0; v < VEC; ++v) { const float d = s[it][v] - mean; var += d * d; }
                 }
             }
-            rstd = rsqrtf(nb_wave_sum(var) / cols + p.eps);
+            rstd = rsqrtf(wave_sum<64>(var) / cols + p.eps);
         }
         float c1 = 0.f, c2 = 0.f;
 #pragma unroll
@@ -106,8 +74,8 @@ __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma
                 dy[it][v] = wdy;
             }
         }
-        c1 = nb_wave_sum(c1) / cols;
-        c2 = p.is_rms ? 0.f : nb_wave_sum(c2) / cols;
+        c1 = wave_sum<64>(c1) / cols;
+        c2 = p.is_rms ? 0.f : wave_sum<64>(c2) / cols;
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int c = (it * 64 + lane) * VEC;
@@ -117,12 +85,12 @@ __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma
                 for (int v = 0; v < VEC; ++v) ds[v] = (dy[it][v] - s[it][v] * c1 - c2) * rstd;
                 if (p.dresidual_out) {
                     float dr[VEC];
-                    nb_load<RT, VEC>(p.dresidual_out, r * p.dres_out_row_stride + c, dr);
+                    loadv<RT, VEC>(p.dresidual_out, r * p.dres_out_row_stride + c, dr);
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) ds[v] += dr[v];
                 }
-                if (p.dx) nb_store<XT, VEC>(p.dx, r * p.dx_row_stride + c, ds);
-                if (p.dresidual) nb_store<RT, VEC>(p.dresidual, r * p.dres_row_stride + c, ds);
+                if (p.dx) storev<XT, VEC>(p.dx, r * p.dx_row_stride + c, ds);
+                if (p.dresidual) storev<RT, VEC>(p.dresidual, r * p.dres_row_stride + c, ds);
             }
         }
     }

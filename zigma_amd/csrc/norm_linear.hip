@@ -17,22 +17,15 @@
 //   Per pass 32 accumulator registers: 160 + 32 + 24 (three fragment groups of w in flight) stay inside 256, i.e. two waves per SIMD, so one workgroup's
 //   prologue and stores hide behind the other's MFMAs.  Every wave reads the whole w stage from LDS: 1 KB per MFMA and wave, the rate LDS delivers.
 // bf16 or fp16 (template parameter T); n = 512; k = 512, 640, 768 (template parameter KS = k / 64); m % 128 == 0.
+#include "lds_pipe.h"
 #include "norm_linear_plan.h"
-#include "zigma_common.h"
 
 namespace zigma {
 namespace nl {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
-// LDS reads are inline assembly on purpose (as in conv_x_proj.hip): hipcc makes a ds_read it can see wait for EVERY direct-to-LDS load in flight, the
-// younger stages included.  Landing is tracked by hand (counted s_waitcnt vmcnt + s_barrier at the top of a stage); reads are settled by an explicit
-// s_waitcnt lgkmcnt that names the destination registers (so that no use can be scheduled above it).
-template <int OFF> __device__ __forceinline__ void lds_rd(u32x4 &d, unsigned addr) {
+// LDS accesses are hand-issued (csrc/lds_pipe.h); reads are settled by an explicit s_waitcnt lgkmcnt that names the destination registers.
+// lds_rd is lds_pipe.h's but for the constraint letter of the offset ("i", there "n"): the letter changes this kernel's schedule, so the local form stays
+template <int OFF = 0> __device__ __forceinline__ void lds_rd(u32x4 &d, unsigned addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
 }
 template <int N> __device__ __forceinline__ void settle2(u32x4 &a, u32x4 &b) {
@@ -45,10 +38,10 @@ __device__ __forceinline__ void settle4(u32x4 &a, u32x4 &b, u32x4 &c, u32x4 &d) 
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
 }
 // s_waitcnt vmcnt(n), n a run-time (wave-uniform) value of {0, 4, 8}: the instruction takes an immediate
-__device__ __forceinline__ void wait_vm(int n) {
-    if (n >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+__device__ __forceinline__ void wait_vm_n(int n) {
+    if (n >= 8) wait_vm<8>();
+    else if (n >= 4) wait_vm<4>();
+    else wait_vm<0>();
 }
 template <typename T> __device__ __forceinline__ v2f unpk(unsigned w) { return v2f{lo16<T>(w), hi16<T>(w)}; }
 
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
     const unsigned smem_lds = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)(smem)));      // LDS byte address
 
     // ---- sources of the stage loads.  One load instruction = 8 rows x 128 B; lane -> (row l3 of the 8, 16-byte slot (lane & 7) ^ swizzle of the row);
-    // the swizzle of row r is (r >> 1) & 7: for rows 8 i + l3 that is (l3 >> 1) ^ ((i & 1) << 2)
+    // the swizzle of row r is swz_slot(r): for rows 8 i + l3 that is (l3 >> 1) ^ ((i & 1) << 2)
     const int64_t x_pitch = p.x_row_stride * 2, w_pitch = p.w_row_stride * 2, o_pitch = p.out_row_stride * 2;
     const unsigned char *xb = reinterpret_cast<const unsigned char *>(p.x) + m0 * x_pitch;                     // (wave-uniform)
     const unsigned char *wb = reinterpret_cast<const unsigned char *>(p.w) + static_cast<int64_t>(wave) * 8 * w_pitch;
@@ -97,7 +90,7 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
     };
 
     // this lane's 16-byte piece at k-step 0 of row j of a 32-row block; k-step ks is ^ (ks << 5): the slot is ((ks << 1) | kh) ^ swizzle
-    const unsigned lrd = smem_lds + static_cast<unsigned>(j * 128 + ((kh ^ ((j >> 1) & 7)) << 4));
+    const unsigned lrd = smem_lds + static_cast<unsigned>(j * 128 + ((kh ^ swz_slot(j)) << 4));
 
     // ---- the rows: x stages -> registers, fp32 sum on the way ----
     u32x4 xf[NF];
@@ -108,13 +101,13 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
     for (int s = 0; s < NXS; ++s) {
         // stage s has landed (this wave's loads: vmcnt, VM_CNT retires in issue order and one younger stage may stay in flight; every wave's: barrier);
         // stage s - 1 is consumed by every wave, its buffer takes stage s + 2
-        wait_vm(4);
+        wait_vm_n(4);
         __builtin_amdgcn_s_barrier();
         if (s + 2 < NXS) issue_x(s + 2, (s + 2) % NST);
         else issue_w(0, s + 2 - NXS, (s + 2) % NST);
         const unsigned a = lrd + (s % NST) * SB + wave * 4096;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) lds_rd<0>(xf[s * 4 + ks], a ^ (ks << 5));
+        for (int ks = 0; ks < 4; ++ks) lds_rd(xf[s * 4 + ks], a ^ (ks << 5));
         settle4(xf[s * 4], xf[s * 4 + 1], xf[s * 4 + 2], xf[s * 4 + 3]);
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
@@ -166,9 +159,9 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
     int buf = NXS % NST;
 #pragma unroll 1
     for (int pass = 0; pass < NPASS; ++pass) {
-        f32x16 acc[2];
-        acc[0] = f32x16{};
-        acc[1] = f32x16{};
+        mfma_f32x16 acc[2];
+        acc[0] = mfma_f32x16{};
+        acc[1] = mfma_f32x16{};
 #pragma unroll
         for (int kk = 0; kk < WPP; ++kk) {
             // behind this stage's loads in the queue: the next stage's (none at the very end) and, in the first two stages of a pass, the 4 stores of
@@ -179,7 +172,7 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
             {
                 const int younger = (pass == NPASS - 1 && kk == WPP - 1) ? 0 : 4;
                 const int stores = (pass > 0 && kk < NST - 1) ? 4 : 0;
-                wait_vm(younger + stores);
+                wait_vm_n(younger + stores);
             }
             __builtin_amdgcn_s_barrier();
             {
@@ -192,7 +185,7 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
             u32x4 wf[3][2];
             auto reads = [&](int g) {
                 const unsigned a = a0 ^ ((g & 3) << 5);
-                if (g < 4) { lds_rd<0>(wf[g % 3][0], a); lds_rd<4096>(wf[g % 3][1], a); }
+                if (g < 4) { lds_rd(wf[g % 3][0], a); lds_rd<4096>(wf[g % 3][1], a); }
                 else { lds_rd<8192>(wf[g % 3][0], a); lds_rd<8192 + 4096>(wf[g % 3][1], a); }
             };
             reads(0);
@@ -216,11 +209,11 @@ __global__ __launch_bounds__(64 * kNlWaves, KS <= 10 ? 2 : 1) void norm_linear_k
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const u32x2 pk = {pack2_pk<T>(acc[nb][q * 4], acc[nb][q * 4 + 1]), pack2_pk<T>(acc[nb][q * 4 + 2], acc[nb][q * 4 + 3])};
-                asm volatile("ds_write_b64 %0, %1" ::"v"(tile + j * kNlOutPitch + nb * 64 + q * 16 + kh * 8), "v"(pk) : "memory");
+                lds_wr8(tile + j * kNlOutPitch + nb * 64 + q * 16 + kh * 8, pk);
             }
         u32x4 t[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) lds_rd<0>(t[i], tile + (i * 8 + l3) * kNlOutPitch + (lane & 7) * 16);
+        for (int i = 0; i < 4; ++i) lds_rd(t[i], tile + (i * 8 + l3) * kNlOutPitch + (lane & 7) * 16);
         settle4(t[0], t[1], t[2], t[3]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4 *>(ob + static_cast<int64_t>(i) * 8 * o_pitch + pass * (2 * kNlPass)) = t[i];

@@ -9,7 +9,6 @@
 namespace zigma {
 
 constexpr int kOptThreads = 256;
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 // (the pointers come out of memory, so the compiler cannot see their address space: say that they are global, or every access is a flat one)
 typedef float __attribute__((address_space(1))) *gf32_ptr;
 typedef const float __attribute__((address_space(1))) *gcf32_ptr;
@@ -175,12 +174,12 @@ __global__ __launch_bounds__(kOptThreads) void multi_adamw_kernel(const zigma_op
             }
             if constexpr (SHADOW) {
                 if (has_shadow) {
-                    v4u o;
+                    u32x4 o;
                     o.x = pack2_pk<T>(pv[0].x, pv[0].y);
                     o.y = pack2_pk<T>(pv[0].z, pv[0].w);
                     o.z = pack2_pk<T>(pv[1].x, pv[1].y);
                     o.w = pack2_pk<T>(pv[1].z, pv[1].w);
-                    *(v4u __attribute__((address_space(1))) *)(shadow + i) = o;
+                    *(u32x4 __attribute__((address_space(1))) *)(shadow + i) = o;
                 }
             }
         }

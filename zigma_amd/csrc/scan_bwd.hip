@@ -21,6 +21,7 @@
 // B_l / C_l: the workgroup widens the tile's 16 x (N + N) values to fp32 once into LDS (one element of each per thread, fetched a tile
 // ahead); every wave reads its 4 states of a step with one wave-uniform ds_read_b128 per operand (a broadcast: no VALU slot, plain
 // operands) and the recurrences run two states per instruction (v_pk_mul_f32 / v_pk_fma_f32), as in scan_tok2_kernel.
+#include "buffer_io.h"
 #include "scan_helpers.h"
 
 namespace zigma {

@@ -1,4 +1,4 @@
-// DPP broadcast / buffer-addressing helpers shared by the forward (scan_tok.inc) and backward (scan_bwd.hip)
+// DPP broadcast helpers and recurrence steps shared by the forward (scan_tok.inc, scan_tok2.inc) and backward (scan_bwd.hip)
 // token-major selective-scan kernels.  gfx950, wave64.
 #pragma once
 #include "zigma_common.h"
@@ -51,19 +51,5 @@ __device__ __forceinline__ void step_h_plain(float dv, float du, float b0, float
         : "v"(dv), "v"(du), "v"(a2[0]), "v"(a2[1]), "v"(a2[2]), "v"(a2[3]), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
 }
 __device__ __forceinline__ void dpp_settle(float &c) { asm volatile("s_nop 1" : "+v"(c)); }
-
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-__device__ __forceinline__ rsrc_t make_rsrc(const void *base, int64_t bytes) {
-    const unsigned n = bytes > 0x7fffffff ? 0x7fffffffu : static_cast<unsigned>(bytes < 0 ? 0 : bytes);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, static_cast<int>(n), 0x00020000);
-}
-template <typename T> __device__ __forceinline__ typename T::raw buf_ld(rsrc_t r, unsigned voff, int soff) {
-    if constexpr (sizeof(typename T::raw) == 2) return static_cast<uint16_t>(__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0));
-    else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-template <typename T> __device__ __forceinline__ void buf_st(typename T::raw v, rsrc_t r, unsigned voff, int soff) {
-    if constexpr (sizeof(typename T::raw) == 2) __builtin_amdgcn_raw_buffer_store_b16(v, r, voff, soff, 0);
-    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
-}
 
 }  // namespace zigma

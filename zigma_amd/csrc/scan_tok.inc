@@ -19,6 +19,7 @@
 #pragma once
 #include <type_traits>
 
+#include "buffer_io.h"
 #include "scan_helpers.h"
 #include "scan_plan.h"
 

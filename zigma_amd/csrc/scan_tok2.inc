@@ -15,6 +15,7 @@
 //     16 VOP2/DPP + 4 v_exp.
 //   * no run-time feature switches inside the loop (row tables are template parameters, no carries, no bounds).
 #pragma once
+#include "buffer_io.h"
 #include "scan_helpers.h"
 
 #include <type_traits>
@@ -141,14 +142,9 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
     const float bc_scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane((LOG2U && !bc_is_c) ? 0x3f317218 : 0x3f800000));   // ln 2 | 1 (wave-uniform: an SGPR; see kAScale)
     const int n_tiles = (k_end - kb) / LT;
     // ---- DTP: W_dt fragments of this wave's 16 channels (B operand: lane = (channel n16, k-group kq)), bias, row descriptors
-    typedef __bf16 dt_bf16x8 __attribute__((ext_vector_type(8)));
-    typedef short dt_s16x4 __attribute__((ext_vector_type(4)));
-    typedef float dt_f32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned dt_u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned dt_u32x2 __attribute__((ext_vector_type(2)));
     const int n16 = lane & 15, kq = lane >> 4;
-    dt_u32x4 wdt0 = {0, 0, 0, 0};
-    dt_u32x4 wdt1 = {0, 0, 0, 0};
+    u32x4 wdt0 = {0, 0, 0, 0};
+    u32x4 wdt1 = {0, 0, 0, 0};
     float dbias = 0.f;
     rsrc_t x_rs = u_rs;
     unsigned xa_voff = 0, up_voff = 0;
@@ -156,8 +152,8 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
     if constexpr (DTP) {
         const int cw = slab * 64 + wave * 16 + n16;
         const unsigned char *wr = reinterpret_cast<const unsigned char *>(p.dt_w) + static_cast<int64_t>(cw) * p.dt_w_row_stride * 2;
-        wdt0 = *reinterpret_cast<const dt_u32x4 *>(wr + kq * 16);                               // r = 8 kq .. 8 kq + 7 (dt_rank >= 32)
-        if (32 + 8 * kq < p.dt_rank) wdt1 = *reinterpret_cast<const dt_u32x4 *>(wr + 64 + kq * 16);     // r = 32 + 8 kq .. + 7, zero beyond dt_rank
+        wdt0 = *reinterpret_cast<const u32x4 *>(wr + kq * 16);                               // r = 8 kq .. 8 kq + 7 (dt_rank >= 32)
+        if (32 + 8 * kq < p.dt_rank) wdt1 = *reinterpret_cast<const u32x4 *>(wr + 64 + kq * 16);     // r = 32 + 8 kq .. + 7, zero beyond dt_rank
         dbias = p.delta_bias ? reinterpret_cast<const float *>(p.delta_bias)[cw] : 0.f;
         x_ls = static_cast<int>(p.dt_x_l_stride) * ES;
         x_rs = make_rsrc(reinterpret_cast<const io_t *>(p.dt_x) + b * p.dt_x_batch_stride, Lm1 * x_ls + 128);
@@ -243,8 +239,8 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
     auto fence_acc = [&]() {
         if constexpr (HI16 && ACC) asm volatile("s_waitcnt vmcnt(0)" : "+v"(rac[0]), "+v"(rac[1]), "+v"(rac[2]), "+v"(rac[3]));
     };
-    dt_u32x4 xa0 = {0, 0, 0, 0};   // DTP: the dt columns of the tile's 16 x_dbl rows as MFMA A fragments
-    dt_u32x4 xa1 = {0, 0, 0, 0};   // (columns 32 .. 63 of the rows: beyond dt_rank they meet zero weights)
+    u32x4 xa0 = {0, 0, 0, 0};   // DTP: the dt columns of the tile's 16 x_dbl rows as MFMA A fragments
+    u32x4 xa1 = {0, 0, 0, 0};   // (columns 32 .. 63 of the rows: beyond dt_rank they meet zero weights)
     uint32_t rbc;
     float Du[RPT];                 // D * u of this wave's rows (forms without the in-kernel dt_proj)
     float cum = 0.f;               // MODE 1: sum of dt over the chunk (every wave sees all steps in its core loop)
@@ -261,8 +257,8 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
         }
         if constexpr (DTP) {
             const int row0 = kb + t * LT;
-            xa0 = __builtin_bit_cast(dt_u32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xa_voff, row0 * x_ls, 0));
-            xa1 = __builtin_bit_cast(dt_u32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xa_voff + 64, row0 * x_ls, 0));
+            xa0 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xa_voff, row0 * x_ls, 0));
+            xa1 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rs, xa_voff + 64, row0 * x_ls, 0));
 #pragma unroll
             for (int i = 0; i < RPT; ++i) ld16(up[i], u_rs, up_voff, (row0 + i) * u_ls);       // (the row of the quad in the SCALAR offset: one lane-offset register)
         }
@@ -305,16 +301,15 @@ __global__ __launch_bounds__(256, R6 ? 6 : 5) void scan_tok2_kernel(const zigma_
             }
         }
         if constexpr (DTP) {
-            dt_f32x4 dacc = {dbias, dbias, dbias, dbias};
+            mfma_f32x4 dacc = {dbias, dbias, dbias, dbias};
             if constexpr (std::is_same<IO, F16>::value) {      // (fp16 models: the same two products on the f16 form of the instruction)
-                typedef _Float16 dt_f16x8 __attribute__((ext_vector_type(8)));
-                dacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dt_f16x8, xa0), __builtin_bit_cast(dt_f16x8, wdt0), dacc, 0, 0, 0);
-                dacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dt_f16x8, xa1), __builtin_bit_cast(dt_f16x8, wdt1), dacc, 0, 0, 0);
+                dacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mfma_f16x8, xa0), __builtin_bit_cast(mfma_f16x8, wdt0), dacc, 0, 0, 0);
+                dacc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(mfma_f16x8, xa1), __builtin_bit_cast(mfma_f16x8, wdt1), dacc, 0, 0, 0);
             } else {
-            dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dt_bf16x8, xa0), __builtin_bit_cast(dt_bf16x8, wdt0), dacc, 0, 0, 0);
+            dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xa0), __builtin_bit_cast(mfma_bf16x8, wdt0), dacc, 0, 0, 0);
             // (the SAME opcode for the second half of k: a v_mfma_f32_16x16x16_bf16 chained behind the 16x16x32 read its C operand before the
             // first product had written all of it — two of every four results wrong on the device; hipcc pads that pair with 3 states)
-            dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dt_bf16x8, xa1), __builtin_bit_cast(dt_bf16x8, wdt1), dacc, 0, 0, 0);
+            dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mfma_bf16x8, xa1), __builtin_bit_cast(mfma_bf16x8, wdt1), dacc, 0, 0, 0);
             }
 #pragma unroll
             for (int i = 0; i < RPT; ++i) {       // D[step 4 kq + i][channel n16]

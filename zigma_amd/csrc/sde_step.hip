@@ -10,16 +10,14 @@ namespace zigma {
 
 constexpr int kSdeThreads = 256;
 constexpr int kSdeOct = 8;                                      // elements per lane: two quads of the noise field
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ v4u philox4x32_10(v4u ctr, uint32_t k0, uint32_t k1) {
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 ctr, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int round = 0; round < 10; ++round) {
         const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * ctr.x;
         const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * ctr.z;
-        ctr = v4u{static_cast<uint32_t>(p1 >> 32) ^ ctr.y ^ k0, static_cast<uint32_t>(p1), static_cast<uint32_t>(p0 >> 32) ^ ctr.w ^ k1, static_cast<uint32_t>(p0)};
+        ctr = u32x4{static_cast<uint32_t>(p1 >> 32) ^ ctr.y ^ k0, static_cast<uint32_t>(p1), static_cast<uint32_t>(p0 >> 32) ^ ctr.w ^ k1, static_cast<uint32_t>(p0)};
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
@@ -49,7 +47,7 @@ template <typename T> __device__ __forceinline__ void load_oct(const void *base,
                 v[4 + j] = hi[j];
             }
         } else {
-            const v4u w = *reinterpret_cast<const v4u *>(static_cast<const uint16_t *>(base) + at);
+            const u32x4 w = *reinterpret_cast<const u32x4 *>(static_cast<const uint16_t *>(base) + at);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 v[2 * j] = lo16<T>(w[j]);
@@ -68,7 +66,7 @@ template <typename T> __device__ __forceinline__ void store_oct(void *base, int6
             *reinterpret_cast<v4f *>(static_cast<float *>(base) + at) = v4f{v[0], v[1], v[2], v[3]};
             *reinterpret_cast<v4f *>(static_cast<float *>(base) + at + 4) = v4f{v[4], v[5], v[6], v[7]};
         } else {
-            *reinterpret_cast<v4u *>(static_cast<uint16_t *>(base) + at) = v4u{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
+            *reinterpret_cast<u32x4 *>(static_cast<uint16_t *>(base) + at) = u32x4{pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
         }
         return;
     }
@@ -97,8 +95,8 @@ __global__ __launch_bounds__(kSdeThreads) void sde_step_kernel(const void *a, co
         for (int h = 0; h < 2; ++h) {
             if (4 * h < cnt) {                                                      // (the second quad of the call's last lane may not exist)
                 const uint64_t q = quad + h;
-                const v4u w = philox4x32_10(v4u{static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), s.step, s.stream}, s.seed_lo, s.seed_hi);
-                if (bits_out) *reinterpret_cast<v4u *>(bits_out + at + 4 * h) = w;
+                const u32x4 w = philox4x32_10(u32x4{static_cast<uint32_t>(q), static_cast<uint32_t>(q >> 32), s.step, s.stream}, s.seed_lo, s.seed_hi);
+                if (bits_out) *reinterpret_cast<u32x4 *>(bits_out + at + 4 * h) = w;
                 float z[4];
                 box_muller(w.x, w.y, z[0], z[1]);
                 box_muller(w.z, w.w, z[2], z[3]);

@@ -14,9 +14,6 @@
 
 namespace zigma {
 
-typedef __bf16 sk_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float sk_f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kSkWaves = 8;
 
 // KS: k / 32 as a compile-time constant — the whole strip of weights (KS 16-byte fragments per lane) is requested up front, no branch sits
@@ -64,18 +61,18 @@ __global__ __launch_bounds__(64 * kSkWaves) void skinny_linear_kernel(const zigm
     };
     auto compute = [&](int strip, const uint4 (&wq)[KS]) {
         const int n0 = strip * 16;
-        sk_f32x4 acc[4];
+        mfma_f32x4 acc[4];
 #pragma unroll
-        for (int mb = 0; mb < 4; ++mb) acc[mb] = sk_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int mb = 0; mb < 4; ++mb) acc[mb] = mfma_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             // (the x fragments do not depend on the strip: without this fence hipcc hoists all 4 KS of them out of the strip loop — 320
             // registers for k = 640 — and spills)
             asm volatile("" ::: "memory");
-            const sk_bf16x8 wf = __builtin_bit_cast(sk_bf16x8, wq[ks]);
+            const mfma_bf16x8 wf = __builtin_bit_cast(mfma_bf16x8, wq[ks]);
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
-                const sk_bf16x8 xf = __builtin_bit_cast(sk_bf16x8, *reinterpret_cast<const uint4 *>(s_x + (mb * 16 + i16) * pitch + ks * 64 + g * 16));
+                const mfma_bf16x8 xf = __builtin_bit_cast(mfma_bf16x8, *reinterpret_cast<const uint4 *>(s_x + (mb * 16 + i16) * pitch + ks * 64 + g * 16));
                 acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf, acc[mb], 0, 0, 0);      // D[i = feature 4 g + r][j = sample i16]
             }
         }

@@ -14,9 +14,6 @@
 
 namespace zigma {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kXpPitch = kXpChunk * 2 + 16;          // bytes per staged weight row (16 B skew)
 
 template <typename T>
@@ -33,9 +30,9 @@ __global__ __launch_bounds__(64 * kXpWaves) void x_proj_kernel(const zigma_xproj
     mr = mr < p.m ? mr : p.m - 1;                                 // rows beyond m: clamped loads, no stores
     const uint16_t *xrow = xw + mr * p.x_row_stride + kh * 8;
 
-    f32x16 acc[3];
+    mfma_f32x16 acc[3];
 #pragma unroll
-    for (int nb = 0; nb < 3; ++nb) acc[nb] = f32x16{};
+    for (int nb = 0; nb < 3; ++nb) acc[nb] = mfma_f32x16{};
     const int n_steps = p.k / 16;                                  // MFMA k-steps over the whole K
     uint4 aq[kXpDepth];                                            // A fragments in flight (k-steps s .. s + depth - 1)
 #pragma unroll
@@ -105,9 +102,9 @@ __global__ __launch_bounds__(64 * kXsWaves) void x_proj_splitk_kernel(const zigm
     uint4 aq[kXsMaxSteps];
 #pragma unroll
     for (int s = 0; s < kXsMaxSteps; ++s) aq[s] = s < steps ? *reinterpret_cast<const uint4 *>(xrow + s * 16) : make_uint4(0, 0, 0, 0);
-    f32x16 acc[3];
+    mfma_f32x16 acc[3];
 #pragma unroll
-    for (int nb = 0; nb < 3; ++nb) acc[nb] = f32x16{};
+    for (int nb = 0; nb < 3; ++nb) acc[nb] = mfma_f32x16{};
     uint4 bq[2][3];
 #pragma unroll
     for (int nb = 0; nb < 3; ++nb) bq[0][nb] = live[nb] ? *reinterpret_cast<const uint4 *>(wrow[nb]) : make_uint4(0, 0, 0, 0);

@@ -10,8 +10,20 @@ namespace zigma {
 
 constexpr int kWave = 64;
 
+// register vectors (ext vectors: an array of HIP's uint4 / float4 structs would live in memory) and the address spaces the builtins ask for
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // 16 bytes in registers
+typedef __attribute__((address_space(3))) unsigned char *lds_ptr_t;
+typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
+
+// sum over the LPR lanes that share a row (LPR = 64: the whole wave)
+template <int LPR> __device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int s = LPR / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+    return v;
+}
 
 // ---- element types -----------------------------------------------------------------------------
 // I/O element wrappers: 16-bit types are carried as raw uint16_t and widened by bit ops (bf16) or
