@@ -45,7 +45,8 @@ extern "C" {
                                * (11, no block changed): zigma_optim_* added
                                * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added
                                * (11, no block changed): zigma_sde_step_fwd / zigma_sde_advance and their blocks added
-                               * (11, no block changed): the plan queries zigma_linear_fwd_plan, zigma_norm_linear_fwd_plan, zigma_linear_f32_split_plan added */
+                               * (11, no block changed): the plan queries zigma_linear_fwd_plan, zigma_norm_linear_fwd_plan, zigma_linear_f32_split_plan added
+                               * (11, no block changed): zigma_optim16_* added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -865,6 +866,91 @@ typedef struct zigma_optim_params {
 int zigma_optim_grad_sumsq(const zigma_optim_params_t *p, void *stream);
 int zigma_optim_prepare(const zigma_optim_params_t *p, void *stream);
 int zigma_optim_adamw(const zigma_optim_params_t *p, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The same tail for a pure bfloat16 model (csrc/optim_step.hip).  (ABI 11, no block changed.)  Parameters and gradients are bf16; both moments
+ * and the optional moving average are float32; the update is formed in float32 and the parameter written back with STOCHASTIC ROUNDING drawn
+ * inside the kernel, so that the expectation of the stored bf16 value is the float32 value (round-to-nearest drops every update below half
+ * an ulp: at lr = 1e-4 a weight of 1.0 never moves).  Three launches: zigma_optim16_grad_sumsq, the EXISTING zigma_optim_prepare (the
+ * caller fills a zigma_optim_params_t with the same partials, n_chunks, state and hyperparameters), zigma_optim16_adamw.
+ *
+ *   table      n_entries x zigma_optim16_row_t in DEVICE memory.  p and g are bf16, m and v float32, all four required; ema (float32) may
+ *              be NULL per row.  Only natural alignment is assumed.  numel == 0 is legal.  dbg_x32 / dbg_bits are test hooks, NULL in
+ *              production: numel floats that receive the float32 value of every element before its rounding, and numel uint16 that receive
+ *              the 16 random bits every element's rounding used (not written with ZIGMA_OPTIM16_NEAREST).  Neither is written on a skipped step.
+ *   chunk_map  as for zigma_optim_*: rows of zigma_multi_cast_chunk_t.  A map row whose entry or offset lies outside the table, or whose
+ *              offset is no multiple of 8, is skipped; so is every map row of a table row that has a NULL p, g, m or v, or whose numel is
+ *              above max_numel.  The table lives in device memory, where the host cannot read it without waiting for the device: these two
+ *              refusals are the kernels' (no pointer of such a row is followed, the sum-of-squares pass stores 0 for it), not a status.
+ *   max_numel  the largest numel of the table, as the host that built it states it.  Needed because an element's random bits are addressed
+ *              by a 32-bit octet index: 2^35 elements or more are refused.
+ *   partials, state   as for zigma_optim_*; the state block is the same zigma_optim_state_t.
+ *   seed_lo, seed_hi, stream   the Philox key and counter word 3.
+ *   flags      ZIGMA_OPTIM16_NEAREST: the parameter is stored as round_to_nearest_even(x) (from_float<BF16>), and no Philox work is done.
+ *
+ * zigma_optim16_grad_sumsq   multi_sumsq_kernel over bf16 gradients: 8 elements per 16-byte load where the piece starts on a 16-byte boundary,
+ *              element by element otherwise; lane, then wave, then the four waves, in a fixed order and without atomics.  Writes `partials` in
+ *              the layout zigma_optim_prepare reads.
+ * zigma_optim16_adamw        grid n_chunks: returns before any store if state->skipped; else per element, in float32:
+ *                  p32 = widen(p), g32 = widen(g)          (exact)
+ *                  the arithmetic of zigma_optim_adamw on (p32, g32, m, v), in its order (the decay as two roundings, m, v, then p) -> x
+ *                  ema += (x - ema) * (1 - ema_decay)      (the float32 x, not its rounding)
+ *                  p = SR(x)
+ *              The gradient is never written.  A workgroup whose present streams all start on 16-byte boundaries moves 8 elements per lane and
+ *              iteration (one 16-byte load each for p and g, two for each float32 stream) and finishes the last numel % 8 one by one; any other
+ *              piece goes element by element.  16 bytes read and 14 written per element with the moving average.
+ *
+ * The rounding.  Let u be the bits of the float32 x.  If the exponent field of u is all ones (inf, NaN), p = from_float<BF16>(x) and no random
+ * bits are used.  Otherwise p = (u + r) >> 16 with r uniform in [0, 65535].  In sign-magnitude this rounds AWAY from zero with probability
+ * (u & 0xffff) / 65536 and towards zero otherwise: E[p] = x exactly, and a bf16-representable x is kept for every r.  A carry out of the largest
+ * finite value gives +-inf, as round-to-nearest would.
+ *
+ * The random bits.  Element i of a tensor (its index in the TENSOR, not in the workgroup's piece) belongs to octet o = i >> 3.
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (o, pid, step, stream), key = (seed_lo, seed_hi))          (the generator of zigma_sde_step_fwd)
+ * and element j = i & 7 takes word j >> 1: its low half if j is even, its high half if j is odd.  `pid` is the row's parameter id (its low 32
+ * bits); `step` is state->step after the prepare launch's increment, converted to uint32.  The counter of the state block is a float32 scalar:
+ * it is exact, and the bits of successive steps distinct, below 2^24 steps.  Chunk offsets are multiples of 8, so the 8-per-lane loop (one
+ * Philox call per lane and iteration), its tail and the element-by-element path draw the same bits for the same element.
+ *
+ * Checked in this order by both, before any launch: NULL block ZIGMA_ERR_NULL; a NULL pointer among those the call uses (sumsq: table,
+ * chunk_map, partials; adamw: table, chunk_map, state) ZIGMA_ERR_NULL; negative counts (or more than 2^31 - 1 chunks) ZIGMA_ERR_SHAPE;
+ * max_numel < 0 or >= 2^35 ZIGMA_ERR_SHAPE; a chunk that is not a multiple of 8 in 8 ... 65536 ZIGMA_ERR_SHAPE; flag bits other than
+ * ZIGMA_OPTIM16_NEAREST ZIGMA_ERR_UNSUPPORTED; beta1 or beta2 outside [0, 1), eps <= 0, a non-finite lr (or weight_decay, max_grad_norm,
+ * ema_decay; NaN anywhere) ZIGMA_ERR_UNSUPPORTED; then n_entries == 0 or n_chunks == 0: nothing is launched, ZIGMA_OK.
+ * ------------------------------------------------------------------------------------------ */
+#define ZIGMA_OPTIM16_NEAREST 1    /* zigma_optim16_params_t.flags: round to nearest even, no random bits */
+
+typedef struct zigma_optim16_row {
+    void *p;             /* parameter, bf16                    */
+    const void *g;       /* gradient, bf16: read only          */
+    float *m;            /* exp_avg                            */
+    float *v;            /* exp_avg_sq                         */
+    float *ema;          /* moving average of p, or NULL       */
+    int64_t numel;
+    int64_t pid;         /* parameter id: counter word 1       */
+    float *dbg_x32;      /* test hook or NULL                  */
+    uint16_t *dbg_bits;  /* test hook or NULL                  */
+    int64_t pad_;        /* rows are 80 bytes                  */
+} zigma_optim16_row_t;
+
+typedef struct zigma_optim16_params {
+    const zigma_optim16_row_t *table;
+    const zigma_multi_cast_chunk_t *chunk_map;
+    int64_t n_entries, n_chunks;
+    int64_t max_numel;
+    float *partials;
+    zigma_optim_state_t *state;
+    double lr, beta1, beta2, eps, weight_decay;
+    double max_grad_norm;   /* <= 0: no clipping (read by zigma_optim_prepare from ITS block; checked here) */
+    double ema_decay;
+    uint32_t seed_lo, seed_hi;   /* the Philox key                  */
+    uint32_t stream;             /* counter word 3                  */
+    int32_t chunk;               /* elements per workgroup          */
+    int32_t flags;               /* ZIGMA_OPTIM16_NEAREST           */
+    int32_t pad_;
+} zigma_optim16_params_t;
+int zigma_optim16_grad_sumsq(const zigma_optim16_params_t *p, void *stream);
+int zigma_optim16_adamw(const zigma_optim16_params_t *p, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * One launch of an SDE sampler's step on the device (csrc/sde_step.hip).  (ABI 11, no block changed.)  The reference draws every Wiener

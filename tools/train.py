@@ -8,8 +8,11 @@ model — synthetic latents, no dataloader / EMA / wandb.  Forward AND backward 
     python tools/train.py --config '{..., "num_classes": 1000}' --class-dropout 0.1          # label dropout: a model that can be guided
 
 --fused-step: the reference's `opt.step()` / `grad_clip` / `update_ema` (train_acc.py:443-448) as zigma_amd.optim.FusedAdamW — AdamW, global-norm
-clipping (before the update), an EMA copy of the model and, under --amp, the 16-bit shadows in one pass, three launches, no host sync.  Without the flag
-the loop is what it was: torch.optim.AdamW(fused=True), no EMA, no clipping.
+clipping (before the update), an EMA copy of the model and, under --amp, the 16-bit shadows in one pass, three launches, no host sync.  With a pure
+bf16 model (--dtype bf16, no --amp) it is zigma_amd.optim.FusedAdamW16: fp32 moments, an fp32 EMA inside the optimizer and the bf16 parameters written
+back with stochastic rounding (--rounding, --opt-seed; every rank passes the same seed, so the replicas stay bit-identical).  Without the flag the
+loop is what it was: torch.optim.AdamW(fused=True), no EMA, no clipping.
+    python tools/train.py --config '{...}' --dtype bf16 --fused-step --max-grad-norm 2.0      # bf16 parameters, stochastic rounding
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/train.py ...   # data parallel
 
 Multi-GPU = plain data parallelism: one process per GPU, `--batch` samples per rank, gradients averaged by
@@ -35,7 +38,10 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--amp", default="off", choices=["off", "bf16", "fp16"],
                     help="mixed precision: the model is fp32 (whatever --dtype says) and the step runs under torch.autocast in this type; fp16 with a GradScaler")
-    ap.add_argument("--fused-step", action="store_true", help="AdamW + clip + EMA + shadow refresh on zigma_amd.optim.FusedAdamW (needs an fp32 model: --amp or --dtype fp32)")
+    ap.add_argument("--fused-step", action="store_true", help="AdamW + clip + EMA on the own kernels: zigma_amd.optim.FusedAdamW for an fp32 model (--amp or --dtype fp32, with the shadow refresh), "
+                                                               "zigma_amd.optim.FusedAdamW16 for a pure bf16 model")
+    ap.add_argument("--rounding", default="stochastic", choices=["stochastic", "nearest"], help="--fused-step with a bf16 model: how the parameter is written back")
+    ap.add_argument("--opt-seed", type=int, default=0, help="--fused-step with a bf16 model: seed of the rounding bits (the same on every rank)")
     ap.add_argument("--wd", type=float, default=None, help="weight decay (default: the optimizer's own, 1e-2)")
     ap.add_argument("--max-grad-norm", type=float, default=None, help="--fused-step: clip the global gradient norm to this before the update")
     ap.add_argument("--ema-decay", type=float, default=0.9999, help="--fused-step: decay of the EMA copy")
@@ -75,9 +81,13 @@ def main():
     if args.fused_step:
         import copy
         from zigma_amd import optim
-        ema = copy.deepcopy(model).requires_grad_(False)
-        opt = optim.FusedAdamW(model.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm, ema_params=ema, ema_decay=args.ema_decay,
-                               shadows=(model, torch.float16 if args.amp == "fp16" else torch.bfloat16) if args.amp != "off" else None, **wd)
+        if mdtype == torch.bfloat16:
+            opt = optim.FusedAdamW16(model.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm, ema=True, ema_decay=args.ema_decay, rounding=args.rounding,
+                                     seed=args.opt_seed, **wd)         # (the fp32 EMA lives in the optimizer: opt.copy_ema_to(a copy of the model) for sampling)
+        else:
+            ema = copy.deepcopy(model).requires_grad_(False)
+            opt = optim.FusedAdamW(model.parameters(), lr=args.lr, max_grad_norm=args.max_grad_norm, ema_params=ema, ema_decay=args.ema_decay,
+                                   shadows=(model, torch.float16 if args.amp == "fp16" else torch.bfloat16) if args.amp != "off" else None, **wd)
     else:
         if args.max_grad_norm is not None or args.time_tail:
             raise SystemExit("tools/train.py: --max-grad-norm and --time-tail go with --fused-step")
@@ -119,10 +129,12 @@ def main():
         losses.append(step().detach())
     ss.fence(device, world)
     dt = (time.perf_counter() - t0) / args.steps
-    tail = {}
+    tail = dict(optimizer=type(opt).__name__)
     if args.fused_step:
         from zigma_amd import optim
-        tail = dict(fused_step=True, step_tail_launches_per_step=optim.STATS["launches"] / max(optim.STATS["steps"], 1), step_tail_table_builds=optim.STATS["table_builds"],
+        if isinstance(opt, optim.FusedAdamW16):
+            tail.update(rounding=args.rounding, opt_seed=args.opt_seed)
+        tail.update(fused_step=True, step_tail_launches_per_step=optim.STATS["launches"] / max(optim.STATS["steps"], 1), step_tail_table_builds=optim.STATS["table_builds"],
                     last_step_skipped=int(opt.skipped), last_grad_norm=float(opt.grad_norm) if args.max_grad_norm is not None else None, max_grad_norm=args.max_grad_norm, ema_decay=args.ema_decay)
         if tail_events:
             tail["step_tail_ms"] = round(sum(a.elapsed_time(b) for a, b in tail_events) / len(tail_events), 4)

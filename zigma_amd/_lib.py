@@ -214,6 +214,19 @@ class OptimParams(C.Structure):
                 + [("shadow_dtype", i32), ("chunk", i32), ("flags", i32), ("pad_", i32)])
 
 
+class Optim16Row(C.Structure):          # one row of the 16-bit step's device table (zigma_amd/optim.py writes the rows as ten int64)
+    _fields_ = [(n, vp) for n in ("p", "g", "m", "v", "ema")] + [("numel", i64), ("pid", i64), ("dbg_x32", vp), ("dbg_bits", vp), ("pad_", i64)]
+
+
+class Optim16Params(C.Structure):
+    _fields_ = ([("table", vp), ("chunk_map", vp), ("n_entries", i64), ("n_chunks", i64), ("max_numel", i64), ("partials", vp), ("state", vp)]
+                + [(n, f64) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm", "ema_decay")]
+                + [(n, C.c_uint32) for n in ("seed_lo", "seed_hi", "stream")] + [("chunk", i32), ("flags", i32), ("pad_", i32)])
+
+
+OPTIM16_NEAREST = 1                     # zigma_optim16_params_t.flags
+
+
 class SdeState(C.Structure):            # the device state block of a trajectory's noise (four 4-byte words)
     _fields_ = [(n, C.c_uint32) for n in ("seed_lo", "seed_hi", "stream", "step")]
 
@@ -229,7 +242,7 @@ class SdeAdvanceParams(C.Structure):
 
 SDE_ROW_ABSOLUTE = 1                    # zigma_sde_step_params_t.flags
 
-EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw", "zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
+EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw", "zigma_optim16_grad_sumsq", "zigma_optim16_adamw", "zigma_multi_cast_fwd", "zigma_linear_fwd", "zigma_norm_linear_fwd", "zigma_linear_f32_split", "zigma_linear_wgrad","zigma_linear_wgrad_workspace_bytes", "zigma_conv_x_proj_fwd", "zigma_scale_reduce_bwd", "zigma_selective_scan_fwd", "zigma_causal_conv1d_fwd", "zigma_add_norm_fwd", "zigma_dt_proj_softplus_fwd", "zigma_cross_attn_fwd", "zigma_x_proj_fwd", "zigma_selective_scan_bwd",
            "zigma_selective_scan_bwd_workspace_bytes", "zigma_causal_conv1d_bwd",
            "zigma_causal_conv1d_bwd_workspace_bytes", "zigma_add_norm_bwd", "zigma_add_norm_bwd_workspace_bytes",
            "zigma_strerror",
@@ -258,7 +271,7 @@ def lib():
                          ("zigma_linear_fwd", LinearParams), ("zigma_conv_x_proj_fwd", ConvXProjParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_calib_launch", CalibParams),
                          ("zigma_linear_wgrad", LinearWgradParams), ("zigma_linear_f32_split", LinearSplitParams), ("zigma_norm_linear_fwd", NormLinearParams),
                          ("zigma_multi_cast_fwd", MultiCastParams), ("zigma_optim_grad_sumsq", OptimParams), ("zigma_optim_prepare", OptimParams),
-                         ("zigma_optim_adamw", OptimParams), ("zigma_sde_step_fwd", SdeStepParams), ("zigma_sde_advance", SdeAdvanceParams)):
+                         ("zigma_optim_adamw", OptimParams), ("zigma_optim16_grad_sumsq", Optim16Params), ("zigma_optim16_adamw", Optim16Params), ("zigma_sde_step_fwd", SdeStepParams), ("zigma_sde_advance", SdeAdvanceParams)):
             fn = getattr(L, name)
             fn.argtypes = [C.POINTER(st), vp]
             fn.restype = C.c_int

@@ -2,6 +2,8 @@
 // average and their 16-bit shadows.  The device table + chunk map of multi_cast.hip: one row per parameter, one map row per workgroup.  Three launches:
 // multi_sumsq_kernel (4 bytes per element read), step_prepare_kernel (one workgroup: norm, skip, step counter, the step's scalars, all on the device, so
 // the host never waits) and multi_adamw_kernel (one pass: 20 bytes per element read, 18 written with EMA and shadow).  No atomics anywhere.
+// zigma_optim16_* (below): the same three launches for bf16 parameters and gradients — multi_sumsq16_kernel, the SAME step_prepare_kernel, and
+// multi_adamw16_kernel, which keeps the moments and the EMA in fp32 and stores the parameter with stochastic rounding (16 bytes read, 14 written).
 #include <cmath>
 
 #include "zigma_common.h"
@@ -215,9 +217,217 @@ static int optim_check(const zigma_optim_params_t &p, int which) {
     return ZIGMA_OK;
 }
 
+// ---- zigma_optim16_*: bf16 parameters and gradients, fp32 moments and EMA, the parameter stored with stochastic rounding ------------------------------
+typedef const uint16_t __attribute__((address_space(1))) *gcu16_ptr;
+typedef u32x4 __attribute__((address_space(1))) *gu32x4_ptr;
+typedef const u32x4 __attribute__((address_space(1))) *gcu32x4_ptr;
+
+// the piece of workgroup blockIdx.x: false for a map row outside the table, off the octet grid or past the tensor's end, and for every piece of a
+// table row the header refuses (a NULL required stream, numel above max_numel) — skipped, never followed
+__device__ __forceinline__ bool optim16_piece(const zigma_optim16_row_t *__restrict__ table, const zigma_multi_cast_chunk_t *__restrict__ chunk_map, int64_t n_entries,
+                                              int chunk, int64_t max_numel, zigma_optim16_row_t &e, int64_t &offset, int &n) {
+    const zigma_multi_cast_chunk_t c = chunk_map[blockIdx.x];
+    if (c.entry < 0 || c.entry >= n_entries) return false;
+    e = table[c.entry];
+    if (e.numel > max_numel || !e.p || !e.g || !e.m || !e.v) return false;
+    if (c.offset < 0 || c.offset >= e.numel || (c.offset & 7) != 0) return false;
+    const int64_t left = e.numel - c.offset;
+    offset = c.offset;
+    n = left < chunk ? static_cast<int>(left) : chunk;
+    return true;
+}
+
+__global__ __launch_bounds__(kOptThreads) void multi_sumsq16_kernel(const zigma_optim16_row_t *__restrict__ table, const zigma_multi_cast_chunk_t *__restrict__ chunk_map,
+                                                                    int64_t n_entries, int chunk, int64_t max_numel, float *__restrict__ partials) {
+    __shared__ float wave_sum[kOptThreads / kWave];
+    zigma_optim16_row_t e;
+    int64_t offset;
+    int n;
+    const int tid = threadIdx.x;
+    float acc = 0.f;
+    if (optim16_piece(table, chunk_map, n_entries, chunk, max_numel, e, offset, n)) {            // (uniform over the workgroup)
+        const gcu16_ptr g = (gcu16_ptr)(static_cast<const uint16_t *>(e.g) + offset);
+        int done = 0;
+        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+            const int n8 = n & ~7;
+            for (int i = tid * 8; i < n8; i += kOptThreads * 8) {
+                const u32x4 w = *(gcu32x4_ptr)(g + i);
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float a = lo16<BF16>(w[h]), b = hi16<BF16>(w[h]);
+                    acc += a * a;
+                    acc += b * b;
+                }
+            }
+            done = n8;
+        }
+        for (int i = done + tid; i < n; i += kOptThreads) {
+            const float a = to_float<BF16>(g[i]);
+            acc += a * a;
+        }
+    }
+    // fixed order: the wave by halving distances, then the four waves in order
+    for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
+    if ((tid & (kWave - 1)) == 0) wave_sum[tid / kWave] = acc;
+    __syncthreads();
+    if (tid == 0) partials[blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];       // (0 for a skipped map row)
+}
+
+// the header's rounding: sign-magnitude add of 16 random bits, then truncation; inf and NaN by from_float
+__device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r16) {
+    const uint32_t u = __float_as_uint(x);
+    if ((u & 0x7f800000u) == 0x7f800000u) return from_float<BF16>(x);
+    return (u + r16) >> 16;
+}
+
+// SR = false: ZIGMA_OPTIM16_NEAREST, no Philox work
+template <bool SR>
+__global__ __launch_bounds__(kOptThreads) void multi_adamw16_kernel(const zigma_optim16_row_t *__restrict__ table, const zigma_multi_cast_chunk_t *__restrict__ chunk_map,
+                                                                    int64_t n_entries, int chunk, int64_t max_numel, const zigma_optim_state_t *__restrict__ state,
+                                                                    AdamConsts c, uint32_t seed_lo, uint32_t seed_hi, uint32_t stream) {
+    const zigma_optim_state_t st = *state;
+    if (st.skipped) return;                                              // before any store: a skipped step changes nothing
+    zigma_optim16_row_t e;
+    int64_t offset;
+    int n;
+    if (!optim16_piece(table, chunk_map, n_entries, chunk, max_numel, e, offset, n)) return;
+    const gu16_ptr p = (gu16_ptr)(static_cast<uint16_t *>(e.p) + offset);
+    const gcu16_ptr g = (gcu16_ptr)(static_cast<const uint16_t *>(e.g) + offset);
+    const gf32_ptr m = (gf32_ptr)(e.m + offset);
+    const gf32_ptr v = (gf32_ptr)(e.v + offset);
+    const bool has_ema = e.ema != nullptr;
+    const gf32_ptr ema = (gf32_ptr)(has_ema ? e.ema + offset : nullptr);
+    const gf32_ptr dbg_x = (gf32_ptr)(e.dbg_x32 ? e.dbg_x32 + offset : nullptr);
+    const gu16_ptr dbg_b = (gu16_ptr)(SR && e.dbg_bits ? e.dbg_bits + offset : nullptr);
+    const float grad_mult = st.grad_mult, step_size = st.step_size, bc2_sqrt = st.bc2_sqrt;
+    const uint32_t step = static_cast<uint32_t>(st.step), pid = static_cast<uint32_t>(e.pid);
+    const uint32_t oct0 = static_cast<uint32_t>(offset >> 3);            // (offset is a multiple of 8 and numel < 2^35)
+    const int tid = threadIdx.x;
+    // uniform over the workgroup: every present stream of the piece starts on a 16-byte boundary -> 8 elements per lane and iteration
+    const uintptr_t low = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                          reinterpret_cast<uintptr_t>(ema);
+    int done = 0;
+    if ((low & 15) == 0) {
+        const int n8 = n & ~7;
+        for (int i = tid * 8; i < n8; i += kOptThreads * 8) {
+            const u32x4 pw = *(gcu32x4_ptr)(p + i);
+            const u32x4 gw = *(gcu32x4_ptr)(g + i);
+            v4f mv[2] = {*(gcv4f_ptr)(m + i), *(gcv4f_ptr)(m + i + 4)};
+            v4f vv[2] = {*(gcv4f_ptr)(v + i), *(gcv4f_ptr)(v + i + 4)};
+            v4f ev[2] = {};
+            if (has_ema) {
+                ev[0] = *(gcv4f_ptr)(ema + i);
+                ev[1] = *(gcv4f_ptr)(ema + i + 4);
+            }
+            u32x4 w = {0u, 0u, 0u, 0u};
+            if constexpr (SR) w = philox4x32_10(u32x4{oct0 + static_cast<uint32_t>(i >> 3), pid, step, stream}, seed_lo, seed_hi);      // one call for the lane's octet
+            u32x4 o;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                uint32_t q[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int j = 2 * h + s;
+                    float pe = s ? hi16<BF16>(pw[h]) : lo16<BF16>(pw[h]);
+                    const float ge = s ? hi16<BF16>(gw[h]) : lo16<BF16>(gw[h]);
+                    float me = mv[j >> 2][j & 3], ve = vv[j >> 2][j & 3];
+                    adamw_element(pe, ge, me, ve, c, grad_mult, step_size, bc2_sqrt);
+                    mv[j >> 2][j & 3] = me;
+                    vv[j >> 2][j & 3] = ve;
+                    ev[j >> 2][j & 3] = ema_element(ev[j >> 2][j & 3], pe, c);
+                    const uint32_t r = (w[h] >> (16 * s)) & 0xffffu;
+                    q[s] = SR ? sr_bf16(pe, r) : static_cast<uint32_t>(from_float<BF16>(pe));
+                    if (dbg_x) dbg_x[i + j] = pe;
+                    if constexpr (SR) {
+                        if (dbg_b) dbg_b[i + j] = static_cast<uint16_t>(r);
+                    }
+                }
+                o[h] = q[0] | (q[1] << 16);
+            }
+            *(gu32x4_ptr)(p + i) = o;
+            *(gv4f_ptr)(m + i) = mv[0];
+            *(gv4f_ptr)(m + i + 4) = mv[1];
+            *(gv4f_ptr)(v + i) = vv[0];
+            *(gv4f_ptr)(v + i + 4) = vv[1];
+            if (has_ema) {
+                *(gv4f_ptr)(ema + i) = ev[0];
+                *(gv4f_ptr)(ema + i + 4) = ev[1];
+            }
+        }
+        done = n8;
+    }
+    for (int i = done + tid; i < n; i += kOptThreads) {                  // unaligned pieces, and a tensor's last numel % 8: the element's own octet and half-word
+        float pe = to_float<BF16>(p[i]), me = m[i], ve = v[i];
+        adamw_element(pe, to_float<BF16>(g[i]), me, ve, c, grad_mult, step_size, bc2_sqrt);
+        m[i] = me;
+        v[i] = ve;
+        if (has_ema) ema[i] = ema_element(ema[i], pe, c);
+        if (dbg_x) dbg_x[i] = pe;
+        if constexpr (SR) {
+            const u32x4 w = philox4x32_10(u32x4{oct0 + static_cast<uint32_t>(i >> 3), pid, step, stream}, seed_lo, seed_hi);
+            const int j = i & 7;
+            const uint32_t lo = (j & 2) ? w.y : w.x, hi = (j & 2) ? w.w : w.z;
+            const uint32_t r = (((j & 4) ? hi : lo) >> (16 * (j & 1))) & 0xffffu;
+            if (dbg_b) dbg_b[i] = static_cast<uint16_t>(r);
+            p[i] = static_cast<uint16_t>(sr_bf16(pe, r));
+        } else {
+            p[i] = from_float<BF16>(pe);
+        }
+    }
+}
+
+// the refusals of both entry points, in the header's order; 1: nothing to launch
+static int optim16_check(const zigma_optim16_params_t &p, bool sumsq) {
+    if (!p.table || !p.chunk_map || !(sumsq ? static_cast<const void *>(p.partials) : static_cast<const void *>(p.state))) return ZIGMA_ERR_NULL;
+    if (p.n_entries < 0 || p.n_chunks < 0 || p.n_chunks > 0x7fffffffLL) return ZIGMA_ERR_SHAPE;
+    if (p.max_numel < 0 || p.max_numel >= (1LL << 35)) return ZIGMA_ERR_SHAPE;
+    if (p.chunk < 8 || p.chunk > 65536 || p.chunk % 8 != 0) return ZIGMA_ERR_SHAPE;
+    if (p.flags & ~ZIGMA_OPTIM16_NEAREST) return ZIGMA_ERR_UNSUPPORTED;
+    if (!(p.beta1 >= 0.0 && p.beta1 < 1.0) || !(p.beta2 >= 0.0 && p.beta2 < 1.0)) return ZIGMA_ERR_UNSUPPORTED;
+    if (!(p.eps > 0.0) || !std::isfinite(p.eps)) return ZIGMA_ERR_UNSUPPORTED;
+    if (!std::isfinite(p.lr) || !std::isfinite(p.weight_decay) || !std::isfinite(p.max_grad_norm) || !std::isfinite(p.ema_decay)) return ZIGMA_ERR_UNSUPPORTED;
+    if (p.n_entries == 0 || p.n_chunks == 0) return 1;
+    return ZIGMA_OK;
+}
+
 }  // namespace zigma
 
 using namespace zigma;
+
+extern "C" int zigma_optim16_grad_sumsq(const zigma_optim16_params_t *pp, void *stream_) {
+    if (!pp) return ZIGMA_ERR_NULL;
+    (void)hipGetLastError();
+    const zigma_optim16_params_t &p = *pp;
+    const int rc = optim16_check(p, true);
+    if (rc != ZIGMA_OK) return rc == 1 ? ZIGMA_OK : rc;
+    hipLaunchKernelGGL(multi_sumsq16_kernel, dim3(static_cast<unsigned>(p.n_chunks)), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream_), p.table, p.chunk_map,
+                       p.n_entries, p.chunk, p.max_numel, p.partials);
+    set_last_kernel("multi_sumsq16");
+    return check_launch();
+}
+
+extern "C" int zigma_optim16_adamw(const zigma_optim16_params_t *pp, void *stream_) {
+    if (!pp) return ZIGMA_ERR_NULL;
+    (void)hipGetLastError();
+    const zigma_optim16_params_t &p = *pp;
+    const int rc = optim16_check(p, false);
+    if (rc != ZIGMA_OK) return rc == 1 ? ZIGMA_OK : rc;
+    const AdamConsts c = {static_cast<float>(p.lr * p.weight_decay), static_cast<float>(1.0 - p.beta1), static_cast<float>(p.beta2), static_cast<float>(1.0 - p.beta2),
+                          static_cast<float>(p.eps), static_cast<float>(1.0 - p.ema_decay)};
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const dim3 grid(static_cast<unsigned>(p.n_chunks));
+    const zigma_optim_state_t *state = p.state;
+    if (p.flags & ZIGMA_OPTIM16_NEAREST) {
+        hipLaunchKernelGGL((multi_adamw16_kernel<false>), grid, dim3(kOptThreads), 0, stream, p.table, p.chunk_map, p.n_entries, p.chunk, p.max_numel, state, c, p.seed_lo,
+                           p.seed_hi, p.stream);
+        set_last_kernel("multi_adamw16_nearest");
+    } else {
+        hipLaunchKernelGGL((multi_adamw16_kernel<true>), grid, dim3(kOptThreads), 0, stream, p.table, p.chunk_map, p.n_entries, p.chunk, p.max_numel, state, c, p.seed_lo,
+                           p.seed_hi, p.stream);
+        set_last_kernel("multi_adamw16_sr");
+    }
+    return check_launch();
+}
 
 extern "C" int zigma_optim_grad_sumsq(const zigma_optim_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;

@@ -11,19 +11,7 @@ namespace zigma {
 constexpr int kSdeThreads = 256;
 constexpr int kSdeOct = 8;                                      // elements per lane: two quads of the noise field
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ u32x4 philox4x32_10(u32x4 ctr, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * ctr.x;
-        const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * ctr.z;
-        ctr = u32x4{static_cast<uint32_t>(p1 >> 32) ^ ctr.y ^ k0, static_cast<uint32_t>(p1), static_cast<uint32_t>(p0 >> 32) ^ ctr.w ^ k1, static_cast<uint32_t>(p0)};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return ctr;
-}
-
+// (philox4x32_10: zigma_common.h)
 // two words -> two normals (the map of the header): u in (0, 1] and x in [0, 2) are exact in fp32
 __device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float &even, float &odd) {
     const float u = static_cast<float>((ra >> 8) + 1u) * 0x1p-24f;

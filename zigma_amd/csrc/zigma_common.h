@@ -25,6 +25,20 @@ template <int LPR> __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11): the counter-based generator of the SDE step's
+// noise (sde_step.hip) and of the 16-bit optimizer's stochastic rounding (optim_step.hip)
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 ctr, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint64_t p0 = static_cast<uint64_t>(0xD2511F53u) * ctr.x;
+        const uint64_t p1 = static_cast<uint64_t>(0xCD9E8D57u) * ctr.z;
+        ctr = u32x4{static_cast<uint32_t>(p1 >> 32) ^ ctr.y ^ k0, static_cast<uint32_t>(p1), static_cast<uint32_t>(p0 >> 32) ^ ctr.w ^ k1, static_cast<uint32_t>(p0)};
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return ctr;
+}
+
 // ---- element types -----------------------------------------------------------------------------
 // I/O element wrappers: 16-bit types are carried as raw uint16_t and widened by bit ops (bf16) or
 // the hardware converter (f16); arithmetic is always float32.

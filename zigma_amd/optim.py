@@ -13,7 +13,10 @@ Two deliberate differences from the reference loop, both stated in DESIGN.md §6
   * a non-finite gradient norm SKIPS the step — parameters, both moments, the EMA, the shadows and the step counter keep their bits — where
     `clip_grad_norm_` would multiply every gradient by NaN and poison the parameters.  `opt.skipped` reports it.
 
-There is no fallback: parameters that are not contiguous fp32 tensors on one GPU are refused at construction."""
+There is no fallback: parameters that are not contiguous fp32 tensors on one GPU are refused at construction.
+
+FusedAdamW16 (below) is the same tail for a pure bf16 model: fp32 moments and EMA, the bf16 parameter written back with stochastic
+rounding drawn inside the update kernel (zigma_optim16_*)."""
 import torch
 
 from . import _lib, amp
@@ -43,6 +46,24 @@ def _check_tensor(t, what, device=None, shape=None):
         raise ValueError(f"FusedAdamW: {what} has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
 
 
+def _check_hyper(who, lr, betas, eps, weight_decay, max_grad_norm, ema_decay):
+    """the constructors' refusals of hyperparameters the launchers would refuse (or torch.optim.AdamW does)"""
+    if isinstance(lr, torch.Tensor):
+        raise ValueError(f"{who}: lr is a host value per launch, not a tensor")
+    if not 0.0 <= lr < float("inf"):
+        raise ValueError(f"{who}: invalid lr {lr}")
+    if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+        raise ValueError(f"{who}: betas {betas} outside [0, 1)")
+    if not 0.0 < eps < float("inf"):
+        raise ValueError(f"{who}: eps must be positive, got {eps}")
+    if not 0.0 <= weight_decay < float("inf"):
+        raise ValueError(f"{who}: invalid weight_decay {weight_decay}")
+    if max_grad_norm is not None and not 0.0 < max_grad_norm < float("inf"):
+        raise ValueError(f"{who}: max_grad_norm must be positive or None, got {max_grad_norm}")
+    if not 0.0 <= ema_decay <= 1.0:
+        raise ValueError(f"{who}: ema_decay {ema_decay} outside [0, 1]")
+
+
 def arena_views(like, device):
     """one zero-filled fp32 arena with a 256-byte slot per tensor of `like` (amp.arena_layout) -> (arena, [view shaped like each tensor])"""
     numels = [t.numel() for t in like]
@@ -69,8 +90,9 @@ class StepTables:
     """the device table, chunk map and partial-sum buffer of a step, rebuilt and uploaded only when the host list of rows has moved (compared every
     step; `zero_grad(set_to_none=False)` keeps the gradients' addresses, so in a steady loop nothing is uploaded or allocated)"""
 
-    def __init__(self, chunk=CHUNK):
+    def __init__(self, chunk=CHUNK, width=8, numel_col=6):
         self.chunk, self.rows, self.numels = chunk, None, None
+        self.width, self.numel_col = width, numel_col                     # int64 words per row, and which of them is numel (zigma_optim16_row_t: 10, 5)
         self.table = self.cmap = self.partials = None
         self.n_chunks = self.builds = 0
 
@@ -78,19 +100,55 @@ class StepTables:
         """-> True if anything was uploaded"""
         if rows == self.rows:
             return False
-        numels = [r[6] for r in rows]
+        numels = [r[self.numel_col] for r in rows]
         if numels != self.numels:
             cmap = amp.build_chunk_map(numels, self.chunk)
             self.cmap = torch.tensor(cmap or [(0, 0)], dtype=torch.int64).to(device)
             self.partials = torch.zeros(max(len(cmap), 1), dtype=torch.float32, device=device)
             self.n_chunks, self.numels = len(cmap), numels
-        self.table = torch.tensor(rows or [(0,) * 8], dtype=torch.int64).to(device)       # (the old table stays alive until here, past its last launch)
+        self.table = torch.tensor(rows or [(0,) * self.width], dtype=torch.int64).to(device)     # (the old table stays alive until here, past its last launch)
         self.rows = rows
         self.builds += 1
         return True
 
 
-class FusedAdamW(torch.optim.Optimizer):
+class _StepTail(torch.optim.Optimizer):
+    """what the two optimizers of this module share: ONE parameter group, the device state block (zigma_optim_state_t in `_block`) behind `step_count`,
+    `skipped` and `grad_norm`, state_dict() as copies, zero_grad() in place"""
+
+    def add_param_group(self, param_group):
+        if self.param_groups:
+            raise ValueError(f"{type(self).__name__}: one parameter group only (the gradient norm is global; the reference trains with one group)")
+        super().add_param_group(param_group)
+
+    @property
+    def step_count(self):
+        """the shared device step counter (fp32 scalar, like the steps of torch's fused / capturable optimizers)"""
+        return self._block[0]
+
+    @property
+    def skipped(self):
+        """device int32 scalar: 1 if the last step changed nothing (non-finite norm or GradScaler's found_inf)"""
+        return self._block.view(torch.int32)[1]
+
+    @property
+    def grad_norm(self):
+        """device fp32 scalar: the last step's global gradient norm before clipping, unscaled (NaN when max_grad_norm is None)"""
+        return self._block[2]
+
+    def state_dict(self):
+        """torch's layout.  Every tensor is a COPY (the live ones are views of the arenas and one shared step, which another optimizer must not
+        alias), and each parameter gets a step of its own, as torch.optim.AdamW keeps them."""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (t.clone() if isinstance(t, torch.Tensor) else t) for n, t in st.items()} for k, st in sd["state"].items()}
+        return sd
+
+    def zero_grad(self, set_to_none=False):
+        """zeroes the gradients in place by default, so that their addresses — and with them the device table — stay put"""
+        super().zero_grad(set_to_none=set_to_none)
+
+
+class FusedAdamW(_StepTail):
     """AdamW (decoupled weight decay, torch.optim.AdamW's formulas) with global-norm clipping, an EMA of the parameters and the 16-bit shadows of
     zigma_amd.amp in one pass, three launches per step (two without clipping), no host synchronisation.
 
@@ -117,20 +175,7 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_params=None, ema_decay=0.9999,
                  shadows=None, *, amsgrad=False, maximize=False):
-        if isinstance(lr, torch.Tensor):
-            raise ValueError("FusedAdamW: lr is a host value per launch, not a tensor")
-        if not 0.0 <= lr < float("inf"):
-            raise ValueError(f"FusedAdamW: invalid lr {lr}")
-        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
-            raise ValueError(f"FusedAdamW: betas {betas} outside [0, 1)")
-        if not 0.0 < eps < float("inf"):
-            raise ValueError(f"FusedAdamW: eps must be positive, got {eps}")
-        if not 0.0 <= weight_decay < float("inf"):
-            raise ValueError(f"FusedAdamW: invalid weight_decay {weight_decay}")
-        if max_grad_norm is not None and not 0.0 < max_grad_norm < float("inf"):
-            raise ValueError(f"FusedAdamW: max_grad_norm must be positive or None, got {max_grad_norm}")
-        if not 0.0 <= ema_decay <= 1.0:
-            raise ValueError(f"FusedAdamW: ema_decay {ema_decay} outside [0, 1]")
+        _check_hyper("FusedAdamW", lr, betas, eps, weight_decay, max_grad_norm, ema_decay)
         # (the keys torch.optim.AdamW's groups carry, so that a state_dict travels both ways)
         defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
                         differentiable=False, fused=True, decoupled_weight_decay=True)
@@ -164,11 +209,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self._install_state()
 
     # ---- one group, torch's state keys ------------------------------------------------------------------------------------------------------------
-    def add_param_group(self, param_group):
-        if self.param_groups:
-            raise ValueError("FusedAdamW: one parameter group only (the gradient norm is global; the reference trains with one group)")
-        super().add_param_group(param_group)
-
     def _check_group(self):
         g = self.param_groups[0]
         if g.get("amsgrad") or g.get("maximize"):
@@ -178,31 +218,9 @@ class FusedAdamW(torch.optim.Optimizer):
         if isinstance(g["lr"], torch.Tensor):
             raise ValueError("FusedAdamW: lr is a host value per launch, not a tensor")
 
-    @property
-    def step_count(self):
-        """the shared device step counter (fp32 scalar, like the steps of torch's fused / capturable optimizers)"""
-        return self._block[0]
-
-    @property
-    def skipped(self):
-        """device int32 scalar: 1 if the last step changed nothing (non-finite norm or GradScaler's found_inf)"""
-        return self._block.view(torch.int32)[1]
-
-    @property
-    def grad_norm(self):
-        """device fp32 scalar: the last step's global gradient norm before clipping, unscaled (NaN when max_grad_norm is None)"""
-        return self._block[2]
-
     def _install_state(self):
         for p, m, v in zip(self.param_groups[0]["params"], self._m, self._v):
             self.state[p] = {"step": self._block[0], "exp_avg": m, "exp_avg_sq": v}
-
-    def state_dict(self):
-        """torch's layout.  Every tensor is a COPY (the live ones are views of the arenas and one shared step, which another optimizer must not
-        alias), and each parameter gets a step of its own, as torch.optim.AdamW keeps them."""
-        sd = super().state_dict()
-        sd["state"] = {k: {n: (t.clone() if isinstance(t, torch.Tensor) else t) for n, t in st.items()} for k, st in sd["state"].items()}
-        return sd
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -227,10 +245,6 @@ class FusedAdamW(torch.optim.Optimizer):
         self._block[0] = steps[0] if steps else 0.0
         self.state.clear()
         self._install_state()
-
-    def zero_grad(self, set_to_none=False):
-        """zeroes the gradients in place by default, so that their addresses — and with them the device table — stay put"""
-        super().zero_grad(set_to_none=set_to_none)
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
     def _shadows_now(self):
@@ -291,6 +305,220 @@ class FusedAdamW(torch.optim.Optimizer):
         _lib.call("zigma_optim_adamw", P, self.device)
         if fresh:
             grp.written_by_step(self._shadow_dtype)
+        STATS["steps"] += 1
+        STATS["launches"] += 3 if self.max_grad_norm is not None else 2
+        return loss
+
+
+# ---- the same tail for a pure bf16 model ----------------------------------------------------------------------------------------------------------------
+MAX_NUMEL16 = 1 << 35     # an element's random bits are addressed by a 32-bit octet index (include/zigma_hip.h)
+_ROUNDINGS = ("stochastic", "nearest")
+
+
+def _check_tensor16(t, what, device=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"FusedAdamW16: {what} is not a tensor")
+    if t.layout != torch.strided:
+        raise ValueError(f"FusedAdamW16: {what} is sparse; the kernel takes dense tensors only")
+    if t.dtype == torch.float16:
+        raise ValueError(f"FusedAdamW16: {what} is float16; the kernel takes bfloat16 only.  A pure fp16 model has no loss scaling to train with: "
+                         "torch.amp.GradScaler will not unscale 16-bit gradients.  Keep fp32 master parameters under torch.autocast(float16) and use FusedAdamW")
+    if t.dtype == torch.float32:
+        raise ValueError(f"FusedAdamW16: {what} is float32; the kernel takes bfloat16 only (fp32 parameters go to zigma_amd.optim.FusedAdamW)")
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"FusedAdamW16: {what} is {t.dtype}; the kernel takes bfloat16 only")
+    if not _device_ok(t):
+        raise ValueError(f"FusedAdamW16: {what} is on {t.device}; the kernel needs a GPU (there is no CPU fallback)")
+    if device is not None and t.device != device:
+        raise ValueError(f"FusedAdamW16: {what} is on {t.device}, the parameters are on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"FusedAdamW16: {what} is not contiguous")
+    if t.numel() >= MAX_NUMEL16:
+        raise ValueError(f"FusedAdamW16: {what} has {t.numel()} elements; the kernel addresses its random bits below 2^35 elements per tensor")
+
+
+def step_rows16(params, grads, ms, vs, emas):
+    """the 16-bit table's rows, one per parameter that has a gradient: ten int64 each, zigma_optim16_row_t.  `pid` is the parameter's index in
+    `params`, NOT the row's index: a parameter's random bits do not depend on which others got a gradient."""
+    rows = []
+    for i, (p, g) in enumerate(zip(params, grads)):
+        if g is None:
+            continue
+        rows.append((p.data_ptr(), g.data_ptr(), ms[i].data_ptr(), vs[i].data_ptr(), emas[i].data_ptr() if emas else 0, p.numel(), i, 0, 0, 0))
+    return rows
+
+
+class FusedAdamW16(_StepTail):
+    """FusedAdamW for a pure bfloat16 model: bf16 parameters and gradients, fp32 moments, an optional fp32 EMA, and the parameter written back with
+    STOCHASTIC ROUNDING drawn inside the update kernel (zigma_optim16_* of include/zigma_hip.h).  Three launches per step (two
+    without clipping), no host synchronisation; clip-before-update and skip-on-a-non-finite-norm as in FusedAdamW.
+
+    Why: in bf16 an update below half an ulp is rounded away.  At lr = 1e-4 a weight of 1.0 (a norm weight) never moves under round-to-nearest, and
+    an EMA with decay 0.9999 kept in bf16 is a frozen copy.  Here the update and the EMA are formed in fp32 from the bf16 parameter, the EMA stays
+    fp32, and the parameter is rounded up or down with probability proportional to the distance: the expectation of what is stored is the fp32 value.
+
+      ema            True: a third fp32 arena, initialised from the parameters (exact widening); ema += (x - ema) * (1 - ema_decay) with the fp32 x
+                     of the step, not its rounding.  `ema_tensors()` hands out the views, `copy_ema_to(module)` writes them, rounded to nearest,
+                     into a module's bf16 parameters (a sampling copy).
+      rounding       "stochastic", or "nearest": round to nearest even, no random bits (what torch.optim.AdamW does on bf16 tensors).
+      seed, stream   the random bits are a function of (seed, stream, the parameter's index in the group, the step counter, the element's index):
+                     Philox4x32-10, nothing else.  EVERY RANK of a DistributedDataParallel run must pass the same seed and stream: the replicas
+                     then round alike and stay bit-identical.
+
+    Under graph replay (torch.cuda.graph) seed, stream and the hyperparameters are baked into the graph, but the step counter is read ON THE DEVICE:
+    every replay draws fresh bits.  The counter is an fp32 scalar, exact below 2^24 steps.  Capture after one eager step, with
+    `zero_grad(set_to_none=False)` (this class's default).
+
+    One parameter group; contiguous bf16 parameters on one GPU with dense contiguous bf16 gradients; anything else raises: fp32 parameters belong to
+    FusedAdamW, fp16 ones have no loss scaling to train with.  state[p] has torch's keys "step" (ONE device scalar shared by all), "exp_avg",
+    "exp_avg_sq" (fp32 views of two arenas) plus "ema".  state_dict() hands out copies and records rounding, seed and stream in the group;
+    load_state_dict() takes its own dicts and those of torch.optim.AdamW on the same bf16 model (bf16 moments are widened), and raises if the
+    per-parameter steps disagree.  `skipped`, `grad_norm` and `step_count` are device scalars, as in FusedAdamW."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema=False, ema_decay=0.9999,
+                 rounding="stochastic", seed=0, stream=0, *, amsgrad=False, maximize=False):
+        _check_hyper("FusedAdamW16", lr, betas, eps, weight_decay, max_grad_norm, ema_decay)
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
+                        differentiable=False, fused=True, decoupled_weight_decay=True, rounding=rounding, seed=seed, stream=stream)
+        super().__init__(params, defaults)
+        self._check_group()
+        ps = self.param_groups[0]["params"]
+        for i, p in enumerate(ps):
+            _check_tensor16(p, f"parameter {i}", ps[0].device)
+        self.device = ps[0].device
+        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
+        self._m_arena, self._m = arena_views(ps, self.device)
+        self._v_arena, self._v = arena_views(ps, self.device)
+        self._ema_arena, self._ema = None, None
+        if ema:
+            self._ema_arena, self._ema = arena_views(ps, self.device)
+            with torch.no_grad():
+                for e, p in zip(self._ema, ps):
+                    e.copy_(p)                                                         # bf16 -> fp32: exact
+        self._block = torch.zeros(8, dtype=torch.float32, device=self.device)             # zigma_optim_state_t
+        self._tables = StepTables(width=10, numel_col=5)
+        self._cast_tables = None
+        self._install_state()
+
+    # ---- one group, torch's state keys ------------------------------------------------------------------------------------------------------------
+    def _check_group(self):
+        g = self.param_groups[0]
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("FusedAdamW16: amsgrad and maximize are not implemented by the kernel")
+        if g.get("decoupled_weight_decay") is False:
+            raise ValueError("FusedAdamW16: the kernel's weight decay is decoupled (AdamW); this group asks for Adam's L2 form")
+        if isinstance(g["lr"], torch.Tensor):
+            raise ValueError("FusedAdamW16: lr is a host value per launch, not a tensor")
+        if g["rounding"] not in _ROUNDINGS:
+            raise ValueError(f"FusedAdamW16: rounding is one of {_ROUNDINGS}, got {g['rounding']!r}")
+        if isinstance(g["seed"], bool) or not isinstance(g["seed"], int) or not 0 <= g["seed"] < 1 << 64:
+            raise ValueError(f"FusedAdamW16: seed is an integer in [0, 2^64), got {g['seed']!r}")
+        if isinstance(g["stream"], bool) or not isinstance(g["stream"], int) or not 0 <= g["stream"] < 1 << 32:
+            raise ValueError(f"FusedAdamW16: stream is an integer in [0, 2^32), got {g['stream']!r}")
+
+    def ema_tensors(self):
+        """the fp32 EMA views, parallel to the parameters (live: the step writes them)"""
+        if self._ema is None:
+            raise RuntimeError("FusedAdamW16: built with ema=False")
+        return list(self._ema)
+
+    def copy_ema_to(self, module):
+        """writes the EMA, rounded to nearest even, into the bf16 parameters of `module` (a copy of the model: the same parameters in the same order) in
+        one zigma_multi_cast_fwd launch"""
+        dst = [q.detach() for q in module.parameters()]
+        src = self.ema_tensors()
+        if len(dst) != len(src):
+            raise ValueError(f"FusedAdamW16: the module has {len(dst)} parameters, the optimizer {len(src)}")
+        for i, (d, s) in enumerate(zip(dst, src)):
+            if d.dtype != torch.bfloat16 or d.shape != s.shape or d.device != s.device or not d.is_contiguous():
+                raise ValueError(f"FusedAdamW16: parameter {i} of the module is not a contiguous bfloat16 tensor of shape {tuple(s.shape)} on {s.device}")
+        self._cast_tables = amp.cast_tensors(src, dst)                                    # (kept alive past the launch)
+        amp._on_optimizer_step(self, (), {})                # the parameters of `module` were written behind their version counters: what is cached of them is stale
+
+    def _install_state(self):
+        for i, p in enumerate(self.param_groups[0]["params"]):
+            self.state[p] = {"step": self._block[0], "exp_avg": self._m[i], "exp_avg_sq": self._v[i]}
+            if self._ema is not None:
+                self.state[p]["ema"] = self._ema[i]
+
+    def load_state_dict(self, state_dict):
+        """its own dicts, or torch.optim.AdamW's on the same bf16 model.  Written out here and not left to torch.optim.Optimizer.load_state_dict, which
+        casts every floating state tensor to its parameter's dtype: the fp32 moments and EMA would come back rounded to bf16.  A dict without "ema"
+        leaves the EMA as it is."""
+        import copy
+        groups = state_dict["param_groups"]
+        ps = self.param_groups[0]["params"]
+        if len(groups) != 1:
+            raise ValueError("FusedAdamW16: one parameter group only")
+        ids = list(groups[0]["params"])
+        if len(ids) != len(ps):
+            raise ValueError(f"FusedAdamW16: the loaded group has {len(ids)} parameters, this optimizer {len(ps)}")
+        old = dict(self.param_groups[0])
+        self.param_groups[0].update({k: copy.deepcopy(v) for k, v in groups[0].items() if k != "params"})
+        try:
+            self._check_group()
+        except ValueError:
+            self.param_groups[0].clear()
+            self.param_groups[0].update(old)
+            raise
+        state = state_dict["state"]
+        loaded = [state.get(i) or None for i in ids]
+        steps = [torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()) for st in loaded if st is not None]
+        steps = torch.stack(steps).tolist() if steps else []
+        if len(set(steps)) > 1 or (steps and steps[0] != 0 and len(steps) != len(ps)):
+            raise ValueError("FusedAdamW16: the loaded per-parameter steps disagree (or some parameters have none); this optimizer keeps ONE step counter: "
+                             f"{sorted(set(steps))}, {len(steps)} of {len(ps)} parameters")
+        with torch.no_grad():
+            for i, st in enumerate(loaded):
+                if st is None:
+                    self._m[i].zero_()
+                    self._v[i].zero_()
+                    continue
+                self._m[i].copy_(st["exp_avg"])                                           # (a bf16 moment of torch's is widened: exact)
+                self._v[i].copy_(st["exp_avg_sq"])
+                if self._ema is not None and "ema" in st:
+                    self._ema[i].copy_(st["ema"])
+            self._block.zero_()
+            self._block[0] = steps[0] if steps else 0.0
+        self.state.clear()
+        self._install_state()
+
+    # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        self._check_group()
+        ps = g["params"]
+        grads = [p.grad for p in ps]
+        for i, (p, gr) in enumerate(zip(ps, grads)):
+            if gr is not None and (gr.dtype != torch.bfloat16 or gr.layout != torch.strided or gr.device != p.device or gr.shape != p.shape or not gr.is_contiguous()
+                                   or not p.is_contiguous() or p.dtype != torch.bfloat16):
+                raise RuntimeError(f"FusedAdamW16: parameter {i} or its gradient is not a dense contiguous bfloat16 tensor on {self.device}")
+        rows = step_rows16(ps, grads, self._m, self._v, self._ema)
+        if not rows:
+            return loss
+        T = self._tables
+        STATS["table_builds"] += T.update(rows, self.device)
+        P = _lib.Optim16Params()
+        P.table, P.chunk_map, P.n_entries, P.n_chunks, P.max_numel = T.table.data_ptr(), T.cmap.data_ptr(), len(rows), T.n_chunks, max(T.numels)
+        P.state = self._block.data_ptr()
+        P.lr, (P.beta1, P.beta2), P.eps, P.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        P.max_grad_norm, P.ema_decay = self.max_grad_norm or 0.0, self.ema_decay
+        P.seed_lo, P.seed_hi, P.stream = g["seed"] & 0xffffffff, g["seed"] >> 32, g["stream"]
+        P.chunk, P.flags = T.chunk, _lib.OPTIM16_NEAREST if g["rounding"] == "nearest" else 0
+        Q = _lib.OptimParams()                              # the prepare launch is the fp32 path's, on its own block
+        Q.table, Q.chunk_map, Q.n_entries, Q.n_chunks, Q.state = P.table, P.chunk_map, P.n_entries, P.n_chunks, P.state
+        Q.lr, Q.beta1, Q.beta2, Q.eps, Q.weight_decay, Q.max_grad_norm, Q.ema_decay = P.lr, P.beta1, P.beta2, P.eps, P.weight_decay, P.max_grad_norm, P.ema_decay
+        Q.shadow_dtype, Q.chunk, Q.flags = -1, T.chunk, 0
+        if self.max_grad_norm is not None:
+            P.partials = Q.partials = T.partials.data_ptr()
+            _lib.call("zigma_optim16_grad_sumsq", P, self.device)
+        _lib.call("zigma_optim_prepare", Q, self.device)
+        _lib.call("zigma_optim16_adamw", P, self.device)
         STATS["steps"] += 1
         STATS["launches"] += 3 if self.max_grad_norm is not None else 2
         return loss
