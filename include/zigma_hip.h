@@ -46,7 +46,9 @@ extern "C" {
                                * (11, no block changed): zigma_final_layer_cfg_fwd / zigma_final_layer_cfg_params_t added
                                * (11, no block changed): zigma_sde_step_fwd / zigma_sde_advance and their blocks added
                                * (11, no block changed): the plan queries zigma_linear_fwd_plan, zigma_norm_linear_fwd_plan, zigma_linear_f32_split_plan added
-                               * (11, no block changed): zigma_optim16_* added */
+                               * (11, no block changed): zigma_optim16_* added
+                               * (11, no block changed): the plan queries of the operators around the blocks, cross-attention, zigma_scale_reduce_bwd and
+                               *    zigma_linear_wgrad added (zigma_patch_embed_fwd_plan ... zigma_linear_wgrad_plan) */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -383,7 +385,7 @@ int zigma_add_norm_bwd(const zigma_norm_bwd_params_t *p, void *stream);
  * modulate backward: a = x, s = scale, s_add = 1 (out = dx, sum_c r1 = dscale, sum_c r2 = dshift); gated add backward: a = branch,
  * s = gate, s_add = 0 (out = dbranch, sum_c r1 = dgate).  dy, a, out: (rows, cols) bf16 rows; s: (batch, cols) bf16 rows;
  * r1, r2: float32 [batch][rows_per_batch / 64][cols], summed over the chunks by the caller (fixed order, no float atomics).
- * Limits: bf16, cols % 128 == 0, rows_per_batch % 64 == 0, 16-byte aligned rows.
+ * Limits and refusals: plan_scale_reduce_bwd() of csrc/attn_plan.h (zigma_scale_reduce_bwd_plan below).
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_glue_bwd_params {
     int64_t rows;
@@ -405,7 +407,8 @@ int zigma_scale_reduce_bwd(const zigma_glue_bwd_params_t *p, void *stream);
  * Replaces the scaled_dot_product_attention / xformers call of CrossAttention.forward (reference model_zigma.py:113-127;
  * ZigMa: 8 heads x 64, 77 text tokens).  q, out: (batch, seqlen, heads*head_dim) rows; k, v: (batch, n_ctx, heads*head_dim)
  * rows (any row / batch pitch: e.g. slices of one batched K/V projection); head h = columns [h*head_dim, (h+1)*head_dim).
- * Limits: bf16 or fp16 (q, k, v, out alike), head_dim 64, n_ctx <= 128, rows 16-byte aligned.
+ * Limits: bf16 or fp16 (q, k, v, out alike), head_dim 64, n_ctx <= 128, rows 16-byte aligned.  Every refusal and the launch geometry, of the forward
+ * and of the backward below: plan_cross_attn() / plan_cross_attn_bwd(), csrc/attn_plan.h.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_xattn_params {
     int32_t batch, seqlen, n_ctx, heads, head_dim;
@@ -575,7 +578,7 @@ int zigma_norm_linear_fwd(const zigma_norm_linear_params_t *p, void *stream);
  * `workspace` of zigma_linear_wgrad_workspace_bytes() bytes (0 when one slab serves; private layout) and are added in ascending slab order,
  * rounded once: no atomics, the result is bit-reproducible.  Nothing outside out[:n, :k] is written.
  * Limits: m >= 1; n, k multiples of 8 up to 8192; row strides multiples of 8 elements; dy, x, out, workspace 16-byte aligned, out rows a
- * multiple of 16 bytes apart.
+ * multiple of 16 bytes apart.  Every refusal, the slab count and the workspace size: plan_wgrad(), csrc/wgrad_plan.h.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_linear_wgrad_params {
     int64_t m;               /* tokens: the contraction length */
@@ -646,6 +649,7 @@ int zigma_linear_f32_split(const zigma_linear_split_params_t *p, void *stream);
  * zigma_skinny_linear_fwd: out = act(x) W^T + bias for m <= 64 rows (the timestep MLP :232-275 and the adaLN modulation :441, :447 of all
  *   blocks in one call); flags bit 0: act = SiLU (rounded to bf16 like the reference's module), else identity.
  *   Limits: n % 16 == 0, k % 128 == 0, k <= 1024; x, w rows 16-byte aligned, out rows 8-byte aligned, bias 8-byte aligned.
+ * Every refusal of the four, in its order, and the launch geometry: plan_patch_embed() ... plan_skinny_linear(), csrc/outer_plan.h.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_patch_embed_params {
     int32_t batch, in_chans, height, width, patch, embed_dim;
@@ -715,7 +719,8 @@ int zigma_skinny_linear_fwd(const zigma_skinny_params_t *p, void *stream);
  * Checked in this order, before any launch: NULL block ZIGMA_ERR_NULL; rows < 0, cols < 8, n_out < 1 ZIGMA_ERR_SHAPE; flags != 0
  * ZIGMA_ERR_UNSUPPORTED; dtype other than ZIGMA_BF16, out_dtype other than ZIGMA_F32 / ZIGMA_BF16 ZIGMA_ERR_DTYPE; cols % 8, cols > 2048,
  * n_out > 16, a geometry field < 1, n_out != patch^2 chans, rows % rows_per_sample, rows_per_sample % tokens_per_frame, tokens_per_frame % grid_w
- * ZIGMA_ERR_SHAPE; rows == 0 ZIGMA_OK, nothing touched; NULL x_cond / x_uncond / weight / scale / out ZIGMA_ERR_NULL; alignment ZIGMA_ERR_STRIDE.
+ * ZIGMA_ERR_SHAPE; rows == 0 ZIGMA_OK, nothing touched; NULL x_cond / x_uncond / weight / scale / out ZIGMA_ERR_NULL; alignment ZIGMA_ERR_STRIDE:
+ * plan_final_layer_cfg(), csrc/outer_plan.h.
  * ------------------------------------------------------------------------------------------ */
 typedef struct zigma_final_layer_cfg_params {
     int64_t rows;            /* rows of EACH half */
@@ -1057,6 +1062,17 @@ int zigma_dt_proj_softplus_fwd_plan(const zigma_dtproj_params_t *p, const char *
 int zigma_linear_fwd_plan(const zigma_linear_params_t *p, const char **kernel);
 int zigma_norm_linear_fwd_plan(const zigma_norm_linear_params_t *p, const char **kernel);
 int zigma_linear_f32_split_plan(const zigma_linear_split_params_t *p, const char **kernel);
+/* ... and of the operators around the blocks (csrc/outer_plan.h), cross-attention and the glue backward (csrc/attn_plan.h) and the weight
+ * gradient (csrc/wgrad_plan.h) (ABI 11, no block changed), under the same rules: every refusal of these entry points is a clause of its plan_*(). */
+int zigma_patch_embed_fwd_plan(const zigma_patch_embed_params_t *p, const char **kernel);
+int zigma_timestep_embed_fwd_plan(const zigma_timestep_embed_params_t *p, const char **kernel);
+int zigma_skinny_linear_fwd_plan(const zigma_skinny_params_t *p, const char **kernel);
+int zigma_final_layer_fwd_plan(const zigma_final_layer_params_t *p, const char **kernel);
+int zigma_final_layer_cfg_fwd_plan(const zigma_final_layer_cfg_params_t *p, const char **kernel);
+int zigma_cross_attn_fwd_plan(const zigma_xattn_params_t *p, const char **kernel);
+int zigma_cross_attn_bwd_plan(const zigma_xattn_bwd_params_t *p, const char **kernel);
+int zigma_scale_reduce_bwd_plan(const zigma_glue_bwd_params_t *p, const char **kernel);
+int zigma_linear_wgrad_plan(const zigma_linear_wgrad_params_t *p, const char **kernel);
 
 /* ------------------------------------------------------------------------------------------ */
 const char *zigma_strerror(int status);

@@ -1117,3 +1117,161 @@ def test_linear_ws_work_partition_covers_every_tile_once(m, n, linear_plan):
             seen[(panel, t)] = block
     assert len(seen) == panels * (m // 64)
     assert max(counts) - min(counts) <= 1
+
+
+_OUTER_PLAN_DRIVER = r"""
+#include "outer_plan.h"
+#include "attn_plan.h"
+#include "wgrad_plan.h"
+using namespace zigma;
+static int outer(const OuterPlan &s, int *f, const char **kernel) {
+    f[0] = s.status; f[1] = s.gx; f[2] = s.gy; f[3] = 1; f[4] = s.block; f[5] = int(s.lds); f[6] = s.inst; f[7] = s.silu;
+    *kernel = s.kernel;
+    return s.status;
+}
+static int attn(const AttnPlan &s, int *f, const char **kernel) {
+    f[0] = s.status; f[1] = s.gx; f[2] = s.gy; f[3] = s.gz; f[4] = s.block; f[5] = 0; f[6] = s.nkb; f[7] = s.masked; f[8] = s.tiles; f[9] = s.chunks; f[10] = s.has_r2;
+    *kernel = s.kernel;
+    return s.status;
+}
+extern "C" int plan_pe(const zigma_patch_embed_params_t *p, int *f, const char **k) { return outer(plan_patch_embed(*p), f, k); }
+extern "C" int plan_te(const zigma_timestep_embed_params_t *p, int *f, const char **k) { return outer(plan_timestep_embed(*p), f, k); }
+extern "C" int plan_sk(const zigma_skinny_params_t *p, int *f, const char **k) { return outer(plan_skinny_linear(*p), f, k); }
+extern "C" int plan_fl(const zigma_final_layer_params_t *p, int *f, const char **k) { return outer(plan_final_layer(*p), f, k); }
+extern "C" int plan_cfg(const zigma_final_layer_cfg_params_t *p, int *f, const char **k) { return outer(plan_final_layer_cfg(*p), f, k); }
+extern "C" int plan_xa(const zigma_xattn_params_t *p, int *f, const char **k) { return attn(plan_cross_attn(*p), f, k); }
+extern "C" int plan_xb(const zigma_xattn_bwd_params_t *p, int *f, const char **k) { return attn(plan_cross_attn_bwd(*p), f, k); }
+extern "C" int plan_gb(const zigma_glue_bwd_params_t *p, int *f, const char **k) { return attn(plan_scale_reduce_bwd(*p), f, k); }
+extern "C" int plan_wg(const zigma_linear_wgrad_params_t *p, int *f, const char **kernel) {
+    const WgradPlan s = plan_wgrad(*p);
+    f[0] = s.status; f[1] = s.gx; f[2] = s.gy; f[3] = 1; f[4] = s.block; f[5] = int(s.need); f[6] = s.bk; f[7] = s.slabs; f[8] = int(s.slab_rows); f[9] = s.n_tiles;
+    *kernel = s.kernel;
+    return s.status;
+}
+extern "C" int chunks(int seqlen) { return attn_bwd_chunks(seqlen); }
+"""
+_OUTER_FIELDS = ("status", "gx", "gy", "gz", "block", "bytes", "inst", "switch", "tiles", "chunks", "has_r2")       # (inst / switch: K | NP | k / 32, SiLU; NKB, masked; bk, slabs)
+
+
+@pytest.fixture(scope="module")
+def outer_plan():
+    """the nine plans of zigma_amd/csrc/outer_plan.h, attn_plan.h and wgrad_plan.h compiled on their own with g++ (no HIP): plan(params) -> status, grid,
+    block, LDS / workspace bytes, switches, kernel, by the type of the parameter block"""
+    from zigma_amd import _lib
+    L = _compile_plan(_OUTER_PLAN_DRIVER)
+    by_type = {t: _plan_caller(L, t, _OUTER_FIELDS, fn) for t, fn in (
+        (_lib.PatchEmbedParams, "plan_pe"), (_lib.TimestepEmbedParams, "plan_te"), (_lib.SkinnyParams, "plan_sk"), (_lib.FinalLayerParams, "plan_fl"),
+        (_lib.FinalLayerCfgParams, "plan_cfg"), (_lib.XAttnParams, "plan_xa"), (_lib.XAttnBwdParams, "plan_xb"), (_lib.GlueBwdParams, "plan_gb"),
+        (_lib.LinearWgradParams, "plan_wg"))}
+    plan = lambda P: by_type[type(P)](P)
+    plan.chunks = L.chunks
+    return plan
+
+
+def test_outer_plan_case_table(outer_plan, libpath):
+    """the nine plans (compiled) on the parameter block the product's builders fill for every case of the table: status, last kernel; and the built
+    library's host-only queries (no device here) answer the same.  Every case in ONE test (the table has 212 of them): all that differ are reported
+    together; tests/test_gpu_outer_plan_query.py runs them one by one."""
+    import outer_plan_cases as oc
+    from zigma_amd import _lib
+    wrong = {}
+    for name, (_, _, want) in oc.CASES.items():
+        fn, P, _ = oc.block(name, "cpu")
+        got = outer_plan(P)
+        if not (got["status"], got["kernel"]) == tuple(want) == _lib.plan(fn, P):
+            wrong[name] = (got["status"], got["kernel"], _lib.plan(fn, P), tuple(want))
+    assert not wrong, wrong
+    assert {c[0] for c in oc.CASES.values()} == set(oc.ENTRY) and len(oc.ENTRY) == 9
+
+
+def test_outer_plan_geometry(outer_plan):
+    """grid, block, dynamic LDS / workspace bytes and template switches of the serving leaves against the closed forms of the kernels' headers"""
+    import outer_plan_cases as oc
+
+    def geometry(name, *fields):
+        got = outer_plan(oc.block(name, "cpu")[1])
+        return tuple(got[f] for f in fields)
+    pe = ("gx", "gy", "block", "bytes", "inst")
+    assert [geometry(f"pe_served_{k}", *pe) for k in ("K16", "K3", "K4_no_bias_no_pos", "K12", "K8_any", "weight_64KB")] == [
+        (1, 2, 256, 16 * 64 * 4, 16), (4, 2, 256, 3 * 64 * 4, 3), (4, 2, 256, 4 * 64 * 4, 4), (1, 2, 256, 12 * 64 * 4, 12), (1, 2, 256, 8 * 64 * 4, 0),
+        (1, 2, 256, 65536, 0)]
+    # 4096 tokens = 256 workgroups of 16 tokens at most: 1024 / 64 / 16 per sample below 8 / below 64 / from 64 samples
+    assert [geometry(f"pe_served_batch_{b}", "gx", "gy") for b in (7, 8, 63, 64)] == [(256, 7), (64, 8), (64, 63), (16, 64)]
+    assert geometry("te_served", "gx", "block") == (1, 256) and geometry("te_served_257_pairs", "gx", "block") == (2, 256)
+    sk = ("gx", "block", "bytes", "inst", "switch")
+    assert geometry("sk_served_k128_m1", *sk) == (1, 512, 64 * 136 * 2, 4, 0) and geometry("sk_served_k128_m64_silu", *sk) == (1, 512, 64 * 136 * 2, 4, 1)
+    assert geometry("sk_served_k1024_m1_silu_no_bias", *sk) == (1, 512, 64 * 1032 * 2, 32, 1) and geometry("sk_served_k1024_m64", *sk) == (1, 512, 64 * 1032 * 2, 32, 0)
+    assert geometry("sk_served_out_plus_8_bytes_n_4112", "gx") == (33,)
+    for entry, rows in (("fl", 5), ("cfg", 8)):
+        got = [geometry(f"{entry}_served_cols_{c}_n_out_{n}", "gx", "block", "bytes", "inst") for c, n in ((8, 1), (640, 16), (648, 3), (1024, 1), (1032, 16), (2048, 16))]
+        assert got == [(1, 256, 8 * 1 * 2, 5), (1, 256, 640 * 16 * 2, 5), (1, 256, 648 * 3 * 2, 8), (1, 256, 1024 * 2, 8), (1, 256, 1032 * 16 * 2, 16),
+                       (1, 256, 2048 * 16 * 2, 16)], (entry, rows)
+    assert geometry("fl_served_no_bias_17_rows", "gx") == (2,)
+    xa = ("gx", "gy", "gz", "block", "inst", "switch", "tiles")
+    assert [geometry(f"xa_served_n_ctx_{n}", *xa) for n in (1, 64, 65, 80, 81, 112, 113, 128)] == [
+        (1, 2, 2, 256, nkb, masked, 4) for nkb, masked in ((5, 1), (5, 1), (5, 0), (5, 0), (8, 1), (8, 1), (8, 0), (8, 0))]
+    assert geometry("xa_served_f16_511_tokens", *xa) == (2, 2, 1, 256, 5, 0, 4) and geometry("xa_served_512_tokens_kv_halves", *xa) == (1, 2, 1, 256, 5, 0, 8)
+    xb = ("gx", "gy", "gz", "block", "inst", "tiles", "chunks")
+    assert [geometry(f"xb_served_n_ctx_{n}", *xb) for n in (1, 80, 81, 128)] == [(1, 2, 2, 256, nkb, 4, 1) for nkb in (5, 5, 8, 8)]
+    assert geometry("xb_served_511_tokens", *xb) == (2, 2, 1, 256, 5, 4, 2) and geometry("xb_served_513_tokens_kv_halves", *xb) == (2, 2, 1, 256, 5, 8, 2)
+    gb = ("gx", "block", "has_r2")
+    assert geometry("gb_served_cols_128_both_sums", *gb) == (2, 256, 1) and geometry("gb_served_cols_128_one_sum_no_out", *gb) == (2, 256, 0)
+    assert geometry("gb_served_cols_8192_both_sums", *gb) == (1, 256, 1) and geometry("gb_served_cols_8192_one_sum_s_a_third_of_its_rows", *gb) == (1, 256, 0)
+    wg = ("gx", "gy", "block", "bytes", "inst", "switch", "tiles", "chunks")      # tiles, slabs, threads, workspace bytes, bk, S, slab_rows, n_tiles
+    assert geometry("wg_served_k64_m511", *wg) == (1, 1, 256, 0, 64, 1, 512, 1) and geometry("wg_served_k72_m512", *wg) == (1, 1, 256, 0, 128, 1, 512, 1)
+    assert geometry("wg_served_k64_m1024_two_slabs", *wg) == (1, 2, 256, 2 * 16 * 64 * 4, 64, 2, 512, 1)
+    assert geometry("wg_served_k72_m1024_f16", *wg) == (1, 2, 256, 2 * 16 * 72 * 4, 128, 2, 512, 1)
+    assert geometry("wg_served_forced_3_slabs_fp32_out", *wg) == (1, 3, 256, 3 * 16 * 64 * 4, 64, 3, 64, 1)
+    assert geometry("wg_served_fp32_out_pitch_68_x_a_column_view", *wg) == (1, 1, 256, 0, 128, 1, 64, 1)
+
+
+def test_outer_predicates_agree_with_the_plans_and_the_parent_commit(outer_plan, libpath):
+    """each of the nine predicates over its sweep (tests/outer_predicate_cases.py): a yes is served by the compiled plan with the expected kernel, on the
+    block the product's builder fills; a no that the plan would serve is explained by a clause Python keeps for itself; every clause and both verdicts are
+    seen.  The answers are the ones recorded on the parent commit, but for the listed exceptions (a yes of the parent to a block the library does not
+    launch).  That allow-list is small: at most 2 % of the recorded points, and it is exactly the points where the parent's hand-written predicates said
+    yes to a block the compiled plans do not launch.  All nine in ONE test, like the 551 routes of test_linear_route_cases.py."""
+    import importlib
+    import outer_predicate_cases as pc
+    total = unserved = 0
+    for which, (module, _, builder, _, sweep) in pc.SWEEPS.items():
+        builder = getattr(importlib.import_module("zigma_amd." + module), builder)
+        got, recorded = pc.answers(which), "".join(pc.RECORDED[which])
+        points, seen, clauses = list(sweep()), set(), set()
+        assert len(points) == len(got) == len(recorded), which
+        total += len(points)
+        for (point, args, kwargs, policy, kernels), eligible, was in zip(points, got, recorded):
+            a, k = pc.block_args(which, args, kwargs)
+            pl = outer_plan(builder(*a, **k))
+            _sweep_verdict(eligible, pl, kernels, policy, (which, point), seen)
+            clauses |= set(policy)
+            unserved += was == "1" and pl["kernel"] is None
+            if eligible != (was == "1"):
+                assert was == "1" and (which, point) in pc.EXCEPTIONS and pl["kernel"] is None, (which, point, "the recorded answer", was, "now", eligible, pl)
+            else:
+                assert (which, point) not in pc.EXCEPTIONS, (which, point, "a listed exception that is none")
+        assert seen == {True, False} | clauses, (which, seen, clauses)
+    assert {w for w, _ in pc.EXCEPTIONS} <= set(pc.SWEEPS)
+    assert unserved == len(pc.EXCEPTIONS) <= pc.MAX_EXCEPTIONS * total, (unserved, len(pc.EXCEPTIONS), total)
+
+
+def test_chunks_and_workspace_bytes_answer_as_the_plans_do(outer_plan, libpath):
+    """zigma_cross_attn_bwd_chunks and zigma_linear_wgrad_workspace_bytes are the fields of plan_cross_attn_bwd() / plan_wgrad()"""
+    import outer_plan_cases as oc
+    from zigma_amd import _lib
+    L = _lib.lib()
+    for seqlen in (-1, 0, 1, 255, 256, 257, 511, 512, 513, 1024, 1025, 65536):
+        assert L.zigma_cross_attn_bwd_chunks(seqlen) == outer_plan.chunks(seqlen) == (0 if seqlen <= 0 else -(-seqlen // (256 if seqlen < 512 else 512)))
+    for name in (n for n, c in oc.CASES.items() if c[0] == "cross_attn_bwd" and c[2].kernel):
+        P = oc.block(name, "cpu")[1]
+        assert outer_plan(P)["chunks"] == P.chunks == L.zigma_cross_attn_bwd_chunks(P.seqlen)
+    for name in (n for n, c in oc.CASES.items() if c[0] == "linear_wgrad"):
+        P = oc.block(name, "cpu")[1]
+        pl = outer_plan(P)
+        assert L.zigma_linear_wgrad_workspace_bytes(ctypes.byref(P)) == pl["bytes"] == (pl["switch"] * P.n * P.k * 4 if pl["switch"] > 1 else 0), name
+    for m, n, k, slabs in ((65536, 2560, 640, 0), (65536, 72, 1280, 0), (4096, 640, 1280, 0), (512, 8, 8, 0), (100, 8192, 8192, 7), (1, 8, 8, 4096)):
+        P = _lib.LinearWgradParams()
+        P.m, P.n, P.k, P.slabs, P.dtype, P.out_dtype = m, n, k, slabs, _lib.BF16, _lib.BF16          # (no operands: the size is asked before they exist)
+        pl = outer_plan(P)
+        assert pl["status"] == -1 and L.zigma_linear_wgrad_workspace_bytes(ctypes.byref(P)) == pl["bytes"] == (pl["switch"] * n * k * 4 if pl["switch"] > 1 else 0)
+        assert pl["switch"] == (slabs or max(1, min(64, m // 512, -(-512 // (-(-n // 128) * -(-k // (64 if k <= 64 else 128)))))))

@@ -249,7 +249,9 @@ EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", 
            "zigma_cross_attn_bwd", "zigma_cross_attn_bwd_chunks", "zigma_patch_embed_fwd", "zigma_timestep_embed_fwd", "zigma_final_layer_fwd",
            "zigma_final_layer_cfg_fwd", "zigma_skinny_linear_fwd", "zigma_calib_launch", "zigma_abi_version", "zigma_last_kernel",
            "zigma_selective_scan_fwd_plan", "zigma_causal_conv1d_fwd_plan", "zigma_conv_x_proj_fwd_plan", "zigma_x_proj_fwd_plan",
-           "zigma_dt_proj_softplus_fwd_plan", "zigma_linear_fwd_plan", "zigma_norm_linear_fwd_plan", "zigma_linear_f32_split_plan")
+           "zigma_dt_proj_softplus_fwd_plan", "zigma_linear_fwd_plan", "zigma_norm_linear_fwd_plan", "zigma_linear_f32_split_plan",
+           "zigma_patch_embed_fwd_plan", "zigma_timestep_embed_fwd_plan", "zigma_skinny_linear_fwd_plan", "zigma_final_layer_fwd_plan", "zigma_final_layer_cfg_fwd_plan",
+           "zigma_cross_attn_fwd_plan", "zigma_cross_attn_bwd_plan", "zigma_scale_reduce_bwd_plan", "zigma_linear_wgrad_plan")
 
 _lib = None
 
@@ -284,7 +286,10 @@ def lib():
             fn.restype = C.c_int64
         for name, st in (("zigma_selective_scan_fwd", ScanParams), ("zigma_causal_conv1d_fwd", ConvParams), ("zigma_conv_x_proj_fwd", ConvXProjParams),
                          ("zigma_x_proj_fwd", XProjParams), ("zigma_dt_proj_softplus_fwd", DtProjParams), ("zigma_linear_fwd", LinearParams),
-                         ("zigma_norm_linear_fwd", NormLinearParams), ("zigma_linear_f32_split", LinearSplitParams)):
+                         ("zigma_norm_linear_fwd", NormLinearParams), ("zigma_linear_f32_split", LinearSplitParams),
+                         ("zigma_patch_embed_fwd", PatchEmbedParams), ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_skinny_linear_fwd", SkinnyParams),
+                         ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_final_layer_cfg_fwd", FinalLayerCfgParams), ("zigma_cross_attn_fwd", XAttnParams),
+                         ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_linear_wgrad", LinearWgradParams)):
             fn = getattr(L, name + "_plan")
             fn.argtypes = [C.POINTER(st), C.POINTER(C.c_char_p)]
             fn.restype = C.c_int
@@ -407,8 +412,9 @@ def plan(fn_name, params):
     """Ask the library what the entry point `fn_name` would do with this parameter block -> (status, kernel name or None): the status the launch
     would return and what zigma_last_kernel() would report after it (None: a refusal or an empty call).  The five forward entry points of the Mamba
     inner answer (plan_scan() of csrc/scan_plan.h, the plans of csrc/front_plan.h) and the three of the dense projections (plan_linear() and
-    plan_linear_split() of csrc/linear_plan.h, plan_norm_linear() of csrc/norm_linear_plan.h).  Host only: nothing is launched or dereferenced, so the block
-    may describe tensors that are yet to be allocated."""
+    plan_linear_split() of csrc/linear_plan.h, plan_norm_linear() of csrc/norm_linear_plan.h), the operators around the blocks (csrc/outer_plan.h),
+    cross-attention in both directions and the glue backward (csrc/attn_plan.h) and the weight gradient (csrc/wgrad_plan.h).  Host only: nothing is launched or
+    dereferenced, so the block may describe tensors that are yet to be allocated."""
     fn = _PLAN_FNS.get(fn_name)
     if fn is None:
         fn = _PLAN_FNS[fn_name] = getattr(lib(), fn_name + "_plan")
@@ -416,6 +422,12 @@ def plan(fn_name, params):
     rc = fn(C.byref(params), C.byref(kernel))
     name = kernel.value
     return rc, name.decode() if name else None
+
+
+def served(fn_name, params):
+    """the entry point would launch a kernel for this block (not a refusal, not an empty call)"""
+    status, kernel = plan(fn_name, params)
+    return status == 0 and kernel is not None
 
 
 TRACE = None        # tests / tools: set to a list to receive (entry point, kernel that served it, parameter block) per call

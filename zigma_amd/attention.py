@@ -5,43 +5,88 @@ for the shapes ZigMa produces (8 heads x 64, 77 text tokens).  `cross_attn` is t
 autograd form for the training path: forward and backward are both hand-written HIP kernels (zigma_cross_attn_bwd recomputes the
 probabilities: with 77 keys they are 80 MB per layer, recomputing them on the matrix cores is cheaper than storing them and than any
 flash machinery) — torch's fused SDPA is an AOT-Triton kernel on ROCm, which the north star rules out.
-Operands outside the kernels' limits (forward: bf16 or fp16, backward: bf16; head_dim 64, n_ctx <= 128, 16-byte aligned rows) take the same math in plain torch ops.
+Operands outside the kernels' limits take the same math in plain torch ops.  The limits are the plans of csrc/attn_plan.h: cross_attn_eligible and
+cross_attn_bwd_eligible build the parameter block the launch would get and ask the library; Python keeps what a block cannot say.
 """
 import torch
 
 from . import _lib
 
-def cross_attn_eligible(q, k, v, heads):
-    if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
+def _xattn_operands(q, k, v, heads):
+    """what a block cannot say: (B, L, C) / (B, n_ctx, C) operands of one dtype with C split into `heads` heads, unit channel strides"""
+    if not (q.dim() == 3 and k.dim() == 3 and k.dtype == q.dtype and v.dtype == q.dtype and tuple(v.shape) == tuple(k.shape)):
         return False
-    if q.dim() != 3 or k.dim() != 3 or v.shape != k.shape or q.shape[2] != heads * 64 or k.shape[2] != heads * 64:
+    if q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2] or q.shape[2] != heads * (q.shape[2] // max(heads, 1)):
         return False
-    if k.shape[1] > 128 or k.shape[1] < 1 or q.shape[0] != k.shape[0] or q.shape[0] > 65535 or heads > 65535:      # (grid dims of the kernels)
-        return False
-    ok = lambda t: t.stride(2) == 1 and t.stride(1) % 8 == 0 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
-    return ok(q) and ok(k) and ok(v)
+    return q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
 
 
-def cross_attn_bwd_eligible(q, k, v, heads):
-    """limits of zigma_cross_attn_bwd: the forward's, bf16 only (the backward kernel has no fp16 form)"""
-    return q.dtype == torch.bfloat16 and cross_attn_eligible(q, k, v, heads)
-
-
-def cross_attn(q, k, v, heads, scale=None):
-    """q: (B, L, H*64); k, v: (B, n_ctx, H*64) (row-strided views are fine) -> (B, L, H*64)."""
-    dev = _lib.require_device(q, k, v)
-    if not cross_attn_eligible(q, k, v, heads):
-        raise RuntimeError("cross_attn: needs bf16 or fp16 (B, L, H*64) / (B, n_ctx <= 128, H*64) operands with 16-byte aligned rows")
-    Bsz, L, C = q.shape
-    out = torch.empty(Bsz, L, C, device=q.device, dtype=q.dtype)
-    P = _lib.XAttnParams()
-    P.batch, P.seqlen, P.n_ctx, P.heads, P.head_dim = Bsz, L, k.shape[1], heads, 64
-    P.dtype, P.flags, P.scale = _lib.dtype_id(q), 0, float(64 ** -0.5 if scale is None else scale)
-    for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
+def _xattn_fill(P, q, k, v, heads, scale, rows):
+    """the fields the forward and backward blocks share; rows: (field prefix, tensor) of the row-strided operands"""
+    P.batch, P.seqlen, P.n_ctx, P.heads, P.head_dim = q.shape[0], q.shape[1], k.shape[1], heads, q.shape[2] // max(heads, 1)
+    P.dtype, P.flags, P.scale = _lib.dtype_id(q), 0, float(max(P.head_dim, 1) ** -0.5 if scale is None else scale)
+    for name, t in rows:
         setattr(P, name + "_batch_stride", t.stride(0))
         setattr(P, name + "_row_stride", t.stride(1))
-    P.q, P.k, P.v, P.out = _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out)
-    _lib.call("zigma_cross_attn_fwd", P, dev)
+    P.q, P.k, P.v = _lib.ptr(q), _lib.ptr(k), _lib.ptr(v)
+    return P
+
+
+def cross_attn_block(q, k, v, heads, scale=None, out=None):
+    """The parameter block of zigma_cross_attn_fwd: q (B, L, H * d), k / v (B, n_ctx, H * d) (row-strided views are fine), out (B, L, H * d) (None: fresh
+    contiguous rows, a placeholder address — a block to ask about).  Reads shapes, strides, dtypes and addresses only."""
+    if out is None:
+        out = _lib.Desc.fresh(q, tuple(q.shape), 1)
+    P = _xattn_fill(_lib.XAttnParams(), q, k, v, heads, scale, (("q", q), ("k", k), ("v", v), ("o", out)))
+    P.out = _lib.ptr(out)
+    return P
+
+
+def cross_attn_eligible(q, k, v, heads, scale=None):
+    """zigma_cross_attn_fwd takes these tensors: what plan_cross_attn() (csrc/attn_plan.h) serves, asked through the library, and what the block cannot
+    say.  Yes is the block that was asked about: cross_attn(..., block=) launches it."""
+    if not (q.is_cuda and q.dtype in _lib._DT and _xattn_operands(q, k, v, heads)):
+        return False
+    P = cross_attn_block(q, k, v, heads, scale)
+    return _lib.served("zigma_cross_attn_fwd", P) and P
+
+
+def cross_attn_bwd_block(q, k, v, dout, heads, scale=None, dq=None, part=None):
+    """The parameter block of zigma_cross_attn_bwd: the forward's operands, dout and dq (B, L, H * d) rows, part (2, chunks, B, n_ctx, H * d) fp32 partial
+    sums of dK and dV with chunks asked of the library (dq / part None: fresh, placeholder addresses)"""
+    chunks = _lib.lib().zigma_cross_attn_bwd_chunks(q.shape[1])
+    if dq is None:
+        dq = _lib.Desc.fresh(q, tuple(q.shape), 1)
+    if part is None:
+        part = _lib.Desc.fresh(q, (2, max(chunks, 1), k.shape[0], k.shape[1], k.shape[2]), 2, torch.float32)
+    P = _xattn_fill(_lib.XAttnBwdParams(), q, k, v, heads, scale, (("q", q), ("k", k), ("v", v), ("do", dout), ("dq", dq)))
+    P.chunks, P.dout, P.dq = chunks, _lib.ptr(dout), _lib.ptr(dq)
+    P.dk_part, P.dv_part = _lib.ptr(part), _lib.ptr(part) + part.stride(0) * 4
+    return P
+
+
+def cross_attn_bwd_eligible(q, k, v, heads, dout=None):
+    """zigma_cross_attn_bwd takes these tensors (dout None: a gradient yet to come, contiguous like q): plan_cross_attn_bwd(), asked through the library"""
+    if not (q.is_cuda and q.dtype in _lib._DT and _xattn_operands(q, k, v, heads)):
+        return False
+    if dout is None:
+        dout = _lib.Desc.fresh(q, tuple(q.shape), 3)
+    elif not (dout.dtype == q.dtype and tuple(dout.shape) == tuple(q.shape) and dout.stride(2) == 1):
+        return False
+    return _lib.served("zigma_cross_attn_bwd", cross_attn_bwd_block(q, k, v, dout, heads))
+
+
+def cross_attn(q, k, v, heads, scale=None, block=None):
+    """q: (B, L, H*d); k, v: (B, n_ctx, H*d) (row-strided views are fine) -> (B, L, H*d).  block: what cross_attn_eligible returned for these operands
+    and this scale."""
+    dev = _lib.require_device(q, k, v)
+    if block is None:
+        if not _xattn_operands(q, k, v, heads):
+            raise RuntimeError("cross_attn: needs (B, L, H*d) / (B, n_ctx, H*d) operands of one dtype with unit channel strides")
+        block = cross_attn_block(q, k, v, heads, scale)
+    out = torch.empty(tuple(q.shape), device=q.device, dtype=q.dtype)
+    block.out = _lib.ptr(out)
+    _lib.call("zigma_cross_attn_fwd", block, dev)
     return out
 
 
@@ -109,24 +154,14 @@ def cross_attn_bwd(q, k, v, dout, heads, scale=None):
     """gradients of cross_attn(q, k, v) w.r.t. q, k, v given dout (zigma_cross_attn_bwd: the probabilities are recomputed, nothing of
     the forward is needed).  Returns (dq, dk, dv) in the operand dtype; dk / dv are accumulated in fp32."""
     dev = _lib.require_device(q, k, v, dout)
-    if not (cross_attn_bwd_eligible(q, k, v, heads) and cross_attn_bwd_eligible(dout, k, v, heads) and dout.shape == q.shape):
-        raise RuntimeError("cross_attn_bwd: needs bf16 (B, L, H*64) / (B, n_ctx <= 128, H*64) operands with 16-byte aligned rows")
-    Bsz, L, C = q.shape
-    NC = k.shape[1]
-    dq = torch.empty(Bsz, L, C, device=q.device, dtype=q.dtype)
-    chunks = _lib.lib().zigma_cross_attn_bwd_chunks(L)
-    part = torch.empty(2, max(chunks, 1), Bsz, NC, C, device=q.device, dtype=torch.float32)
-    P = _lib.XAttnBwdParams()
-    P.batch, P.seqlen, P.n_ctx, P.heads, P.head_dim = Bsz, L, NC, heads, 64
-    P.dtype, P.flags, P.scale, P.chunks = _lib.dtype_id(q), 0, float(64 ** -0.5 if scale is None else scale), chunks
-    for name, t in (("q", q), ("k", k), ("v", v), ("do", dout), ("dq", dq)):
-        setattr(P, name + "_batch_stride", t.stride(0))
-        setattr(P, name + "_row_stride", t.stride(1))
-    P.q, P.k, P.v, P.dout, P.dq = _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(dout), _lib.ptr(dq)
-    P.dk_part, P.dv_part = _lib.ptr(part[0]), _lib.ptr(part[1])
-    if L == 0 or Bsz == 0:
+    if not (_xattn_operands(q, k, v, heads) and dout.dtype == q.dtype and dout.shape == q.shape and dout.stride(2) == 1):
+        raise RuntimeError("cross_attn_bwd: needs (B, L, H*d) / (B, n_ctx, H*d) operands of one dtype with unit channel strides")
+    dq = torch.empty(tuple(q.shape), device=q.device, dtype=q.dtype)
+    chunks = _lib.lib().zigma_cross_attn_bwd_chunks(q.shape[1])
+    part = torch.empty(2, max(chunks, 1), *k.shape, device=q.device, dtype=torch.float32)
+    if q.shape[1] == 0 or q.shape[0] == 0:
         part.zero_()
-    _lib.call("zigma_cross_attn_bwd", P, dev)
+    _lib.call("zigma_cross_attn_bwd", cross_attn_bwd_block(q, k, v, dout, heads, scale, dq, part), dev)
     dkv = (part[:, 0] if chunks <= 1 else part.sum(1)).to(q.dtype)
     return dq, dkv[0], dkv[1]
 
@@ -164,11 +199,11 @@ class CrossAttnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, do):
         q, k, v = ctx.saved_tensors
-        do = do if do.stride(-1) == 1 and do.stride(1) % 8 == 0 and do.stride(0) % 8 == 0 and do.data_ptr() % 16 == 0 else do.contiguous()
+        do = do if cross_attn_bwd_eligible(q, k, v, ctx.heads, do) else do.contiguous()
         fn = cross_attn_bwd if BWD_KERNEL else cross_attn_bwd_math
         return (*fn(q, k, v, do, ctx.heads, ctx.scale), None, None)
 
 
 def cross_attn_train(q, k, v, heads, scale=None):
     """differentiable cross_attn (the training path)"""
-    return CrossAttnFn.apply(q, k, v, heads, float(64 ** -0.5 if scale is None else scale))
+    return CrossAttnFn.apply(q, k, v, heads, float((q.shape[2] // heads) ** -0.5 if scale is None else scale))

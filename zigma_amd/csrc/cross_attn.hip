@@ -13,16 +13,12 @@
 //   O^T / rowsum -> per-wave LDS tile (8-byte pieces) -> 16-byte stores, 128 contiguous bytes per token
 // HBM-bound by construction: reads Q once, writes O once (2 x 67 MB at B=64, L=1024); K/V come from L2.
 // bf16 or fp16 (template parameter T: both MFMAs, the P and O packs; P = exp2(.) <= 1 is in fp16's range), head_dim 64, n_ctx <= 128.
+#include "attn_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
 
-constexpr int kXaD = 64;                 // head dim
-constexpr int kXaWaves = 4, kXaTok = 16; // tokens per wave (MFMA M)
 constexpr int kXaKPitch = (kXaD + 8) * 2;   // bytes per K row in LDS (16 B skew)
-
-// 16-token tiles per wave = how many query tokens share one staging of K_h / V_h^T (20 KB): 8 (512 tokens per workgroup) where the
-// sequence has them — 35.5 us against 38.0 with 4 and 40.2 with 16 at the headline shape (tools/attn_probe.py) —, 4 for short ones
 
 // NKB 16-key blocks: n_ctx <= 16 * NKB; MASK_ALL = false: n_ctx > 16 (NKB - 1), padded keys only in the last block
 template <int NKB, bool MASK_ALL, typename T>
@@ -167,29 +163,20 @@ extern "C" int zigma_cross_attn_fwd(const zigma_xattn_params_t *pp, void *stream
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_xattn_params_t &p = *pp;
-    if (p.batch < 0 || p.seqlen < 0 || p.heads < 1 || p.n_ctx < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    // the softmax takes its maximum over the RAW scores and folds the scale into the exponent (fma(s, sc, -m * sc)): that is the
-    // maximum of the scaled scores only for a positive scale (the reference's is head_dim^-0.5)
-    if (!(p.scale > 0.f) || !(p.scale < 3.0e38f)) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
-    if (!p.q || !p.k || !p.v || !p.out) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.head_dim != kXaD || p.n_ctx > 128 || p.batch > 65535 || p.heads > 65535) return ZIGMA_ERR_SHAPE;
-    auto mis = [](const void *q, int64_t rs, int64_t bs) { return reinterpret_cast<uintptr_t>(q) % 16 != 0 || rs % 8 != 0 || bs % 8 != 0; };
-    if (mis(p.q, p.q_row_stride, p.q_batch_stride) || mis(p.k, p.k_row_stride, p.k_batch_stride) ||
-        mis(p.v, p.v_row_stride, p.v_batch_stride) || mis(p.out, p.o_row_stride, p.o_batch_stride))
-        return ZIGMA_ERR_STRIDE;
-    const int tiles = p.seqlen >= 512 ? 8 : 4;
-    const int tok_per_wg = kXaTok * kXaWaves * tiles;
-    dim3 grid((p.seqlen + tok_per_wg - 1) / tok_per_wg, p.heads, p.batch), block(64 * kXaWaves);
+    const AttnPlan plan = plan_cross_attn(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), block(plan.block);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define ZIGMA_XA(N_, M_) hipLaunchKernelGGL((cross_attn_kernel<N_, M_, T>), grid, block, 0, stream, p, tiles)
+#define ZIGMA_XA(N_, M_) hipLaunchKernelGGL((cross_attn_kernel<N_, M_, T>), grid, block, 0, stream, p, plan.tiles)
     ZIGMA_DISPATCH_16BIT(p.dtype, T, {
-        if (p.n_ctx <= 80) { if (p.n_ctx > 64) ZIGMA_XA(5, false); else ZIGMA_XA(5, true); }
-        else { if (p.n_ctx > 112) ZIGMA_XA(8, false); else ZIGMA_XA(8, true); }
+        if (plan.nkb == 5) { if (!plan.masked) ZIGMA_XA(5, false); else ZIGMA_XA(5, true); }      // (in this order: the kernels are emitted in the order of use)
+        else { if (!plan.masked) ZIGMA_XA(8, false); else ZIGMA_XA(8, true); }
     })
 #undef ZIGMA_XA
-    set_last_kernel("cross_attn_mfma");
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+extern "C" int zigma_cross_attn_fwd_plan(const zigma_xattn_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_attn(plan_cross_attn(*pp), kernel) : ZIGMA_ERR_NULL;
 }

@@ -17,13 +17,13 @@
 // order through LDS and written as fp32 partials per (chunk of tokens, sample): the caller adds the chunks (deterministic, no atomics).
 // HBM traffic: reads Q and dO once, writes dQ once (3 x 67 MB at B=64, L=1024, 8 heads).
 // bf16 only, head_dim 64, n_ctx <= 128.
+#include "attn_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kXbD = 64, kXbWaves = 4, kXbTok = 16;
 constexpr int kXbRowPitch = (kXbD + 8) * 2;      // bytes per K / V row and per dQ-tile row in LDS (16 B skew)
 constexpr int kXbRedPitch = (kXbD + 4) * 4;      // bytes per key row of the fp32 dK / dV reduction tiles
 
@@ -268,44 +268,28 @@ __global__ __launch_bounds__(64 * kXbWaves) __attribute__((amdgpu_waves_per_eu(W
     }
 }
 
-static int xb_tiles(int seqlen) { return seqlen >= 512 ? 8 : 4; }
-
 }  // namespace zigma
 
 using namespace zigma;
 
-extern "C" int zigma_cross_attn_bwd_chunks(int seqlen) {
-    if (seqlen <= 0) return 0;
-    const int tok_per_wg = kXbTok * kXbWaves * xb_tiles(seqlen);
-    return (seqlen + tok_per_wg - 1) / tok_per_wg;
-}
+extern "C" int zigma_cross_attn_bwd_chunks(int seqlen) { return attn_bwd_chunks(seqlen); }
 
 extern "C" int zigma_cross_attn_bwd(const zigma_xattn_bwd_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_xattn_bwd_params_t &p = *pp;
-    if (p.batch < 0 || p.seqlen < 0 || p.heads < 1 || p.n_ctx < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    // the forward's domain (zigma_cross_attn_fwd takes a positive finite scale only): an inf or nan scale would come back as NaN gradients
-    if (!(p.scale > 0.f) || !(p.scale < 3.0e38f)) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.batch == 0 || p.seqlen == 0) return ZIGMA_OK;
-    if (!p.q || !p.k || !p.v || !p.dout || !p.dq || !p.dk_part || !p.dv_part) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.head_dim != kXbD || p.n_ctx > 128 || p.batch > 65535 || p.heads > 65535) return ZIGMA_ERR_SHAPE;
-    if (p.chunks != zigma_cross_attn_bwd_chunks(p.seqlen)) return ZIGMA_ERR_SHAPE;
-    auto mis = [](const void *q, int64_t rs, int64_t bs) { return reinterpret_cast<uintptr_t>(q) % 16 != 0 || rs % 8 != 0 || bs % 8 != 0; };
-    if (mis(p.q, p.q_row_stride, p.q_batch_stride) || mis(p.k, p.k_row_stride, p.k_batch_stride) ||
-        mis(p.v, p.v_row_stride, p.v_batch_stride) || mis(p.dout, p.do_row_stride, p.do_batch_stride) ||
-        mis(p.dq, p.dq_row_stride, p.dq_batch_stride) || reinterpret_cast<uintptr_t>(p.dk_part) % 16 != 0 ||
-        reinterpret_cast<uintptr_t>(p.dv_part) % 16 != 0)
-        return ZIGMA_ERR_STRIDE;
-    const int tiles = xb_tiles(p.seqlen);
-    dim3 grid(p.chunks, p.heads, p.batch), block(64 * kXbWaves);
+    const AttnPlan plan = plan_cross_attn_bwd(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx, plan.gy, plan.gz), block(plan.block);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     // measured at B=64, L=1024, 8 heads, 77 keys (tools/attn_probe.py): 2 waves per SIMD without operand prefetch 147 us, with 194 us
     // (45 spilled registers); 1 wave per SIMD 171 us without / 188 us with prefetch
-    if (p.n_ctx <= 80) hipLaunchKernelGGL((cross_attn_bwd_kernel<5, 2, false>), grid, block, 0, stream, p, tiles);
-    else hipLaunchKernelGGL((cross_attn_bwd_kernel<8, 1, false>), grid, block, 0, stream, p, tiles);
-    set_last_kernel("cross_attn_bwd_mfma");
+    if (plan.nkb == 5) hipLaunchKernelGGL((cross_attn_bwd_kernel<5, 2, false>), grid, block, 0, stream, p, plan.tiles);
+    else hipLaunchKernelGGL((cross_attn_bwd_kernel<8, 1, false>), grid, block, 0, stream, p, plan.tiles);
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+extern "C" int zigma_cross_attn_bwd_plan(const zigma_xattn_bwd_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_attn(plan_cross_attn_bwd(*pp), kernel) : ZIGMA_ERR_NULL;
 }

@@ -7,6 +7,7 @@
 // None of them is GEMM-shaped (K = 3 input channels; 3 output channels): as library GEMMs + ATen elementwise kernels they cost
 // 120 + 60 + 60 us of a 18.9 ms forward in ~20 launches of ~5 us minimum each; here each is ONE HBM-bound pass.
 // Rounding points follow the reference's bf16 evaluation: conv + bias -> bf16, + pos -> bf16; LayerNorm -> bf16, linear + bias -> bf16.
+#include "outer_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
@@ -134,8 +135,6 @@ __global__ void timestep_embed_kernel(const zigma_timestep_embed_params_t p) {
 // 16 lanes per row (4 rows per wave, 16 per workgroup): the row (E <= 2048 features, 8 per lane and pass of 128) stays in registers for the
 // two statistics passes and the n_out dot products; sums over the 16 lanes are 4 cross-lane steps; w sits in LDS as bf16 and the 4 rows of
 // a wave read the same pieces (broadcast)
-constexpr int kFlMaxPass = 16;      // E <= 16 lanes * 8 * 16
-
 // one row on its 16 lanes: statistics, the bf16-rounded LayerNorm output, the n_out dot products -> lane o of the 16 holds sum_e w[o, e] y[e] (fp32, no bias).
 // Shared by final_layer_kernel and final_layer_cfg_kernel: the same operations in the same order, so both give the same bits per row.
 // YOUT: also store the bf16 LayerNorm row to yrow (the guided kernel's test hook).
@@ -263,32 +262,19 @@ extern "C" int zigma_patch_embed_fwd(const zigma_patch_embed_params_t *pp, void 
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_patch_embed_params_t &p = *pp;
-    if (p.batch < 0 || p.in_chans < 1 || p.patch < 1 || p.embed_dim < 8 || p.height < 1 || p.width < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.embed_dim % 8 != 0 || p.height % p.patch != 0 || p.width % p.patch != 0) return ZIGMA_ERR_SHAPE;
-    const int64_t K = static_cast<int64_t>(p.in_chans) * p.patch * p.patch, lds = K * p.embed_dim * 4;
-    if (lds > 65536) return ZIGMA_ERR_SHAPE;
-    if (p.batch == 0) return ZIGMA_OK;
-    if (!p.x || !p.weight || !p.out) return ZIGMA_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(p.out) % 16 != 0 || p.out_row_stride % 8 != 0 || p.out_batch_stride % 8 != 0) return ZIGMA_ERR_STRIDE;
-    if (reinterpret_cast<uintptr_t>(p.weight) % 16 != 0) return ZIGMA_ERR_STRIDE;
-    if (p.bias && reinterpret_cast<uintptr_t>(p.bias) % 16 != 0) return ZIGMA_ERR_STRIDE;
-    if (p.pos && (reinterpret_cast<uintptr_t>(p.pos) % 16 != 0 || p.pos_row_stride % 8 != 0)) return ZIGMA_ERR_STRIDE;
-    const int64_t L = static_cast<int64_t>(p.height / p.patch) * (p.width / p.patch);
-    if (L > 0x7fffffff || p.batch > 65535) return ZIGMA_ERR_SHAPE;
-    const int64_t want = (L + 15) / 16;
-    const int64_t per = p.batch >= 64 ? 16 : (p.batch >= 8 ? 64 : 1024);      // ~1024+ workgroups, each staging the weight once for several tokens
-    const dim3 grid(static_cast<unsigned>(want < per ? want : per), static_cast<unsigned>(p.batch));
+    const OuterPlan plan = plan_patch_embed(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx, plan.gy);
+    const size_t lds = static_cast<size_t>(plan.lds);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    switch (K) {
-        case 3: hipLaunchKernelGGL(patch_embed_kernel<3>, grid, dim3(256), static_cast<size_t>(lds), stream, p); break;
-        case 4: hipLaunchKernelGGL(patch_embed_kernel<4>, grid, dim3(256), static_cast<size_t>(lds), stream, p); break;
-        case 12: hipLaunchKernelGGL(patch_embed_kernel<12>, grid, dim3(256), static_cast<size_t>(lds), stream, p); break;
-        case 16: hipLaunchKernelGGL(patch_embed_kernel<16>, grid, dim3(256), static_cast<size_t>(lds), stream, p); break;
-        default: hipLaunchKernelGGL(patch_embed_kernel<0>, grid, dim3(256), static_cast<size_t>(lds), stream, p); break;
+    switch (plan.inst) {
+        case 3: hipLaunchKernelGGL(patch_embed_kernel<3>, grid, dim3(plan.block), lds, stream, p); break;
+        case 4: hipLaunchKernelGGL(patch_embed_kernel<4>, grid, dim3(plan.block), lds, stream, p); break;
+        case 12: hipLaunchKernelGGL(patch_embed_kernel<12>, grid, dim3(plan.block), lds, stream, p); break;
+        case 16: hipLaunchKernelGGL(patch_embed_kernel<16>, grid, dim3(plan.block), lds, stream, p); break;
+        default: hipLaunchKernelGGL(patch_embed_kernel<0>, grid, dim3(plan.block), lds, stream, p); break;
     }
-    set_last_kernel("patch_embed");
+    set_last_kernel(plan.kernel);
     return check_launch();
 }
 
@@ -296,37 +282,30 @@ extern "C" int zigma_timestep_embed_fwd(const zigma_timestep_embed_params_t *pp,
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_timestep_embed_params_t &p = *pp;
-    if (p.batch < 0 || p.dim < 2) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.batch == 0) return ZIGMA_OK;
-    if (!p.t || !p.freqs || !p.out) return ZIGMA_ERR_NULL;
-    const int n = p.batch * (p.dim / 2);
-    hipLaunchKernelGGL(timestep_embed_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_), p);
-    set_last_kernel("timestep_embed");
+    const OuterPlan plan = plan_timestep_embed(p);
+    if (!plan.kernel) return plan.status;
+    hipLaunchKernelGGL(timestep_embed_kernel, dim3(plan.gx), dim3(plan.block), 0, static_cast<hipStream_t>(stream_), p);
+    set_last_kernel(plan.kernel);
     return check_launch();
 }
+
+// a final-layer plan to its instantiation: KERNEL_<5 | 8 | 16> passes of 128 features
+#define ZIGMA_FL_LAUNCH(KERNEL_)                                                                                              \
+    const dim3 grid(plan.gx), block(plan.block);                                                                              \
+    const size_t lds = static_cast<size_t>(plan.lds);                                                                         \
+    hipStream_t stream = static_cast<hipStream_t>(stream_);                                                                   \
+    if (plan.inst == 5) hipLaunchKernelGGL(KERNEL_<5>, grid, block, lds, stream, p);                                          \
+    else if (plan.inst == 8) hipLaunchKernelGGL(KERNEL_<8>, grid, block, lds, stream, p);                                     \
+    else hipLaunchKernelGGL(KERNEL_<16>, grid, block, lds, stream, p);
 
 extern "C" int zigma_final_layer_fwd(const zigma_final_layer_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_final_layer_params_t &p = *pp;
-    if (p.rows < 0 || p.cols < 8 || p.n_out < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.cols % 8 != 0 || p.cols > 128 * kFlMaxPass || p.n_out > 16) return ZIGMA_ERR_SHAPE;
-    if (p.rows == 0) return ZIGMA_OK;
-    if (!p.x || !p.weight || !p.out) return ZIGMA_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(p.x) % 16 != 0 || p.x_row_stride % 8 != 0 || reinterpret_cast<uintptr_t>(p.weight) % 16 != 0) return ZIGMA_ERR_STRIDE;
-    const int64_t want = (p.rows + 15) / 16;
-    const dim3 grid(static_cast<unsigned>(want < 4096 ? want : 4096)), block(256);
-    const size_t lds = static_cast<size_t>(p.n_out) * p.cols * 2;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int np = (p.cols + 127) / 128;
-    if (np <= 5) hipLaunchKernelGGL(final_layer_kernel<5>, grid, block, lds, stream, p);
-    else if (np <= 8) hipLaunchKernelGGL(final_layer_kernel<8>, grid, block, lds, stream, p);
-    else hipLaunchKernelGGL(final_layer_kernel<16>, grid, block, lds, stream, p);
-    set_last_kernel("final_layer");
+    const OuterPlan plan = plan_final_layer(p);
+    if (!plan.kernel) return plan.status;
+    ZIGMA_FL_LAUNCH(final_layer_kernel)
+    set_last_kernel(plan.kernel);
     return check_launch();
 }
 
@@ -334,26 +313,23 @@ extern "C" int zigma_final_layer_cfg_fwd(const zigma_final_layer_cfg_params_t *p
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_final_layer_cfg_params_t &p = *pp;
-    if (p.rows < 0 || p.cols < 8 || p.n_out < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dtype != ZIGMA_BF16 || (p.out_dtype != ZIGMA_F32 && p.out_dtype != ZIGMA_BF16)) return ZIGMA_ERR_DTYPE;
-    if (p.cols % 8 != 0 || p.cols > 128 * kFlMaxPass || p.n_out > 16) return ZIGMA_ERR_SHAPE;
-    if (p.rows_per_sample < 1 || p.tokens_per_frame < 1 || p.grid_w < 1 || p.patch < 1 || p.chans < 1) return ZIGMA_ERR_SHAPE;
-    if (static_cast<int64_t>(p.patch) * p.patch * p.chans != p.n_out) return ZIGMA_ERR_SHAPE;
-    if (p.rows % p.rows_per_sample != 0 || p.rows_per_sample % p.tokens_per_frame != 0 || p.tokens_per_frame % p.grid_w != 0) return ZIGMA_ERR_SHAPE;
-    if (p.rows == 0) return ZIGMA_OK;
-    if (!p.x_cond || !p.x_uncond || !p.weight || !p.scale || !p.out) return ZIGMA_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(p.x_cond) % 16 != 0 || reinterpret_cast<uintptr_t>(p.x_uncond) % 16 != 0 || p.x_row_stride % 8 != 0
-        || reinterpret_cast<uintptr_t>(p.weight) % 16 != 0 || reinterpret_cast<uintptr_t>(p.y_out) % 16 != 0
-        || reinterpret_cast<uintptr_t>(p.scale) % 4 != 0 || reinterpret_cast<uintptr_t>(p.out) % (p.out_dtype == ZIGMA_F32 ? 4 : 2) != 0) return ZIGMA_ERR_STRIDE;
-    const int64_t want = (p.rows + 15) / 16;
-    const dim3 grid(static_cast<unsigned>(want < 4096 ? want : 4096)), block(256);
-    const size_t lds = static_cast<size_t>(p.n_out) * p.cols * 2;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int np = (p.cols + 127) / 128;
-    if (np <= 5) hipLaunchKernelGGL(final_layer_cfg_kernel<5>, grid, block, lds, stream, p);
-    else if (np <= 8) hipLaunchKernelGGL(final_layer_cfg_kernel<8>, grid, block, lds, stream, p);
-    else hipLaunchKernelGGL(final_layer_cfg_kernel<16>, grid, block, lds, stream, p);
-    set_last_kernel("final_layer_cfg");
+    const OuterPlan plan = plan_final_layer_cfg(p);
+    if (!plan.kernel) return plan.status;
+    ZIGMA_FL_LAUNCH(final_layer_cfg_kernel)
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+#undef ZIGMA_FL_LAUNCH
+
+extern "C" int zigma_patch_embed_fwd_plan(const zigma_patch_embed_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_outer(plan_patch_embed(*pp), kernel) : ZIGMA_ERR_NULL;
+}
+extern "C" int zigma_timestep_embed_fwd_plan(const zigma_timestep_embed_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_outer(plan_timestep_embed(*pp), kernel) : ZIGMA_ERR_NULL;
+}
+extern "C" int zigma_final_layer_fwd_plan(const zigma_final_layer_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_outer(plan_final_layer(*pp), kernel) : ZIGMA_ERR_NULL;
+}
+extern "C" int zigma_final_layer_cfg_fwd_plan(const zigma_final_layer_cfg_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_outer(plan_final_layer_cfg(*pp), kernel) : ZIGMA_ERR_NULL;
 }

@@ -13,11 +13,10 @@
 //
 // One workgroup = 64 rows x all columns, walked in 128-column slabs: 16 groups of 16 lanes, a group takes 4 of the 64 rows, a lane
 // 16 bytes of the slab; the 16 groups' partial sums of a slab meet in LDS.  bf16; cols % 128 == 0; rows_per_batch % 64 == 0; 16-byte aligned rows.
+#include "attn_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
-
-constexpr int kGbRows = 64, kGbMaxIters = 64;
 
 template <bool HAS_R2>
 __global__ __launch_bounds__(256) void scale_reduce_bwd_kernel(const zigma_glue_bwd_params_t p) {
@@ -101,18 +100,16 @@ extern "C" int zigma_scale_reduce_bwd(const zigma_glue_bwd_params_t *pp, void *s
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_glue_bwd_params_t &p = *pp;
-    if (p.rows < 0 || p.cols < 1 || p.rows_per_batch < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.rows == 0) return ZIGMA_OK;
-    if (!p.dy || !p.a || !p.s || !p.r1) return ZIGMA_ERR_NULL;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.cols % 128 != 0 || p.cols > 128 * kGbMaxIters || p.rows_per_batch % kGbRows != 0 || p.rows % p.rows_per_batch != 0) return ZIGMA_ERR_SHAPE;
-    auto bad = [](const void *q, int64_t st) { return q && (reinterpret_cast<uintptr_t>(q) % 16 != 0 || st % 8 != 0); };
-    if (bad(p.dy, p.dy_row_stride) || bad(p.a, p.a_row_stride) || bad(p.out, p.out_row_stride) || bad(p.s, p.s_batch_stride)) return ZIGMA_ERR_STRIDE;
-    const dim3 grid(static_cast<unsigned>(p.rows / kGbRows)), block(256);
+    const AttnPlan plan = plan_scale_reduce_bwd(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx), block(plan.block);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (p.r2) hipLaunchKernelGGL((scale_reduce_bwd_kernel<true>), grid, block, 0, stream, p);
+    if (plan.has_r2) hipLaunchKernelGGL((scale_reduce_bwd_kernel<true>), grid, block, 0, stream, p);
     else hipLaunchKernelGGL((scale_reduce_bwd_kernel<false>), grid, block, 0, stream, p);
-    set_last_kernel("scale_reduce_bwd");
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+extern "C" int zigma_scale_reduce_bwd_plan(const zigma_glue_bwd_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_attn(plan_scale_reduce_bwd(*pp), kernel) : ZIGMA_ERR_NULL;
 }

@@ -10,11 +10,10 @@
 //   8 consecutive k), the whole strip (k / 32 loads of 16 bytes per lane) in flight per wave; B fragments = x rows from LDS (lane = sample, 8 consecutive k); 4 accumulator blocks
 //   (64 samples); bias added from a 8-byte read per lane; out[m][n0 + 4 g + r] leaves as 8-byte stores.
 // HBM-bound on the weight read.
+#include "outer_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
-
-constexpr int kSkWaves = 8;
 
 // KS: k / 32 as a compile-time constant — the whole strip of weights (KS 16-byte fragments per lane) is requested up front, no branch sits
 // between the loads and the products (with a run-time k the refill conditions made hipcc wait for ALL loads at every step: 0.5 us per k-step)
@@ -123,26 +122,17 @@ extern "C" int zigma_skinny_linear_fwd(const zigma_skinny_params_t *pp, void *st
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_skinny_params_t &p = *pp;
-    if (p.m < 0 || p.n < 0 || p.k < 0) return ZIGMA_ERR_SHAPE;
-    if (p.flags & ~1) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dtype != ZIGMA_BF16) return ZIGMA_ERR_DTYPE;
-    if (p.m > 64 || p.n % 16 != 0 || p.k % 128 != 0 || p.k > 1024) return ZIGMA_ERR_SHAPE;       // (64 x (k + 8) bf16 of LDS <= 129 KB; k / 128 instantiations)
-    if (p.m == 0 || p.n == 0) return ZIGMA_OK;
-    if (p.k == 0 || !p.x || !p.w || !p.out) return ZIGMA_ERR_NULL;
-    auto mis = [](const void *q, int64_t rs, int al) { return reinterpret_cast<uintptr_t>(q) % al != 0 || rs % (al / 2) != 0; };
-    if (mis(p.x, p.x_row_stride, 16) || mis(p.w, p.w_row_stride, 16) || mis(p.out, p.out_row_stride, 8)) return ZIGMA_ERR_STRIDE;
-    if (p.bias && reinterpret_cast<uintptr_t>(p.bias) % 8 != 0) return ZIGMA_ERR_STRIDE;
-    const int n_strips = p.n / 16;
-    const int want = (n_strips + kSkWaves - 1) / kSkWaves;
-    const dim3 grid(want < 256 ? want : 256), block(64 * kSkWaves);      // one workgroup per CU (LDS), persistent over the strips: x is staged once
-    const size_t lds = static_cast<size_t>(64) * (p.k + 8) * 2;
+    const OuterPlan plan = plan_skinny_linear(p);
+    if (!plan.kernel) return plan.status;
+    const dim3 grid(plan.gx), block(plan.block);
+    const size_t lds = static_cast<size_t>(plan.lds);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     // (more than 64 KB of dynamic LDS needs a function attribute; it applies to the CURRENT device only, so it is set per call —
     // a host-side table update, no device work — instead of once per process: a second GPU driven by the same process would
     // otherwise launch without it and fail)
 #define ZIGMA_SK_CASE(KS_)                                                                                                     \
     case KS_: {                                                                                                                \
-        const int v = p.flags & 1;                                                                                             \
+        const int v = plan.silu;                                                                                               \
         const void *fn = v ? reinterpret_cast<const void *>(skinny_linear_kernel<true, KS_>)                                   \
                            : reinterpret_cast<const void *>(skinny_linear_kernel<false, KS_>);                                 \
         if (lds > 65536 &&                                                                                                     \
@@ -152,11 +142,15 @@ extern "C" int zigma_skinny_linear_fwd(const zigma_skinny_params_t *pp, void *st
         else hipLaunchKernelGGL((skinny_linear_kernel<false, KS_>), grid, block, lds, stream, p);                              \
         break;                                                                                                                 \
     }
-    switch (p.k / 32) {
+    switch (plan.inst) {
         ZIGMA_SK_CASE(4) ZIGMA_SK_CASE(8) ZIGMA_SK_CASE(12) ZIGMA_SK_CASE(16) ZIGMA_SK_CASE(20) ZIGMA_SK_CASE(24) ZIGMA_SK_CASE(28) ZIGMA_SK_CASE(32)
         default: return ZIGMA_ERR_SHAPE;
     }
 #undef ZIGMA_SK_CASE
-    set_last_kernel("skinny_linear_mfma");
+    set_last_kernel(plan.kernel);
     return check_launch();
+}
+
+extern "C" int zigma_skinny_linear_fwd_plan(const zigma_skinny_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_outer(plan_skinny_linear(*pp), kernel) : ZIGMA_ERR_NULL;
 }

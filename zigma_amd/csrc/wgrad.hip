@@ -25,12 +25,10 @@
 //   wgrad_kernel<bf16 | f16, 128>: 94 VGPR + 64 AGPR, 40 960 B LDS, 3 waves / SIMD (3 workgroups per CU), no scratch
 //   wgrad_kernel<bf16 | f16, 64>:  84 VGPR + 32 AGPR, 32 768 B LDS, 4 waves / SIMD (4 workgroups per CU), no scratch
 //   wgrad_reduce_kernel:           14 VGPR, no LDS, 8 waves / SIMD, no scratch
+#include "wgrad_plan.h"
 #include "zigma_common.h"
 
 namespace zigma {
-
-constexpr int kWgBN = 128, kWgKT = 64, kWgThreads = 256;
-constexpr int kWgMaxSlabs = 4096;
 
 struct wgrad_args_t {
     const uint16_t *dy, *x;
@@ -175,60 +173,21 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
     }
 }
 
-// ---- host ------------------------------------------------------------------------------------------
-static inline int wgrad_bk(const zigma_linear_wgrad_params_t &p) { return p.k <= 64 ? 64 : 128; }
-static inline int64_t wgrad_tiles(const zigma_linear_wgrad_params_t &p) {
-    const int bk = wgrad_bk(p);
-    return static_cast<int64_t>((p.n + kWgBN - 1) / kWgBN) * ((p.k + bk - 1) / bk);
-}
-// S: about two workgroups per CU (256 CUs) while a slab keeps >= 512 tokens; a non-zero `slabs` forces it
-static inline int wgrad_slabs(const zigma_linear_wgrad_params_t &p) {
-    if (p.slabs > 0) return p.slabs;
-    const int64_t tiles = wgrad_tiles(p);
-    int64_t s = (512 + tiles - 1) / tiles;
-    const int64_t most = p.m / 512;
-    if (s > most) s = most;
-    if (s > 64) s = 64;
-    return s < 1 ? 1 : static_cast<int>(s);
-}
-static int wgrad_check(const zigma_linear_wgrad_params_t &p) {
-    if (p.dtype != ZIGMA_BF16 && p.dtype != ZIGMA_F16) return ZIGMA_ERR_DTYPE;
-    if (p.out_dtype != p.dtype && p.out_dtype != ZIGMA_F32) return ZIGMA_ERR_DTYPE;
-    if (p.m < 1 || p.n < 8 || p.k < 8 || p.n % 8 != 0 || p.k % 8 != 0 || p.n > 8192 || p.k > 8192 || p.slabs < 0 || p.slabs > kWgMaxSlabs)
-        return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    return ZIGMA_OK;
-}
-
 }  // namespace zigma
 
 using namespace zigma;
 
-extern "C" int64_t zigma_linear_wgrad_workspace_bytes(const zigma_linear_wgrad_params_t *pp) {
-    if (!pp || wgrad_check(*pp) != ZIGMA_OK) return 0;
-    const int s = wgrad_slabs(*pp);
-    return s > 1 ? static_cast<int64_t>(s) * pp->n * pp->k * 4 : 0;
-}
+extern "C" int64_t zigma_linear_wgrad_workspace_bytes(const zigma_linear_wgrad_params_t *pp) { return pp ? plan_wgrad(*pp).need : 0; }
 
 extern "C" int zigma_linear_wgrad(const zigma_linear_wgrad_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     const zigma_linear_wgrad_params_t &p = *pp;
-    if (!p.dy || !p.x || !p.out) return ZIGMA_ERR_NULL;
-    const int rc = wgrad_check(p);
-    if (rc != ZIGMA_OK) return rc;
-    const int S = wgrad_slabs(p);
-    const int64_t need = S > 1 ? static_cast<int64_t>(S) * p.n * p.k * 4 : 0;
-    if (need > 0 && !p.workspace) return ZIGMA_ERR_NULL;
-    if (p.workspace_bytes < need) return ZIGMA_ERR_SHAPE;
-    const int64_t out_elem = p.out_dtype == ZIGMA_F32 ? 4 : 2;
-    if (p.dy_row_stride < p.n || p.x_row_stride < p.k || p.out_row_stride < p.k || p.dy_row_stride % 8 != 0 || p.x_row_stride % 8 != 0 ||
-        reinterpret_cast<uintptr_t>(p.dy) % 16 != 0 || reinterpret_cast<uintptr_t>(p.x) % 16 != 0 || reinterpret_cast<uintptr_t>(p.out) % 16 != 0 ||
-        (p.out_row_stride * out_elem) % 16 != 0 || (need > 0 && reinterpret_cast<uintptr_t>(p.workspace) % 16 != 0))
-        return ZIGMA_ERR_STRIDE;
+    const WgradPlan plan = plan_wgrad(p);
+    if (!plan.kernel) return plan.status;
 
     (void)hipGetLastError();                                             // (after the refusals: a refused block never touches the device)
     const hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int bk = wgrad_bk(p);
+    const int S = plan.slabs;
     wgrad_args_t a;
     a.dy = static_cast<const uint16_t *>(p.dy);
     a.x = static_cast<const uint16_t *>(p.x);
@@ -236,21 +195,24 @@ extern "C" int zigma_linear_wgrad(const zigma_linear_wgrad_params_t *pp, void *s
     a.out = a.direct ? p.out : p.workspace;
     a.dy_pitch = p.dy_row_stride, a.x_pitch = p.x_row_stride, a.out_pitch = p.out_row_stride;
     a.m = p.m;
-    a.slab_rows = ((p.m + S - 1) / S + kWgKT - 1) / kWgKT * kWgKT;      // whole 64-token steps; slabs past m write zero partials
-    a.n = p.n, a.k = p.k, a.n_tiles = (p.n + kWgBN - 1) / kWgBN;
+    a.slab_rows = plan.slab_rows;
+    a.n = p.n, a.k = p.k, a.n_tiles = plan.n_tiles;
     a.out_f32 = p.out_dtype == ZIGMA_F32;
-    const dim3 grid(static_cast<unsigned>(wgrad_tiles(p)), static_cast<unsigned>(S));
-    if (bk == 64) {
-        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((wgrad_kernel<T, 64>), grid, dim3(kWgThreads), 0, stream, a))
-        set_last_kernel(S == 1 ? "wgrad_128x64" : "wgrad_128x64_splitk");
+    const dim3 grid(plan.gx, plan.gy);
+    if (plan.bk == 64) {
+        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((wgrad_kernel<T, 64>), grid, dim3(plan.block), 0, stream, a))
     } else {
-        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((wgrad_kernel<T, 128>), grid, dim3(kWgThreads), 0, stream, a))
-        set_last_kernel(S == 1 ? "wgrad_128x128" : "wgrad_128x128_splitk");
+        ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL((wgrad_kernel<T, 128>), grid, dim3(plan.block), 0, stream, a))
     }
+    set_last_kernel(plan.kernel);
     int st = check_launch();
     if (st != ZIGMA_OK || S == 1) return st;
     const int64_t quads = static_cast<int64_t>(p.n) * (p.k / 4);
     ZIGMA_DISPATCH_16BIT(p.dtype, T, hipLaunchKernelGGL(wgrad_reduce_kernel<T>, dim3(static_cast<unsigned>((quads + 255) / 256)), dim3(256), 0, stream,
                                                       static_cast<const float *>(p.workspace), p.out, p.out_row_stride, p.n, p.k, S, a.out_f32))
     return check_launch();
+}
+
+extern "C" int zigma_linear_wgrad_plan(const zigma_linear_wgrad_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_wgrad(*pp, kernel) : ZIGMA_ERR_NULL;
 }

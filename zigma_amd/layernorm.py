@@ -205,14 +205,31 @@ def block_norm(x, weight, bias, residual, eps, is_rms, *, residual_in_fp32=True,
     return rs(xe), rs(res_out), rs(y), rs(ym)
 
 
+GLUE_CHUNK_ROWS = 64     # the layout of zigma_scale_reduce_bwd's partial sums r1 / r2 (include/zigma_hip.h): one row per 64 rows of a sample
+
+
+def glue_bwd_block(dy, a, s, s_add=0.0, out=None, r1=None, r2=None, want_out=True, want_sum=False):
+    """The parameter block of zigma_scale_reduce_bwd: dy, a (B, L, E) rows of all samples in one pitch, s (B, E) rows, out (B, L, E), r1 / r2 (B, chunks, E)
+    fp32 (None: fresh where wanted, placeholder addresses — a block to ask about).  Reads shapes, strides, dtypes and addresses only."""
+    Bsz, L, E = dy.shape
+    if want_out and out is None:
+        out = _lib.Desc.fresh(dy, (Bsz, L, E), 1)
+    P = _lib.GlueBwdParams()
+    P.rows, P.cols, P.rows_per_batch, P.dtype, P.flags, P.s_add = Bsz * L, E, L, _lib.dtype_id(dy), 0, float(s_add)
+    P.dy_row_stride, P.a_row_stride, P.out_row_stride, P.s_batch_stride = dy.stride(1), a.stride(1), E, s.stride(0)
+    P.dy, P.a, P.s, P.out = _lib.ptr(dy), _lib.ptr(a), _lib.ptr(s), _lib.ptr(out)
+    P.r1, P.r2 = _lib.ptr(r1) if r1 is not None else 2 * _lib.FRESH_ADDRESS, _lib.ptr(r2) if r2 is not None else (3 * _lib.FRESH_ADDRESS if want_sum else None)
+    return P
+
+
 def glue_bwd_eligible(dy, a, s):
-    """limits of zigma_scale_reduce_bwd: bf16 (B, L, E) rows in one pitch, L % 64 == 0, E % 128 == 0, E <= 8192, 16-byte aligned"""
-    if not (dy.is_cuda and dy.dtype == torch.bfloat16 and a.dtype == dy.dtype and s.dtype == dy.dtype and dy.dim() == 3 and a.shape == dy.shape):
+    """zigma_scale_reduce_bwd takes these tensors: what plan_scale_reduce_bwd() (csrc/attn_plan.h) serves, asked through the library, and what the block
+    cannot say — (B, L, E) rows of all samples in one pitch, s (B, E), one dtype on the device, unit channel strides"""
+    if not (dy.is_cuda and dy.dtype in _lib._DT and a.dtype == dy.dtype and s.dtype == dy.dtype and dy.dim() == 3 and a.shape == dy.shape):
         return False
     Bsz, L, E = dy.shape
-    ok = lambda t: t.stride(2) == 1 and t.stride(1) % 8 == 0 and t.stride(0) == L * t.stride(1) and t.data_ptr() % 16 == 0
-    return (L % 64 == 0 and E % 128 == 0 and E <= 8192 and ok(dy) and ok(a) and s.shape == (Bsz, E) and s.stride(1) == 1 and s.stride(0) % 8 == 0
-            and s.data_ptr() % 16 == 0)
+    rows = lambda t: t.stride(2) == 1 and t.stride(0) == L * t.stride(1)
+    return rows(dy) and rows(a) and s.shape == (Bsz, E) and s.stride(1) == 1 and _lib.served("zigma_scale_reduce_bwd", glue_bwd_block(dy, a, s))
 
 
 def scale_reduce_bwd(dy, a, s, s_add=0.0, want_out=True, want_sum=False):
@@ -220,13 +237,9 @@ def scale_reduce_bwd(dy, a, s, s_add=0.0, want_out=True, want_sum=False):
         out = dy * (s[:, None] + s_add);  r1 = sum_L dy * a;  r2 = sum_L dy (if want_sum)      ->  (out | None, r1, r2 | None), r in dy.dtype"""
     dev = _lib.require_device(dy, a, s)
     Bsz, L, E = dy.shape
-    nch = L // 64
+    nch = L // GLUE_CHUNK_ROWS
     out = torch.empty(Bsz, L, E, device=dy.device, dtype=dy.dtype) if want_out else None
     r1 = torch.empty(Bsz, nch, E, device=dy.device, dtype=torch.float32)
     r2 = torch.empty(Bsz, nch, E, device=dy.device, dtype=torch.float32) if want_sum else None
-    P = _lib.GlueBwdParams()
-    P.rows, P.cols, P.rows_per_batch, P.dtype, P.flags, P.s_add = Bsz * L, E, L, _lib.dtype_id(dy), 0, float(s_add)
-    P.dy_row_stride, P.a_row_stride, P.out_row_stride, P.s_batch_stride = dy.stride(1), a.stride(1), E, s.stride(0)
-    P.dy, P.a, P.s, P.out, P.r1, P.r2 = _lib.ptr(dy), _lib.ptr(a), _lib.ptr(s), _lib.ptr(out), _lib.ptr(r1), _lib.ptr(r2)
-    _lib.call("zigma_scale_reduce_bwd", P, dev)
+    _lib.call("zigma_scale_reduce_bwd", glue_bwd_block(dy, a, s, s_add, out, r1, r2, want_out, want_sum), dev)
     return out, r1.sum(1).to(dy.dtype), None if r2 is None else r2.sum(1).to(dy.dtype)

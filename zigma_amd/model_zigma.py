@@ -99,8 +99,9 @@ class PatchEmbed(nn.Module):
         p = self.patch_size[0]
         no_grad = not (torch.is_grad_enabled() and (x.requires_grad or self.proj.weight.requires_grad
                                                     or (self.proj.bias is not None and self.proj.bias.requires_grad) or (pos is not None and pos.requires_grad)))
-        if no_grad and _embed.patch_embed_eligible(x, self.proj.weight, self.proj.bias, pos):
-            return _embed.patch_embed(x, self.proj.weight, self.proj.bias, pos)
+        block = no_grad and _embed.patch_embed_eligible(x, self.proj.weight, self.proj.bias, pos)
+        if block:
+            return _embed.patch_embed(x, self.proj.weight, self.proj.bias, pos, block=block)
         cols = x.reshape(Bsz, Cin, H // p, p, W // p, p).permute(0, 2, 4, 1, 3, 5).reshape(Bsz, -1, Cin * p * p)
         tok = F.linear(cols, self.proj.weight.reshape(self.proj.weight.shape[0], -1), self.proj.bias)
         return tok if pos is None else tok + pos
@@ -147,12 +148,13 @@ class CrossAttention(nn.Module):
         if q is None:
             q = project("to_q", x, self.to_q.weight, self.to_q.bias)
         needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
-        if cross_attn_eligible(q, k, v, H) and (not needs_grad or cross_attn_bwd_eligible(q, k, v, H)):
+        block = cross_attn_eligible(q, k, v, H, self.scale)        # (the accepted parameter block: the launch only sets the output's address)
+        if block and (not needs_grad or cross_attn_bwd_eligible(q, k, v, H)):
             # HIP kernel: attention core in one pass (K/V of the head in LDS); under autograd its differentiable form (backward =
             # library GEMMs + ATen elementwise ops).  No fused SDPA anywhere: on ROCm that is an AOT-Triton kernel.
             if needs_grad:
                 return self._proj_out(cross_attn_train(q, k, v, H, self.scale), residual, gate)
-            return self._proj_out(cross_attn(q, k, v, H, self.scale), residual, gate)
+            return self._proj_out(cross_attn(q, k, v, H, self.scale, block=block), residual, gate)
         # operands the kernels do not take (fp32 models, fp16 under autograd — the backward kernel is bf16-only —, CPU tensors, long contexts): the same math in torch ops
         return self._proj_out(attention_math(q, k.reshape(Bsz, k.shape[1], -1), v.reshape(Bsz, v.shape[1], -1), H, self.scale), residual, gate)
 
@@ -207,14 +209,17 @@ class TimestepEmbedder(nn.Module):
     def forward(self, t):
         freqs = self._freqs if self._freqs.dtype == self.dtype else self._freqs.to(self.dtype)
         l1, l2 = self.mlp[0], self.mlp[2]
-        if self.frequency_embedding_size % 2 == 0 and _embed.timestep_embed_eligible(t, freqs):
-            t_freq = _embed.timestep_embed(t, freqs, self.frequency_embedding_size)       # one kernel instead of ~8 elementwise launches
+        block = self.frequency_embedding_size % 2 == 0 and _embed.timestep_embed_eligible(t, freqs)
+        if block:
+            t_freq = _embed.timestep_embed(t, freqs, self.frequency_embedding_size, block=block)       # one kernel instead of ~8 elementwise launches
         else:
             t_freq = self.timestep_embedding(t, self.frequency_embedding_size, dtype=self.dtype, freqs=freqs).to(dtype=self.dtype)
-        if _embed.skinny_linear_eligible(t_freq, l1.weight, l1.bias):
-            h = _embed.skinny_linear(t_freq, l1.weight, l1.bias)
-            if _embed.skinny_linear_eligible(h, l2.weight, l2.bias):
-                return _embed.skinny_linear(h, l2.weight, l2.bias, silu=True)                # SiLU folded into the staging of the second product
+        block = _embed.skinny_linear_eligible(t_freq, l1.weight, l1.bias)
+        if block:
+            h = _embed.skinny_linear(t_freq, l1.weight, l1.bias, block=block)
+            block = _embed.skinny_linear_eligible(h, l2.weight, l2.bias, silu=True)
+            if block:
+                return _embed.skinny_linear(h, l2.weight, l2.bias, silu=True, block=block)                # SiLU folded into the staging of the second product
             return l2(F.silu(h))
         return self.mlp(t_freq)
 
@@ -249,8 +254,9 @@ class FinalLayer(nn.Module):
             self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 2 * hidden_size, bias=True))
 
     def forward(self, x, c=None):
-        if c is None and _embed.final_layer_eligible(x, self.linear.weight, self.linear.bias):
-            return _embed.final_layer(x, self.linear.weight, self.linear.bias, self.norm_final.eps)      # LayerNorm + projection in one pass
+        block = c is None and _embed.final_layer_eligible(x, self.linear.weight, self.linear.bias, self.norm_final.eps)
+        if block:
+            return _embed.final_layer(x, self.linear.weight, self.linear.bias, self.norm_final.eps, block=block)      # LayerNorm + projection in one pass
         x = layer_norm_fn(x, None, None, eps=self.norm_final.eps)
         if c is not None:
             shift, scale = self.adaLN_modulation(c).chunk(2, dim=1)
@@ -701,8 +707,9 @@ class ZigMa(nn.Module):
             self._cond_cache = cache
         _, Wm, bm, Wkv = cache
         n = len(blocks)
-        if _embed.skinny_linear_eligible(c, Wm, bm):       # <= 64 samples against n * 6E weight rows: weight-streaming MFMA kernel
-            mods_all = _embed.skinny_linear(c, Wm, bm, silu=True)
+        block = _embed.skinny_linear_eligible(c, Wm, bm, silu=True)       # a few samples against n * 6E weight rows: weight-streaming MFMA kernel
+        if block:
+            mods_all = _embed.skinny_linear(c, Wm, bm, silu=True, block=block)
         else:
             mods_all = F.linear(F.silu(c), Wm, bm)
         mods = mods_all.view(c.shape[0], n, -1).unbind(1)                           # n x (B, 3E | 6E), row pitch n*6E
@@ -755,7 +762,8 @@ class ZigMa(nn.Module):
         lin, frames = self.final_layer.linear, self.video_frames
         grid = int((h.shape[1] // max(frames, 1)) ** 0.5)
         geom = dict(patch=self.x_embedder.patch_size[0], chans=self.out_channels, grid=grid, frames=frames, out_dtype=x.dtype)
-        if _embed.final_layer_guided_eligible(h, lin.weight, lin.bias, scale, **geom):
-            return _embed.final_layer_guided(h, lin.weight, lin.bias, self.final_layer.norm_final.eps, scale, **geom)
+        block = _embed.final_layer_guided_eligible(h, lin.weight, lin.bias, scale, eps=self.final_layer.norm_final.eps, **geom)
+        if block:
+            return _embed.final_layer_guided(h, lin.weight, lin.bias, self.final_layer.norm_final.eps, scale, block=block, **geom)
         v_c, v_u = self._head(h, x.dtype).chunk(2)
         return v_u + scale.view(-1, *([1] * (x.dim() - 1))).to(x.dtype) * (v_c - v_u)

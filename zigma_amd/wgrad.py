@@ -9,7 +9,7 @@ x_proj 227 -> 72, dt_proj 205 -> 64 us — 17 ms of a 122 ms training step.  `Li
 (zigma_linear_fwd) where one serves the shape — the "train" rows of zigma_amd/routing.py (routing.POLICY="off": the library for both).
 
 The same products have an own entry point, zigma_linear_wgrad (csrc/wgrad.hip: split-K over token slabs, MFMA operands by transposed LDS reads, fp32 partials
-added in slab order, row-strided operands): wgrad_own() launches it, plan_wgrad() decides per product between it and the slab bmm (PLAN_TABLE; knob OWN_WGRAD)."""
+added in slab order, row-strided operands): wgrad_own() launches it, own_serves() asks the library's plan of it (csrc/wgrad_plan.h) about the block wgrad_block() builds, plan_wgrad() decides per product between it and the slab bmm (PLAN_TABLE; knob OWN_WGRAD)."""
 import ctypes
 from collections import namedtuple
 
@@ -86,17 +86,34 @@ PLAN_TABLE = (
 )
 
 
+def wgrad_block(dy2, x2, out_dtype=None, slabs=0, out=None, workspace=None):
+    """The parameter block of zigma_linear_wgrad: dy2 (m, n) rows, x2 (m, k) rows, out (n, k) rows of out_dtype (None: fresh rows, a placeholder address —
+    a block to ask about), the workspace the library asks for at this shape (None: a placeholder of that size).  Reads shapes, strides, dtypes and
+    addresses only."""
+    (m, n), k = dy2.shape, x2.shape[1]
+    out_dtype = out_dtype or (out.dtype if out is not None else dy2.dtype)
+    if out is None:
+        out = _lib.Desc.fresh(dy2, (n, k), 1, out_dtype)
+    P = _lib.LinearWgradParams()
+    P.m, P.n, P.k, P.slabs, P.flags = m, n, k, int(slabs), 0
+    # (a mixed pair has no representation in the block: it goes in as an unknown operand type and comes back as ZIGMA_ERR_DTYPE)
+    P.dtype = _lib._DT.get(dy2.dtype, -1) if x2.dtype == dy2.dtype else -1
+    P.out_dtype = _lib._DT.get(out_dtype, -1)
+    P.dy_row_stride, P.x_row_stride, P.out_row_stride = dy2.stride(0), x2.stride(0), out.stride(0)
+    P.dy, P.x, P.out = _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(out)
+    if workspace is None:
+        P.workspace, P.workspace_bytes = 2 * _lib.FRESH_ADDRESS, _lib.lib().zigma_linear_wgrad_workspace_bytes(ctypes.byref(P))
+    else:
+        P.workspace, P.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return P
+
+
 def own_serves(dy2, x2):
-    """the tensor-level limits of zigma_linear_wgrad (include/zigma_hip.h), read from device, dtype, shape, strides and data_ptr only"""
-    if not (dy2.is_cuda and x2.is_cuda) or dy2.dtype not in (torch.bfloat16, torch.float16) or x2.dtype != dy2.dtype:
+    """zigma_linear_wgrad takes these tensors: what plan_wgrad() (csrc/wgrad_plan.h) serves, asked through the library, and what the block cannot say —
+    two matrices with the same rows on the device, unit channel strides"""
+    if not (dy2.is_cuda and x2.is_cuda) or len(dy2.shape) != 2 or len(x2.shape) != 2 or dy2.shape[0] != x2.shape[0]:
         return False
-    if len(dy2.shape) != 2 or len(x2.shape) != 2 or dy2.shape[0] != x2.shape[0] or dy2.shape[0] < 1:
-        return False
-    for t in (dy2, x2):
-        w = t.shape[1]
-        if w < 8 or w % 8 or w > 8192 or t.stride(1) != 1 or t.stride(0) < w or t.stride(0) % 8 or t.data_ptr() % 16:
-            return False
-    return True
+    return dy2.stride(1) == 1 and x2.stride(1) == 1 and _lib.served("zigma_linear_wgrad", wgrad_block(dy2, x2))
 
 
 def plan_row(dy2, x2):
@@ -129,25 +146,13 @@ def wgrad_own(dy2, x2, out_dtype=None, slabs=0, out=None, workspace=None):
         raise RuntimeError("wgrad_own: dy2 (m, n) and x2 (m, k) with the same m")
     if dy2.stride(1) != 1 or x2.stride(1) != 1:
         raise RuntimeError("wgrad_own: the channel stride of both operands must be 1")
-    m, n = dy2.shape
-    k = x2.shape[1]
-    out_dtype = out_dtype or (out.dtype if out is not None else dy2.dtype)
-    P = _lib.LinearWgradParams()
-    P.m, P.n, P.k, P.slabs, P.flags = m, n, k, int(slabs), 0
-    # (a mixed pair has no representation in the block: it goes in as an unknown operand type and comes back as ZIGMA_ERR_DTYPE)
-    P.dtype = _lib.dtype_id(dy2) if x2.dtype == dy2.dtype else -1
-    P.out_dtype = _lib._DT.get(out_dtype, -1)
     if out is None:
-        out = torch.empty(n, k, device=dev, dtype=out_dtype)
-    elif out.shape != (n, k) or out.stride(1) != 1 or out.dtype != out_dtype:
+        out = torch.empty(dy2.shape[1], x2.shape[1], device=dev, dtype=out_dtype or dy2.dtype)
+    elif out.shape != (dy2.shape[1], x2.shape[1]) or out.stride(1) != 1 or out.dtype != (out_dtype or out.dtype):
         raise RuntimeError("wgrad_own: out must be (n, k) rows of out_dtype with channel stride 1")
-    P.dy_row_stride, P.x_row_stride, P.out_row_stride = dy2.stride(0), x2.stride(0), out.stride(0)
-    P.dy, P.x, P.out = _lib.ptr(dy2), _lib.ptr(x2), _lib.ptr(out)
+    P = wgrad_block(dy2, x2, out_dtype, slabs, out, workspace)
     if workspace is None:
         ws = _lib.workspace("zigma_linear_wgrad", P, dev)
-    else:
-        ws = workspace
-        P.workspace, P.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     _lib.call("zigma_linear_wgrad", P, dev)
     return out
 
