@@ -13,6 +13,7 @@ import torch
 import optim16_cases as c16
 import optim_cases as oc
 import sde_cases as sc
+from test_optim_cpu import checked_instantiations
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -49,11 +50,12 @@ def test_symbols_sources_and_kernels_are_registered():
     for name in ("zigma_optim16_grad_sumsq", "zigma_optim16_adamw", "zigma_optim_prepare"):
         assert name in _lib.EXPORTS
     assert "optim_step.hip" in build.SOURCES and build.SOURCE_FLAGS["optim_step.hip"] == build._RES
-    assert "multi_sumsq16_kernel" in build.NO_SCRATCH_KERNELS and "multi_adamw16_kernel" in build.NO_SCRATCH_KERNELS
+    assert "multi_sumsq_kernel" in build.NO_SCRATCH_KERNELS and "multi_adamw_kernel" in build.NO_SCRATCH_KERNELS
+    assert checked_instantiations() == (7, 2, 5)          # the bf16 norm kernel and the two bf16 update kernels are among the checked ones
     hdr = open(os.path.join(ROOT, "include", "zigma_hip.h")).read()
     assert "#define ZIGMA_ABI_VERSION 11 " in hdr and "(11, no block changed): zigma_optim16_* added" in hdr
     src = open(os.path.join(ROOT, "zigma_amd", "csrc", "optim_step.hip")).read()
-    assert "multi_sumsq16_kernel" in src and "multi_adamw16_kernel" in src
+    assert "multi_sumsq_kernel<zigma_optim16_row_t>" in src and "StoreBf16<true>" in src and "StoreBf16<false>" in src
     # one copy of the generator, in the shared header
     csrc = os.path.join(ROOT, "zigma_amd", "csrc")
     holders = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".inc")) and "u32x4 philox4x32_10(" in open(os.path.join(csrc, f)).read()]

@@ -2,6 +2,7 @@
 build, the float64 oracle of tests/optim_cases.py pinned to torch, the error constant K of the GPU sweep, and the optimizer's host logic.  No GPU."""
 import copy
 import ctypes
+import functools
 import os
 import subprocess
 import tempfile
@@ -41,12 +42,24 @@ def test_optim_structs_match_the_header():
     assert got["abi"] == 11
 
 
+@functools.lru_cache(maxsize=None)
+def checked_instantiations():
+    """-> (what build.check_no_scratch counts in a compile of csrc/optim_step.hip alone, the norm kernels among them, the update kernels among them)"""
+    from zigma_amd import build
+    with tempfile.TemporaryDirectory() as d:
+        cmd = [build.HIPCC, *build.FLAGS, *build._RES, "-c", os.path.join(build.CSRC, "optim_step.hip"), "-o", os.path.join(d, "optim_step.o")]
+        remarks = subprocess.run(cmd, check=True, capture_output=True, text=True).stderr
+    names = [ln.split("Function Name: ")[1].split()[0] for ln in remarks.splitlines() if "remark: Function Name: " in ln]
+    return build.check_no_scratch(remarks, "optim_step.hip"), sum("multi_sumsq_kernel" in n for n in names), sum("multi_adamw_kernel" in n for n in names)
+
+
 def test_symbols_sources_and_kernels_are_registered():
     from zigma_amd import _lib, build
     for name in ("zigma_optim_grad_sumsq", "zigma_optim_prepare", "zigma_optim_adamw"):
         assert name in _lib.EXPORTS
     assert "optim_step.hip" in build.SOURCES and build.SOURCE_FLAGS["optim_step.hip"] == build._RES
     assert "multi_sumsq_kernel" in build.NO_SCRATCH_KERNELS and "multi_adamw_kernel" in build.NO_SCRATCH_KERNELS
+    assert checked_instantiations() == (7, 2, 5)          # both tails' kernels are instantiations of those two: 2 norm (fp32, bf16), 5 update (3 fp32, 2 bf16)
     hdr = open(os.path.join(ROOT, "include", "zigma_hip.h")).read()
     assert "#define ZIGMA_ABI_VERSION 11 " in hdr and "(11, no block changed): zigma_optim_* added" in hdr
     assert os.path.exists(os.path.join(ROOT, "zigma_amd", "csrc", "optim_step.hip"))

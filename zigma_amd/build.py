@@ -34,13 +34,13 @@ _RES = ["-Rpass-analysis=kernel-resource-usage"]
 # multi_cast_kernel (csrc/multi_cast.hip) is a pure stream of 16-byte accesses: scratch traffic would come straight off its copy rate, so the same check.
 # final_layer_cfg_kernel (csrc/embed.hip) keeps a row of up to 2048 features (128 registers per lane) through two statistics passes and the dot products, twice per
 # output: the same check.
-# multi_sumsq_kernel and multi_adamw_kernel (csrc/optim_step.hip) stream up to ten 16-byte accesses per lane and iteration and hold 40 values between them: the same check.
-# multi_sumsq16_kernel and multi_adamw16_kernel (the same file) add a Philox call per lane and iteration to that stream: the same check.
+# multi_sumsq_kernel and multi_adamw_kernel (csrc/optim_step.hip; 2 + 5 instantiations, fp32 and bf16 parameters) stream up to ten 16-byte accesses per lane and
+# iteration and hold 40 values between them, the stochastically rounding store adds a Philox call per lane and iteration: the same check.
 # sde_step_kernel (csrc/sde_step.hip) calls the library's logf and sincospif, whose results come back through pointers: a pointer left in scratch would put memory
 # traffic into a kernel that has none to spare, so the same check.
 SOURCE_FLAGS = {"cross_attn.hip": _VGPR_MFMA, "scan_tok_bf16.hip": _RES, "scan_tok_f16.hip": _RES, "wgrad.hip": _RES, "linear_split.hip": _RES, "norm_linear.hip": _RES, "multi_cast.hip": _RES, "optim_step.hip": _RES, "embed.hip": _RES, "sde_step.hip": _RES}
 NO_SCRATCH_KERNELS = ("scan_tok2_kernel", "wgrad_kernel", "wgrad_reduce_kernel", "linear_split_kernel", "norm_linear_kernel", "multi_cast_kernel", "multi_sumsq_kernel",
-                      "multi_adamw_kernel", "multi_sumsq16_kernel", "multi_adamw16_kernel", "final_layer_cfg_kernel", "sde_step_kernel")
+                      "multi_adamw_kernel", "final_layer_cfg_kernel", "sde_step_kernel")
 
 
 def check_no_scratch(remarks, src):

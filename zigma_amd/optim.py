@@ -29,21 +29,22 @@ def _device_ok(t):
     return t.is_cuda
 
 
-def _check_tensor(t, what, device=None, shape=None):
+def _check_tensor(who, t, what, dtype, wrong_dtype, device=None, shape=None):
+    """`wrong_dtype(dtype)` is the class's sentence about a tensor of another element type"""
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"FusedAdamW: {what} is not a tensor")
+        raise TypeError(f"{who}: {what} is not a tensor")
     if t.layout != torch.strided:
-        raise ValueError(f"FusedAdamW: {what} is sparse; the kernel takes dense tensors only")
-    if t.dtype != torch.float32:
-        raise ValueError(f"FusedAdamW: {what} is {t.dtype}; the kernel takes float32 only (keep fp32 master parameters and train under torch.autocast)")
+        raise ValueError(f"{who}: {what} is sparse; the kernel takes dense tensors only")
+    if t.dtype != dtype:
+        raise ValueError(f"{who}: {what} is {wrong_dtype(t.dtype)}")
     if not _device_ok(t):
-        raise ValueError(f"FusedAdamW: {what} is on {t.device}; the kernel needs a GPU (there is no CPU fallback)")
+        raise ValueError(f"{who}: {what} is on {t.device}; the kernel needs a GPU (there is no CPU fallback)")
     if device is not None and t.device != device:
-        raise ValueError(f"FusedAdamW: {what} is on {t.device}, the parameters are on {device}")
+        raise ValueError(f"{who}: {what} is on {t.device}, the parameters are on {device}")
     if not t.is_contiguous():
-        raise ValueError(f"FusedAdamW: {what} is not contiguous")
+        raise ValueError(f"{who}: {what} is not contiguous")
     if shape is not None and t.shape != shape:
-        raise ValueError(f"FusedAdamW: {what} has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
+        raise ValueError(f"{who}: {what} has shape {tuple(t.shape)}, its parameter {tuple(shape)}")
 
 
 def _check_hyper(who, lr, betas, eps, weight_decay, max_grad_norm, ema_decay):
@@ -113,13 +114,53 @@ class StepTables:
 
 
 class _StepTail(torch.optim.Optimizer):
-    """what the two optimizers of this module share: ONE parameter group, the device state block (zigma_optim_state_t in `_block`) behind `step_count`,
-    `skipped` and `grad_norm`, state_dict() as copies, zero_grad() in place"""
+    """what the two optimizers of this module share: ONE parameter group of torch.optim.AdamW's keys, fp32 moment arenas, the device state block
+    (zigma_optim_state_t in `_block`) behind `step_count`, `skipped` and `grad_norm`, state_dict() as copies, zero_grad() in place, and the step:
+    checks, rows, tables, three launches.  A subclass names its element type (`_dtype`, `_wrong_dtype`), and supplies `_rows(ps, grads)`,
+    `_launch(group, tables, n_rows)` and, if its group carries more keys, `_check_group_extra(group)`."""
+
+    def __init__(self, params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, amsgrad, maximize, **more_keys):
+        _check_hyper(type(self).__name__, lr, betas, eps, weight_decay, max_grad_norm, ema_decay)
+        # (the keys torch.optim.AdamW's groups carry, so that a state_dict travels both ways)
+        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
+                        differentiable=False, fused=True, decoupled_weight_decay=True, **more_keys)
+        super().__init__(params, defaults)
+        self._check_group()
+        ps = self.param_groups[0]["params"]
+        for i, p in enumerate(ps):
+            self._check_tensor(p, f"parameter {i}", ps[0].device)
+        self.device = ps[0].device
+        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
+
+    def _allocate(self, tables):
+        """the end of a constructor, past its refusals: the fp32 moment arenas, the state block, the step's tables, state[p]"""
+        ps = self.param_groups[0]["params"]
+        self._m_arena, self._m = arena_views(ps, self.device)
+        self._v_arena, self._v = arena_views(ps, self.device)
+        self._block = torch.zeros(8, dtype=torch.float32, device=self.device)             # zigma_optim_state_t
+        self._tables = tables
+        self._install_state()
 
     def add_param_group(self, param_group):
         if self.param_groups:
             raise ValueError(f"{type(self).__name__}: one parameter group only (the gradient norm is global; the reference trains with one group)")
         super().add_param_group(param_group)
+
+    def _check_tensor(self, t, what, device=None, shape=None):
+        _check_tensor(type(self).__name__, t, what, self._dtype, self._wrong_dtype, device, shape)
+
+    def _check_group(self):
+        g, who = self.param_groups[0], type(self).__name__
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError(f"{who}: amsgrad and maximize are not implemented by the kernel")
+        if g.get("decoupled_weight_decay") is False:
+            raise ValueError(f"{who}: the kernel's weight decay is decoupled (AdamW); this group asks for Adam's L2 form")
+        if isinstance(g["lr"], torch.Tensor):
+            raise ValueError(f"{who}: lr is a host value per launch, not a tensor")
+        self._check_group_extra(g)
+
+    def _check_group_extra(self, g):
+        pass
 
     @property
     def step_count(self):
@@ -136,6 +177,10 @@ class _StepTail(torch.optim.Optimizer):
         """device fp32 scalar: the last step's global gradient norm before clipping, unscaled (NaN when max_grad_norm is None)"""
         return self._block[2]
 
+    def _install_state(self):
+        for p, m, v in zip(self.param_groups[0]["params"], self._m, self._v):
+            self.state[p] = {"step": self._block[0], "exp_avg": m, "exp_avg_sq": v}
+
     def state_dict(self):
         """torch's layout.  Every tensor is a COPY (the live ones are views of the arenas and one shared step, which another optimizer must not
         alias), and each parameter gets a step of its own, as torch.optim.AdamW keeps them."""
@@ -143,9 +188,65 @@ class _StepTail(torch.optim.Optimizer):
         sd["state"] = {k: {n: (t.clone() if isinstance(t, torch.Tensor) else t) for n, t in st.items()} for k, st in sd["state"].items()}
         return sd
 
+    def _loaded_step(self, loaded):
+        """the ONE step of the loaded per-parameter states (None: a parameter without state); raises if they disagree"""
+        n = len(self.param_groups[0]["params"])
+        steps = [torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()) for st in loaded if st is not None]
+        steps = torch.stack(steps).tolist() if steps else []
+        if len(set(steps)) > 1 or (steps and steps[0] != 0 and len(steps) != n):
+            raise ValueError(f"{type(self).__name__}: the loaded per-parameter steps disagree (or some parameters have none); this optimizer keeps ONE step counter: "
+                             f"{sorted(set(steps))}, {len(steps)} of {n} parameters")
+        return steps[0] if steps else 0.0
+
+    def _restart_at(self, step):
+        """the end of a load: a fresh state block at `step`, state[p] on the live tensors again"""
+        self._block.zero_()
+        self._block[0] = step
+        self.state.clear()
+        self._install_state()
+
     def zero_grad(self, set_to_none=False):
         """zeroes the gradients in place by default, so that their addresses — and with them the device table — stay put"""
         super().zero_grad(set_to_none=set_to_none)
+
+    def _fill(self, P, g, T, n_rows):
+        """what both parameter blocks carry: table, map, counts, state, partials (when there is a norm pass), the seven hyperparameters, chunk"""
+        P.table, P.chunk_map, P.n_entries, P.n_chunks = T.table.data_ptr(), T.cmap.data_ptr(), n_rows, T.n_chunks
+        P.state, P.chunk = self._block.data_ptr(), T.chunk
+        P.lr, (P.beta1, P.beta2), P.eps, P.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
+        P.max_grad_norm, P.ema_decay = self.max_grad_norm or 0.0, self.ema_decay
+        if self.max_grad_norm is not None:
+            P.partials = T.partials.data_ptr()
+        return P
+
+    def _launches(self, sumsq, P, prepare_block, adamw):
+        if self.max_grad_norm is not None:
+            _lib.call(sumsq, P, self.device)
+        _lib.call("zigma_optim_prepare", prepare_block, self.device)
+        _lib.call(adamw, P, self.device)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        g = self.param_groups[0]
+        self._check_group()
+        ps, dt = g["params"], self._dtype
+        grads = [p.grad for p in ps]
+        for i, (p, gr) in enumerate(zip(ps, grads)):
+            if gr is not None and (gr.dtype != dt or gr.layout != torch.strided or gr.device != p.device or gr.shape != p.shape or not gr.is_contiguous()
+                                   or not p.is_contiguous() or p.dtype != dt):
+                raise RuntimeError(f"{type(self).__name__}: parameter {i} or its gradient is not a dense contiguous {str(dt).replace('torch.', '')} tensor on {self.device}")
+        rows = self._rows(ps, grads)
+        if not rows:
+            return loss
+        STATS["table_builds"] += self._tables.update(rows, self.device)
+        self._launch(g, self._tables, len(rows))
+        STATS["steps"] += 1
+        STATS["launches"] += 3 if self.max_grad_norm is not None else 2
+        return loss
 
 
 class FusedAdamW(_StepTail):
@@ -172,27 +273,23 @@ class FusedAdamW(_StepTail):
     raises if its per-parameter steps disagree."""
 
     _step_supports_amp_scaling = True
+    _dtype = torch.float32
+
+    @staticmethod
+    def _wrong_dtype(dtype):
+        return f"{dtype}; the kernel takes float32 only (keep fp32 master parameters and train under torch.autocast)"
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_params=None, ema_decay=0.9999,
                  shadows=None, *, amsgrad=False, maximize=False):
-        _check_hyper("FusedAdamW", lr, betas, eps, weight_decay, max_grad_norm, ema_decay)
-        # (the keys torch.optim.AdamW's groups carry, so that a state_dict travels both ways)
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
-                        differentiable=False, fused=True, decoupled_weight_decay=True)
-        super().__init__(params, defaults)
-        self._check_group()
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, amsgrad, maximize)
         ps = self.param_groups[0]["params"]
-        for i, p in enumerate(ps):
-            _check_tensor(p, f"parameter {i}", ps[0].device)
-        self.device = ps[0].device
-        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
         self._ema = None
         if ema_params is not None:
             ema = list(ema_params.parameters()) if isinstance(ema_params, torch.nn.Module) else list(ema_params)
             if len(ema) != len(ps):
                 raise ValueError(f"FusedAdamW: {len(ema)} ema tensors for {len(ps)} parameters")
             for i, (e, p) in enumerate(zip(ema, ps)):
-                _check_tensor(e, f"ema tensor {i}", self.device, p.shape)
+                self._check_tensor(e, f"ema tensor {i}", self.device, p.shape)
                 if e.data_ptr() == p.data_ptr() and p.numel():
                     raise ValueError(f"FusedAdamW: ema tensor {i} IS parameter {i}; pass a copy (copy.deepcopy(model))")
             self._ema = ema
@@ -202,38 +299,15 @@ class FusedAdamW(_StepTail):
             if not isinstance(mod, torch.nn.Module) or dt not in (torch.bfloat16, torch.float16):
                 raise ValueError("FusedAdamW: shadows is a module or (module, torch.bfloat16 / torch.float16)")
             self._shadow_module, self._shadow_dtype = mod, dt
-        self._m_arena, self._m = arena_views(ps, self.device)
-        self._v_arena, self._v = arena_views(ps, self.device)
-        self._block = torch.zeros(8, dtype=torch.float32, device=self.device)             # zigma_optim_state_t
-        self._tables = StepTables()
-        self._install_state()
-
-    # ---- one group, torch's state keys ------------------------------------------------------------------------------------------------------------
-    def _check_group(self):
-        g = self.param_groups[0]
-        if g.get("amsgrad") or g.get("maximize"):
-            raise ValueError("FusedAdamW: amsgrad and maximize are not implemented by the kernel")
-        if g.get("decoupled_weight_decay") is False:
-            raise ValueError("FusedAdamW: the kernel's weight decay is decoupled (AdamW); this group asks for Adam's L2 form")
-        if isinstance(g["lr"], torch.Tensor):
-            raise ValueError("FusedAdamW: lr is a host value per launch, not a tensor")
-
-    def _install_state(self):
-        for p, m, v in zip(self.param_groups[0]["params"], self._m, self._v):
-            self.state[p] = {"step": self._block[0], "exp_avg": m, "exp_avg_sq": v}
+        self._allocate(StepTables())
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         if len(self.param_groups) != 1:
             raise ValueError("FusedAdamW: one parameter group only")
         self._check_group()
-        ps = self.param_groups[0]["params"]
-        loaded = [self.state[p] if p in self.state and len(self.state[p]) else None for p in ps]
-        steps = [torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()) for st in loaded if st is not None]
-        steps = torch.stack(steps).tolist() if steps else []
-        if len(set(steps)) > 1 or (steps and steps[0] != 0 and len(steps) != len(ps)):
-            raise ValueError("FusedAdamW: the loaded per-parameter steps disagree (or some parameters have none); this optimizer keeps ONE step counter: "
-                             f"{sorted(set(steps))}, {len(steps)} of {len(ps)} parameters")
+        loaded = [self.state[p] if p in self.state and len(self.state[p]) else None for p in self.param_groups[0]["params"]]
+        step = self._loaded_step(loaded)
         for st, m, v in zip(loaded, self._m, self._v):
             if st is None:
                 m.zero_()
@@ -241,10 +315,7 @@ class FusedAdamW(_StepTail):
             else:
                 m.copy_(st["exp_avg"])
                 v.copy_(st["exp_avg_sq"])
-        self._block.zero_()
-        self._block[0] = steps[0] if steps else 0.0
-        self.state.clear()
-        self._install_state()
+        self._restart_at(step)
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
     def _shadows_now(self):
@@ -268,73 +339,25 @@ class FusedAdamW(_StepTail):
             raise RuntimeError(f"FusedAdamW: {name} must be a one-element float32 tensor on {self.device}")
         return t
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        g = self.param_groups[0]
-        self._check_group()
-        ps = g["params"]
-        grads = [p.grad for p in ps]
-        for i, (p, gr) in enumerate(zip(ps, grads)):
-            if gr is not None and (gr.dtype != torch.float32 or gr.layout != torch.strided or gr.device != p.device or gr.shape != p.shape or not gr.is_contiguous()
-                                   or not p.is_contiguous()):
-                raise RuntimeError(f"FusedAdamW: parameter {i} or its gradient is not a dense contiguous float32 tensor on {self.device}")
+    def _rows(self, ps, grads):
+        return step_rows(ps, grads, self._m, self._v, self._ema, self._shadows_now()[0])
+
+    def _launch(self, g, T, n_rows):
         shadows, grp = self._shadows_now()
-        rows = step_rows(ps, grads, self._m, self._v, self._ema, shadows)
-        if not rows:
-            return loss
-        T = self._tables
-        STATS["table_builds"] += T.update(rows, self.device)
-        grad_scale, found_inf = self._scaler_scalar("grad_scale"), self._scaler_scalar("found_inf")
-        P = _lib.OptimParams()
-        P.table, P.chunk_map, P.n_entries, P.n_chunks = T.table.data_ptr(), T.cmap.data_ptr(), len(rows), T.n_chunks
-        P.state, P.grad_scale, P.found_inf = self._block.data_ptr(), _lib.ptr(grad_scale), _lib.ptr(found_inf)
-        P.lr, (P.beta1, P.beta2), P.eps, P.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
-        P.max_grad_norm, P.ema_decay = self.max_grad_norm or 0.0, self.ema_decay
-        P.shadow_dtype, P.chunk, P.flags = (_lib._DT[self._shadow_dtype] if shadows else -1), T.chunk, 0
+        P = self._fill(_lib.OptimParams(), g, T, n_rows)
+        P.grad_scale, P.found_inf = _lib.ptr(self._scaler_scalar("grad_scale")), _lib.ptr(self._scaler_scalar("found_inf"))
+        P.shadow_dtype = _lib._DT[self._shadow_dtype] if shadows else -1
         # were the shadows current before this step?  Then they are current after it: written by the kernel, or — a skipped step — as unchanged as the
         # parameters.  If they were stale, a skipped step would leave them stale, so nothing is recorded and the next forward refreshes as ever.
         fresh = grp is not None and grp.fresh(self._shadow_dtype)
-        if self.max_grad_norm is not None:
-            P.partials = T.partials.data_ptr()
-            _lib.call("zigma_optim_grad_sumsq", P, self.device)
-        _lib.call("zigma_optim_prepare", P, self.device)
-        _lib.call("zigma_optim_adamw", P, self.device)
+        self._launches("zigma_optim_grad_sumsq", P, P, "zigma_optim_adamw")
         if fresh:
             grp.written_by_step(self._shadow_dtype)
-        STATS["steps"] += 1
-        STATS["launches"] += 3 if self.max_grad_norm is not None else 2
-        return loss
 
 
 # ---- the same tail for a pure bf16 model ----------------------------------------------------------------------------------------------------------------
 MAX_NUMEL16 = 1 << 35     # an element's random bits are addressed by a 32-bit octet index (include/zigma_hip.h)
 _ROUNDINGS = ("stochastic", "nearest")
-
-
-def _check_tensor16(t, what, device=None):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"FusedAdamW16: {what} is not a tensor")
-    if t.layout != torch.strided:
-        raise ValueError(f"FusedAdamW16: {what} is sparse; the kernel takes dense tensors only")
-    if t.dtype == torch.float16:
-        raise ValueError(f"FusedAdamW16: {what} is float16; the kernel takes bfloat16 only.  A pure fp16 model has no loss scaling to train with: "
-                         "torch.amp.GradScaler will not unscale 16-bit gradients.  Keep fp32 master parameters under torch.autocast(float16) and use FusedAdamW")
-    if t.dtype == torch.float32:
-        raise ValueError(f"FusedAdamW16: {what} is float32; the kernel takes bfloat16 only (fp32 parameters go to zigma_amd.optim.FusedAdamW)")
-    if t.dtype != torch.bfloat16:
-        raise ValueError(f"FusedAdamW16: {what} is {t.dtype}; the kernel takes bfloat16 only")
-    if not _device_ok(t):
-        raise ValueError(f"FusedAdamW16: {what} is on {t.device}; the kernel needs a GPU (there is no CPU fallback)")
-    if device is not None and t.device != device:
-        raise ValueError(f"FusedAdamW16: {what} is on {t.device}, the parameters are on {device}")
-    if not t.is_contiguous():
-        raise ValueError(f"FusedAdamW16: {what} is not contiguous")
-    if t.numel() >= MAX_NUMEL16:
-        raise ValueError(f"FusedAdamW16: {what} has {t.numel()} elements; the kernel addresses its random bits below 2^35 elements per tensor")
 
 
 def step_rows16(params, grads, ms, vs, emas):
@@ -375,40 +398,34 @@ class FusedAdamW16(_StepTail):
     load_state_dict() takes its own dicts and those of torch.optim.AdamW on the same bf16 model (bf16 moments are widened), and raises if the
     per-parameter steps disagree.  `skipped`, `grad_norm` and `step_count` are device scalars, as in FusedAdamW."""
 
+    _dtype = torch.bfloat16
+
+    @staticmethod
+    def _wrong_dtype(dtype):
+        if dtype == torch.float16:
+            return ("float16; the kernel takes bfloat16 only.  A pure fp16 model has no loss scaling to train with: torch.amp.GradScaler will not unscale "
+                    "16-bit gradients.  Keep fp32 master parameters under torch.autocast(float16) and use FusedAdamW")
+        if dtype == torch.float32:
+            return "float32; the kernel takes bfloat16 only (fp32 parameters go to zigma_amd.optim.FusedAdamW)"
+        return f"{dtype}; the kernel takes bfloat16 only"
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema=False, ema_decay=0.9999,
                  rounding="stochastic", seed=0, stream=0, *, amsgrad=False, maximize=False):
-        _check_hyper("FusedAdamW16", lr, betas, eps, weight_decay, max_grad_norm, ema_decay)
-        defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=False,
-                        differentiable=False, fused=True, decoupled_weight_decay=True, rounding=rounding, seed=seed, stream=stream)
-        super().__init__(params, defaults)
-        self._check_group()
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, ema_decay, amsgrad, maximize, rounding=rounding, seed=seed, stream=stream)
         ps = self.param_groups[0]["params"]
         for i, p in enumerate(ps):
-            _check_tensor16(p, f"parameter {i}", ps[0].device)
-        self.device = ps[0].device
-        self.max_grad_norm, self.ema_decay = max_grad_norm, ema_decay
-        self._m_arena, self._m = arena_views(ps, self.device)
-        self._v_arena, self._v = arena_views(ps, self.device)
+            if p.numel() >= MAX_NUMEL16:
+                raise ValueError(f"FusedAdamW16: parameter {i} has {p.numel()} elements; the kernel addresses its random bits below 2^35 elements per tensor")
         self._ema_arena, self._ema = None, None
         if ema:
             self._ema_arena, self._ema = arena_views(ps, self.device)
             with torch.no_grad():
                 for e, p in zip(self._ema, ps):
                     e.copy_(p)                                                         # bf16 -> fp32: exact
-        self._block = torch.zeros(8, dtype=torch.float32, device=self.device)             # zigma_optim_state_t
-        self._tables = StepTables(width=10, numel_col=5)
         self._cast_tables = None
-        self._install_state()
+        self._allocate(StepTables(width=10, numel_col=5))
 
-    # ---- one group, torch's state keys ------------------------------------------------------------------------------------------------------------
-    def _check_group(self):
-        g = self.param_groups[0]
-        if g.get("amsgrad") or g.get("maximize"):
-            raise ValueError("FusedAdamW16: amsgrad and maximize are not implemented by the kernel")
-        if g.get("decoupled_weight_decay") is False:
-            raise ValueError("FusedAdamW16: the kernel's weight decay is decoupled (AdamW); this group asks for Adam's L2 form")
-        if isinstance(g["lr"], torch.Tensor):
-            raise ValueError("FusedAdamW16: lr is a host value per launch, not a tensor")
+    def _check_group_extra(self, g):
         if g["rounding"] not in _ROUNDINGS:
             raise ValueError(f"FusedAdamW16: rounding is one of {_ROUNDINGS}, got {g['rounding']!r}")
         if isinstance(g["seed"], bool) or not isinstance(g["seed"], int) or not 0 <= g["seed"] < 1 << 64:
@@ -436,10 +453,10 @@ class FusedAdamW16(_StepTail):
         amp._on_optimizer_step(self, (), {})                # the parameters of `module` were written behind their version counters: what is cached of them is stale
 
     def _install_state(self):
-        for i, p in enumerate(self.param_groups[0]["params"]):
-            self.state[p] = {"step": self._block[0], "exp_avg": self._m[i], "exp_avg_sq": self._v[i]}
-            if self._ema is not None:
-                self.state[p]["ema"] = self._ema[i]
+        super()._install_state()
+        if self._ema is not None:
+            for p, e in zip(self.param_groups[0]["params"], self._ema):
+                self.state[p]["ema"] = e
 
     def load_state_dict(self, state_dict):
         """its own dicts, or torch.optim.AdamW's on the same bf16 model.  Written out here and not left to torch.optim.Optimizer.load_state_dict, which
@@ -463,11 +480,7 @@ class FusedAdamW16(_StepTail):
             raise
         state = state_dict["state"]
         loaded = [state.get(i) or None for i in ids]
-        steps = [torch.as_tensor(st["step"]).detach().to(device="cpu", dtype=torch.float32).reshape(()) for st in loaded if st is not None]
-        steps = torch.stack(steps).tolist() if steps else []
-        if len(set(steps)) > 1 or (steps and steps[0] != 0 and len(steps) != len(ps)):
-            raise ValueError("FusedAdamW16: the loaded per-parameter steps disagree (or some parameters have none); this optimizer keeps ONE step counter: "
-                             f"{sorted(set(steps))}, {len(steps)} of {len(ps)} parameters")
+        step = self._loaded_step(loaded)
         with torch.no_grad():
             for i, st in enumerate(loaded):
                 if st is None:
@@ -478,47 +491,18 @@ class FusedAdamW16(_StepTail):
                 self._v[i].copy_(st["exp_avg_sq"])
                 if self._ema is not None and "ema" in st:
                     self._ema[i].copy_(st["ema"])
-            self._block.zero_()
-            self._block[0] = steps[0] if steps else 0.0
-        self.state.clear()
-        self._install_state()
+            self._restart_at(step)
 
     # ---- the step ---------------------------------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        g = self.param_groups[0]
-        self._check_group()
-        ps = g["params"]
-        grads = [p.grad for p in ps]
-        for i, (p, gr) in enumerate(zip(ps, grads)):
-            if gr is not None and (gr.dtype != torch.bfloat16 or gr.layout != torch.strided or gr.device != p.device or gr.shape != p.shape or not gr.is_contiguous()
-                                   or not p.is_contiguous() or p.dtype != torch.bfloat16):
-                raise RuntimeError(f"FusedAdamW16: parameter {i} or its gradient is not a dense contiguous bfloat16 tensor on {self.device}")
-        rows = step_rows16(ps, grads, self._m, self._v, self._ema)
-        if not rows:
-            return loss
-        T = self._tables
-        STATS["table_builds"] += T.update(rows, self.device)
-        P = _lib.Optim16Params()
-        P.table, P.chunk_map, P.n_entries, P.n_chunks, P.max_numel = T.table.data_ptr(), T.cmap.data_ptr(), len(rows), T.n_chunks, max(T.numels)
-        P.state = self._block.data_ptr()
-        P.lr, (P.beta1, P.beta2), P.eps, P.weight_decay = g["lr"], g["betas"], g["eps"], g["weight_decay"]
-        P.max_grad_norm, P.ema_decay = self.max_grad_norm or 0.0, self.ema_decay
+    def _rows(self, ps, grads):
+        return step_rows16(ps, grads, self._m, self._v, self._ema)
+
+    def _launch(self, g, T, n_rows):
+        P = self._fill(_lib.Optim16Params(), g, T, n_rows)
+        P.max_numel, P.flags = max(T.numels), _lib.OPTIM16_NEAREST if g["rounding"] == "nearest" else 0
         P.seed_lo, P.seed_hi, P.stream = g["seed"] & 0xffffffff, g["seed"] >> 32, g["stream"]
-        P.chunk, P.flags = T.chunk, _lib.OPTIM16_NEAREST if g["rounding"] == "nearest" else 0
-        Q = _lib.OptimParams()                              # the prepare launch is the fp32 path's, on its own block
-        Q.table, Q.chunk_map, Q.n_entries, Q.n_chunks, Q.state = P.table, P.chunk_map, P.n_entries, P.n_chunks, P.state
-        Q.lr, Q.beta1, Q.beta2, Q.eps, Q.weight_decay, Q.max_grad_norm, Q.ema_decay = P.lr, P.beta1, P.beta2, P.eps, P.weight_decay, P.max_grad_norm, P.ema_decay
-        Q.shadow_dtype, Q.chunk, Q.flags = -1, T.chunk, 0
-        if self.max_grad_norm is not None:
-            P.partials = Q.partials = T.partials.data_ptr()
-            _lib.call("zigma_optim16_grad_sumsq", P, self.device)
-        _lib.call("zigma_optim_prepare", Q, self.device)
-        _lib.call("zigma_optim16_adamw", P, self.device)
-        STATS["steps"] += 1
-        STATS["launches"] += 3 if self.max_grad_norm is not None else 2
-        return loss
+        Q = self._fill(_lib.OptimParams(), g, T, n_rows)    # the prepare launch is the fp32 path's, on its own block
+        Q.shadow_dtype = -1
+        self._launches("zigma_optim16_grad_sumsq", P, Q, "zigma_optim16_adamw")
+
+
