@@ -48,7 +48,9 @@ extern "C" {
                                * (11, no block changed): the plan queries zigma_linear_fwd_plan, zigma_norm_linear_fwd_plan, zigma_linear_f32_split_plan added
                                * (11, no block changed): zigma_optim16_* added
                                * (11, no block changed): the plan queries of the operators around the blocks, cross-attention, zigma_scale_reduce_bwd and
-                               *    zigma_linear_wgrad added (zigma_patch_embed_fwd_plan ... zigma_linear_wgrad_plan) */
+                               *    zigma_linear_wgrad added (zigma_patch_embed_fwd_plan ... zigma_linear_wgrad_plan)
+                               * (11, no block changed): the plan queries zigma_add_norm_fwd_plan, zigma_add_norm_bwd_plan, zigma_selective_scan_bwd_plan,
+                               *    zigma_causal_conv1d_bwd_plan added */
 
 /* zigma_scan_params_t.flags */
 #define ZIGMA_SCAN_Z_PREACTIVATED 2   /* z already holds silu(z) (the in_proj GEMM epilogue applied it): out_z = y * z */
@@ -1073,6 +1075,13 @@ int zigma_cross_attn_fwd_plan(const zigma_xattn_params_t *p, const char **kernel
 int zigma_cross_attn_bwd_plan(const zigma_xattn_bwd_params_t *p, const char **kernel);
 int zigma_scale_reduce_bwd_plan(const zigma_glue_bwd_params_t *p, const char **kernel);
 int zigma_linear_wgrad_plan(const zigma_linear_wgrad_params_t *p, const char **kernel);
+/* ... and of add-norm in both directions (csrc/norm_plan.h) and the scan and conv backward (csrc/bwd_plan.h) (ABI 11, no block changed), under the same
+ * rules: with these every compute entry point the model's forward or backward calls answers a query.  The three *_workspace_bytes() are the `need` of
+ * the same plans. */
+int zigma_add_norm_fwd_plan(const zigma_norm_params_t *p, const char **kernel);
+int zigma_add_norm_bwd_plan(const zigma_norm_bwd_params_t *p, const char **kernel);
+int zigma_selective_scan_bwd_plan(const zigma_scan_bwd_params_t *p, const char **kernel);
+int zigma_causal_conv1d_bwd_plan(const zigma_conv_bwd_params_t *p, const char **kernel);
 
 /* ------------------------------------------------------------------------------------------ */
 const char *zigma_strerror(int status);

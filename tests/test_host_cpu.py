@@ -619,13 +619,13 @@ def _compile_plan(driver):
         return ctypes.CDLL(so)
 
 
-def _plan_caller(L, params_type, names, fn="plan"):
+def _plan_caller(L, params_type, names, fn="plan", field_type=ctypes.c_int):
     """plan(P) -> dict of the driver's integer fields and the kernel string"""
     entry = getattr(L, fn)
-    entry.argtypes = [ctypes.POINTER(params_type), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_char_p)]
+    entry.argtypes = [ctypes.POINTER(params_type), ctypes.POINTER(field_type), ctypes.POINTER(ctypes.c_char_p)]
 
     def plan(P):
-        f, k = (ctypes.c_int * len(names))(), ctypes.c_char_p()
+        f, k = (field_type * len(names))(), ctypes.c_char_p()
         entry(ctypes.byref(P), f, ctypes.byref(k))
         return dict(zip(names, f), kernel=k.value.decode() if k.value else None)
     return plan
@@ -1275,3 +1275,257 @@ def test_chunks_and_workspace_bytes_answer_as_the_plans_do(outer_plan, libpath):
         pl = outer_plan(P)
         assert pl["status"] == -1 and L.zigma_linear_wgrad_workspace_bytes(ctypes.byref(P)) == pl["bytes"] == (pl["switch"] * n * k * 4 if pl["switch"] > 1 else 0)
         assert pl["switch"] == (slabs or max(1, min(64, m // 512, -(-512 // (-(-n // 128) * -(-k // (64 if k <= 64 else 128)))))))
+
+
+_BWD_PLAN_DRIVER = r"""
+#include "norm_plan.h"
+#include "bwd_plan.h"
+using namespace zigma;
+static int norm(const NormPlan &s, int64_t *f, const char **kernel) {
+    f[0] = s.status; f[1] = s.gx; f[2] = 1; f[3] = 1; f[4] = s.block; f[5] = s.need; f[6] = s.vec; f[7] = s.iters; f[8] = s.lpr; f[9] = s.res32; f[10] = s.w32; f[11] = s.fin_gx;
+    *kernel = s.kernel;
+    return s.status;
+}
+static int bwd(const BwdPlan &s, int64_t *f, const char **kernel) {
+    f[0] = s.status; f[1] = s.gx; f[2] = s.gy; f[3] = s.gz; f[4] = s.block; f[5] = s.need; f[6] = s.inst; f[7] = s.silu; f[8] = s.io; f[9] = s.wt; f[10] = s.n_tiles + s.n_seg;
+    f[11] = s.fin_gx; f[12] = s.fin2_gx; f[13] = s.n_slabs + s.n_parts; f[14] = s.ck; f[15] = s.bc; f[16] = s.pa;
+    *kernel = s.kernel;
+    return s.status;
+}
+extern "C" int plan_an(const zigma_norm_params_t *p, int64_t *f, const char **k) { return norm(plan_add_norm(*p), f, k); }
+extern "C" int plan_nb(const zigma_norm_bwd_params_t *p, int64_t *f, const char **k) { return norm(plan_add_norm_bwd(*p), f, k); }
+extern "C" int plan_sb(const zigma_scan_bwd_params_t *p, int64_t *f, const char **k) { return bwd(plan_scan_bwd(*p), f, k); }
+extern "C" int plan_cb(const zigma_conv_bwd_params_t *p, int64_t *f, const char **k) { return bwd(plan_conv_bwd(*p), f, k); }
+extern "C" int max_batch() { return kBwdMaxBatch; }
+"""
+_NORM_FIELDS = ("status", "gx", "gy", "gz", "block", "need", "vec", "iters", "lpr", "res32", "w32", "fin_gx")
+_BWD_FIELDS = ("status", "gx", "gy", "gz", "block", "need", "inst", "silu", "io", "wt", "pieces", "fin_gx", "fin2_gx", "parts", "ck", "bc", "pa")   # pieces: tiles | segments; parts: slabs | partials
+
+
+@pytest.fixture(scope="module")
+def bwd_plan():
+    """the four plans of zigma_amd/csrc/norm_plan.h and bwd_plan.h compiled on their own with g++ (no HIP): plan(params) -> status, grids, block,
+    workspace bytes, instantiation, kernel, by the type of the parameter block"""
+    from zigma_amd import _lib
+    L = _compile_plan(_BWD_PLAN_DRIVER)
+    by_type = {t: _plan_caller(L, t, names, fn, ctypes.c_int64) for t, fn, names in (
+        (_lib.NormParams, "plan_an", _NORM_FIELDS), (_lib.NormBwdParams, "plan_nb", _NORM_FIELDS), (_lib.ScanBwdParams, "plan_sb", _BWD_FIELDS),
+        (_lib.ConvBwdParams, "plan_cb", _BWD_FIELDS))}
+    plan = lambda P: by_type[type(P)](P)
+    plan.max_batch = L.max_batch()
+    return plan
+
+
+def _bwd_plan_case_table(bwd_plan):
+    """the four plans (compiled) on the parameter block the product's builders fill for every case of the table: status, last kernel, and for add-norm
+    the instantiation; the built library's host-only queries (no device here) answer the same.  Every case in ONE test: all that differ are reported
+    together; tests/test_gpu_bwd_plan_query.py runs them one by one."""
+    import bwd_plan_cases as bc
+    from zigma_amd import _lib
+    wrong = {}
+    for name, (_, _, want) in bc.CASES.items():
+        fn, P, _, _ = bc.block(name, "cpu")
+        got = bwd_plan(P)
+        if not (got["status"], got["kernel"]) == tuple(want) == _lib.plan(fn, P):
+            wrong[name] = (got["status"], got["kernel"], _lib.plan(fn, P), tuple(want))
+        elif name in bc.INSTANTIATION and (got["vec"], got["iters"], got["lpr"]) != bc.INSTANTIATION[name]:
+            wrong[name] = (got["vec"], got["iters"], got["lpr"])
+    assert not wrong, wrong
+    assert {c[0] for c in bc.CASES.values()} == set(bc.ENTRY) and len(bc.ENTRY) == 4
+    assert set(bc.INSTANTIATION) == {n for n, c in bc.CASES.items() if c[2].kernel and c[0].startswith("add_norm")}
+
+
+def _bwd_plan_geometry(bwd_plan):
+    """grids, blocks, dtype slots, template switches and workspace sections of the serving leaves against the closed forms of the kernels' headers"""
+    import bwd_plan_cases as bc
+
+    def geometry(name, *fields):
+        got = bwd_plan(bc.block(name, "cpu")[1])
+        return tuple(got[f] for f in fields)
+    an = ("gx", "block", "res32", "w32")
+    assert geometry("an_served_rows_4_cols_128", *an) == (1, 256, 0, 0) and geometry("an_served_rows_5_cols_128", *an) == (2, 256, 0, 0)      # 16 rows | 4 rows per workgroup
+    assert geometry("an_served_full_fp32_residual", *an) == (1, 256, 1, 0) and geometry("an_served_full_fp32_residual_fp32_weight_f16", *an) == (1, 256, 1, 1)
+    assert geometry("an_served_fp32_weight_16_bytes_in", *an) == (1, 256, 0, 1) and geometry("an_served_f32", *an) == (1, 256, 1, 1)
+    nb = ("gx", "block", "fin_gx", "need", "res32", "w32")
+    assert geometry("nb_served_cols_768", *nb) == (2, 256, 24, 2 * 2 * 768 * 4, 1, 0) and geometry("nb_served_cols_772", *nb) == (2, 256, 26, 2 * 2 * 772 * 4, 1, 0)
+    assert geometry("nb_served_2049_rows_of_8_f16_no_weight_dx_only", *nb) == (512, 256, 2, 512 * 2 * 8 * 4, 0, 0)
+    assert geometry("nb_served_f32_dresidual_only", "res32", "w32") == (1, 1)
+    sb = ("gx", "gy", "block", "inst", "io", "pieces", "parts", "fin_gx", "fin2_gx", "ck", "bc", "pa", "need")
+    from zigma_amd._lib import BF16, F16, F32
+    assert geometry("sb_served_16_states", *sb) == (1, 2, 256, 4, BF16, 2, 1, 8, 5, 2 * 2 * 16 * 64, 2 * 32 * 2 * 16, 2 * 64 * 18, (4096 + 2048 + 2304) * 4)
+    assert geometry("sb_served_8_states", *sb) == (1, 2, 128, 2, BF16, 2, 1, 4, 3, 2 * 2 * 8 * 64, 2 * 32 * 2 * 8, 2 * 64 * 10, (2048 + 1024 + 1280) * 4)
+    assert geometry("sb_served_8_states_forward_checkpoints", "ck", "need") == (0, (1024 + 1280) * 4)
+    assert geometry("sb_served_f32_33_steps", *sb) == (1, 2, 256, 4, F32, 3, 1, 9, 5, 2 * 3 * 16 * 64, 2 * 48 * 2 * 16, 2 * 64 * 18, (6144 + 3072 + 2304) * 4)
+    assert geometry("sb_served_f16_reset_period_16", "io", "inst") == (F16, 4)
+    cb = ("gx", "gy", "gz", "block", "inst", "silu", "io", "wt", "pieces", "parts", "fin_gx", "need")
+    assert geometry("cb_served_width_4_silu_bias", *cb) == (1, 1, 2, 64, 4, 1, BF16, BF16, 1, 2, 1, 2 * 8 * 5 * 4)
+    assert geometry("cb_served_width_3_no_silu", *cb) == (1, 1, 2, 64, 3, 0, BF16, BF16, 1, 2, 1, 2 * 8 * 4 * 4)
+    assert geometry("cb_served_width_2_no_bias_fp32_taps", *cb) == (1, 1, 2, 64, 2, 1, BF16, F32, 1, 2, 1, 2 * 8 * 3 * 4)
+    assert geometry("cb_served_f16_width_4_no_silu_fp32_taps", "inst", "silu", "io", "wt") == (4, 0, F16, F32)
+    assert geometry("cb_served_129_positions_row_table", *cb) == (1, 2, 2, 64, 4, 1, BF16, BF16, 2, 4, 1, 2 * 2 * 8 * 5 * 4)
+
+
+def _norm_case_block(c, lead, tail, pitch, windows):
+    """the block tests/test_gpu_outer_fwd.py builds for a case of outer_fwd_cases.norm_cases(), on allocator-aligned placeholder addresses"""
+    import outer_fwd_cases as oc
+    from zigma_amd import _lib
+    ids, es = {"f32": _lib.F32, "f16": _lib.F16, "bf16": _lib.BF16}, {"f32": 4, "f16": 2, "bf16": 2}
+    u, at = oc.norm_uses(c), lead + c["align"]
+    P = _lib.NormParams()
+    P.rows, P.cols, P.rows_per_batch, P.flags = c["rows"], c["cols"], c["rpb"], c["flags"]
+    P.x_dtype, P.res_dtype, P.w_dtype, P.mod_dtype = ids[c["xk"]], ids[c["rk"]], ids[c["wk"]], ids[c["xk"]]
+    k = [0]
+
+    def put(field, kind, stride=None):
+        k[0] += 1
+        setattr(P, field, k[0] * _lib.FRESH_ADDRESS + at * es[kind])
+        if stride:
+            setattr(P, stride, pitch)
+    put("x", c["xk"], "x_row_stride")
+    for use, field, kind, stride in (("branch", "branch", c["xk"], "branch_row_stride"), ("x_out", "x_out", c["xk"], "x_out_row_stride"),
+                                     ("res", "residual", c["rk"], "res_row_stride"), ("res_out", "residual_out", c["rk"], "res_out_row_stride"),
+                                     ("y_out", "y_out", c["xk"], "y_row_stride")):
+        if u[use]:
+            put(field, kind, stride)
+    if c["form"] != "ln":
+        put("weight", c["wk"])
+    if c["form"] == "ln-wb":
+        put("bias", c["wk"])
+    if u["branch"] or u["mod"]:
+        base = 20 * _lib.FRESH_ADDRESS + at * es[c["xk"]]
+        P.mod_batch_stride = lead + c["align"] + 6 * c["cols"] + tail
+        if u["mod"]:
+            put("y_mod", c["xk"], "y_mod_row_stride")
+            P.shift, P.scale = (base + w * c["cols"] * es[c["xk"]] for w in windows[:2])
+        if u["branch"]:
+            P.gate = base + windows[2] * c["cols"] * es[c["xk"]]
+    return P, [es[c["xk"]], es[c["rk"]], es[c["wk"]], es[c["xk"]]]
+
+
+def _add_norm_plan_agrees_with_both_hand_restatements(bwd_plan):
+    """plan_add_norm()'s (VEC, ITERS, LPR) and kernel name against the two independent restatements of the selection the tests keep —
+    kernel_standins._norm_instantiation (from a block) and outer_fwd_cases.norm_branch (from a case) — on every case of outer_fwd_cases.norm_cases() and on
+    a seeded sweep of 4000 blocks: cols 1 ... 4200, every pitch and offset residue mod 8, every dtype slot; on its first half every operand shares one
+    offset (a case of norm_branch), on its second every pointer and pitch draws its own"""
+    import kernel_standins as ks
+    import outer_fwd_cases as oc
+    from zigma_amd import _lib
+
+    def check(P, es, c=None):
+        got = bwd_plan(P)
+        try:
+            inst, name = ks._norm_instantiation(P, es)
+        except Exception:
+            inst, name = None, None
+        assert ((got["vec"], got["iters"], got["lpr"]) if got["kernel"] else None, got["kernel"]) == (inst, name), (c, got, inst, name)
+        if c is not None:
+            assert oc.norm_branch(c) == inst and (inst is None or oc.norm_kernel_name(c) == name), (c, inst, name)
+        return inst
+    seen = set()
+    for c in oc.norm_cases():
+        P, es = _norm_case_block(c, oc.LEAD, oc.TAIL, oc.norm_pitch(c), oc.MOD_WINDOWS)
+        assert check(P, es, c) == c["branch"]
+        seen.add(c["branch"])
+    rng = np.random.default_rng(20251)
+    kinds = [(x, r, w) for x in ("f32", "bf16", "f16") for r in ("f32", x) for w in ("f32", x)]
+    for i in range(4000):
+        xk, rk, wk = kinds[i % len(kinds)]
+        cols = int(rng.integers(1, 4201)) if i % 4 else int(rng.integers(1, 34)) * 128
+        c = dict(xk=xk, rk=rk, wk=wk, cols=cols, rows=int(rng.integers(1, 9)), rpb=1, flags=int(rng.integers(0, 2)) if i % 8 == 0 else 0,
+                 align=int(rng.integers(0, 8)) if i % 3 else 0, form=oc.NORM_FORMS[i % 4], opt=oc.NORM_OPTIONS[i % 9])
+        P, es = _norm_case_block(c, oc.LEAD, oc.TAIL, oc.norm_pitch(c), oc.MOD_WINDOWS)
+        if i < 2000:
+            seen.add(check(P, es, c))
+            continue
+        for field, ctype in P._fields_:           # every pointer in use and every pitch: its own residue mod 8 elements
+            if ctype is _lib.vp and getattr(P, field):
+                setattr(P, field, getattr(P, field) + int(rng.integers(0, 8)) * es[{"residual": 1, "residual_out": 1, "weight": 2, "bias": 2}.get(field, 0)] * (i % 2))
+            elif field.endswith("_stride"):
+                setattr(P, field, getattr(P, field) + int(rng.integers(0, 8)) * (i % 3 == 0))
+        seen.add(check(P, es))
+    assert seen == {None, (8, 2, 64), (4, 4, 64), (4, 16, 64), (1, 16, 64), (1, 64, 64)} | {(8, it, 16) for it in range(1, 9)}
+
+
+def _add_norm_bwd_plan_agrees_with_the_recorded_selection(bwd_plan):
+    """plan_add_norm_bwd()'s (VEC, ITERS) against bwd_fuzz_cases.norm_branch — the selection the backward sweep records per case — on every case of its table
+    and on a seeded sweep: cols 1 ... 2100, every pitch pad mod 8, every dtype slot"""
+    import bwd_fuzz_cases as fc
+    from zigma_amd import _lib
+    ids, es = {"f32": _lib.F32, "f16": _lib.F16, "bf16": _lib.BF16}, {"f32": 4, "f16": 2, "bf16": 2}
+
+    def check(xk, rk, wk, rows, cols, pad):
+        P = _lib.NormBwdParams()
+        P.rows, P.cols, P.x_dtype, P.res_dtype, P.w_dtype = rows, cols, ids[xk], ids[rk], ids[wk or xk]
+        P.xsum_row_stride = P.dy_row_stride = P.dres_out_row_stride = cols + pad
+        P.dx_row_stride = P.dres_row_stride = cols
+        for k, field in enumerate(("xsum", "dy", "dresidual_out", "dx", "dresidual", "dweight", "dbias", "workspace") + (("weight",) if wk else ())):
+            setattr(P, field, (k + 1) * _lib.FRESH_ADDRESS)
+        P.workspace_bytes = 1 << 40
+        got = bwd_plan(P)
+        want = fc.norm_branch(cols, pad)
+        assert ((got["vec"], got["iters"]) if got["kernel"] else None) == want and got["status"] == (0 if want else -2), (xk, rk, wk, rows, cols, pad, got)
+        return want
+    seen = set()
+    for c in fc.norm_cases():
+        assert check(c["xk"], c["rk"], c["wk"], c["rows"], c["cols"], c["pitch_pad"]) == c["branch"]
+        seen.add(c["branch"])
+    rng = np.random.default_rng(20252)
+    for i in range(3000):
+        xk, rk, wk = fc.NORM_DTYPES[i % 9]
+        seen.add(check(xk, rk, wk if i % 5 else None, int(rng.integers(1, 3000)), int(rng.integers(1, 2101)) if i % 4 else int(rng.integers(1, 526)) * 4, int(rng.integers(0, 8)) * (i % 2)))
+    assert seen == set(fc.NORM_BRANCHES) | {None}
+
+
+def _bwd_workspace_bytes_answer_as_the_plans_do(bwd_plan):
+    """the three *_workspace_bytes exports are the `need` of their plans, and both are the closed forms of the launchers they replace (bwd_ws_layout, nb_grid,
+    the conv segment count): a seeded sweep up to batch 65535, seqlen 1 ... 4097, dim in multiples of 4, and the sizes that answer 0"""
+    from zigma_amd import _lib
+    L = _lib.lib()
+    rng = np.random.default_rng(20253)
+    up = lambda a, b: -(-a // b)
+    pick = lambda n, *edges: int(edges[int(rng.integers(0, len(edges)))]) if rng.integers(0, 4) == 0 else int(rng.integers(1, n + 1))
+    for i in range(3000):
+        batch, seqlen, dim = pick(65535, 1, 65535, 0, -1), pick(4097, 1, 16, 17, 128, 129, 4096, 4097, 0), 4 * pick(1024, 1, 16, 0)
+        S = _lib.ScanBwdParams()
+        S.batch, S.dim, S.seqlen, S.dstate, S.checkpoints = batch, dim, seqlen, (16, 8, 16, 0)[i % 4], (None, 1 << 30)[i % 2]
+        want = 0
+        if min(batch, dim, seqlen, S.dstate) > 0:
+            tiles, slabs = up(seqlen, 16), dim // 64
+            want = 4 * ((0 if S.checkpoints else batch * slabs * tiles * S.dstate * 64) + batch * slabs * tiles * 16 * 2 * S.dstate + batch * dim * (S.dstate + 2))
+        assert L.zigma_selective_scan_bwd_workspace_bytes(ctypes.byref(S)) == bwd_plan(S)["need"] == want, (batch, dim, seqlen, S.dstate)
+        Cv = _lib.ConvBwdParams()
+        Cv.batch, Cv.dim, Cv.seqlen, Cv.width = batch, dim, seqlen, (4, 3, 2)[i % 3]
+        want = batch * up(seqlen, 128) * dim * (Cv.width + 1) * 4 if min(batch, dim, seqlen) > 0 else 0
+        assert L.zigma_causal_conv1d_bwd_workspace_bytes(ctypes.byref(Cv)) == bwd_plan(Cv)["need"] == want, (batch, dim, seqlen, Cv.width)
+        N = _lib.NormBwdParams()
+        N.rows, N.cols = batch * (1, 7, 2048)[i % 3] if i % 11 else pick(2049, 2047, 2048, 2049, 0, -1), pick(2100, 1, 2048, 2049, 0)
+        want = max(1, min(512, up(N.rows, 4))) * 2 * N.cols * 4 if N.rows > 0 and N.cols > 0 else 0
+        assert L.zigma_add_norm_bwd_workspace_bytes(ctypes.byref(N)) == bwd_plan(N)["need"] == want, (N.rows, N.cols)
+    for fn in ("zigma_selective_scan_bwd", "zigma_causal_conv1d_bwd", "zigma_add_norm_bwd"):
+        assert getattr(L, fn + "_workspace_bytes")(None) == 0
+
+
+def _backward_batch_limit_is_the_one_python_constant(bwd_plan):
+    """both backward plans serve batch == _lib.GRID_DIM_MAX and refuse one more (ZIGMA_ERR_SHAPE): the constant the bindings slice the batch by, and
+    z_preactivated_eligible() reads, is the plans' kBwdMaxBatch"""
+    import bwd_plan_cases as bc
+    from zigma_amd import _lib
+    assert bwd_plan.max_batch == _lib.GRID_DIM_MAX == 65535
+    for name in ("sb_served_16_states", "cb_served_width_4_silu_bias"):
+        fn, P, _, _ = bc.block(name, "cpu")
+        kernel = bc.CASES[name][2].kernel
+        P.workspace_bytes = 1 << 50                 # (a query dereferences nothing)
+        P.batch = _lib.GRID_DIM_MAX
+        assert (bwd_plan(P)["status"], bwd_plan(P)["kernel"]) == (0, kernel) == _lib.plan(fn, P)
+        P.batch = _lib.GRID_DIM_MAX + 1
+        assert (bwd_plan(P)["status"], bwd_plan(P)["kernel"]) == (-2, None) == _lib.plan(fn, P)
+
+
+def test_bwd_plans(bwd_plan, libpath):
+    """add-norm in both directions and the scan and conv backward: the case table, the geometry of the serving leaves, the add-norm selections against the
+    restatements the tests keep, the three size exports and the batch limit — the six checks above in ONE test, like the nine plans of
+    test_outer_plan_case_table (an assertion names the check it belongs to by its frame)"""
+    for check in (_bwd_plan_case_table, _bwd_plan_geometry, _add_norm_plan_agrees_with_both_hand_restatements,
+                  _add_norm_bwd_plan_agrees_with_the_recorded_selection, _bwd_workspace_bytes_answer_as_the_plans_do,
+                  _backward_batch_limit_is_the_one_python_constant):
+        check(bwd_plan)

@@ -251,7 +251,8 @@ EXPORTS = ("zigma_sde_step_fwd", "zigma_sde_advance", "zigma_optim_grad_sumsq", 
            "zigma_selective_scan_fwd_plan", "zigma_causal_conv1d_fwd_plan", "zigma_conv_x_proj_fwd_plan", "zigma_x_proj_fwd_plan",
            "zigma_dt_proj_softplus_fwd_plan", "zigma_linear_fwd_plan", "zigma_norm_linear_fwd_plan", "zigma_linear_f32_split_plan",
            "zigma_patch_embed_fwd_plan", "zigma_timestep_embed_fwd_plan", "zigma_skinny_linear_fwd_plan", "zigma_final_layer_fwd_plan", "zigma_final_layer_cfg_fwd_plan",
-           "zigma_cross_attn_fwd_plan", "zigma_cross_attn_bwd_plan", "zigma_scale_reduce_bwd_plan", "zigma_linear_wgrad_plan")
+           "zigma_cross_attn_fwd_plan", "zigma_cross_attn_bwd_plan", "zigma_scale_reduce_bwd_plan", "zigma_linear_wgrad_plan",
+           "zigma_add_norm_fwd_plan", "zigma_add_norm_bwd_plan", "zigma_selective_scan_bwd_plan", "zigma_causal_conv1d_bwd_plan")
 
 _lib = None
 
@@ -289,7 +290,9 @@ def lib():
                          ("zigma_norm_linear_fwd", NormLinearParams), ("zigma_linear_f32_split", LinearSplitParams),
                          ("zigma_patch_embed_fwd", PatchEmbedParams), ("zigma_timestep_embed_fwd", TimestepEmbedParams), ("zigma_skinny_linear_fwd", SkinnyParams),
                          ("zigma_final_layer_fwd", FinalLayerParams), ("zigma_final_layer_cfg_fwd", FinalLayerCfgParams), ("zigma_cross_attn_fwd", XAttnParams),
-                         ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_linear_wgrad", LinearWgradParams)):
+                         ("zigma_cross_attn_bwd", XAttnBwdParams), ("zigma_scale_reduce_bwd", GlueBwdParams), ("zigma_linear_wgrad", LinearWgradParams),
+                         ("zigma_add_norm_fwd", NormParams), ("zigma_add_norm_bwd", NormBwdParams), ("zigma_selective_scan_bwd", ScanBwdParams),
+                         ("zigma_causal_conv1d_bwd", ConvBwdParams)):
             fn = getattr(L, name + "_plan")
             fn.argtypes = [C.POINTER(st), C.POINTER(C.c_char_p)]
             fn.restype = C.c_int
@@ -405,6 +408,26 @@ def workspace(fn_name, params, device):
     return ws
 
 
+GRID_DIM_MAX = 65535        # a 16-bit grid dimension: the batch of one zigma_selective_scan_bwd / zigma_causal_conv1d_bwd launch (kBwdMaxBatch of csrc/bwd_plan.h)
+                            # and of the scan's single grid (csrc/scan_plan.h)
+
+
+def sum_over_batch_slices(batch, run):
+    """A batch past GRID_DIM_MAX goes to the backward kernels in slices: run(a, b) launches on samples [a, b) — per-sample outputs land in views of one
+    allocation — and returns its parameter gradients (a tuple; None where there is none) -> their sums over the slices"""
+    total = None
+    for a in range(0, batch, GRID_DIM_MAX):
+        part = run(a, min(a + GRID_DIM_MAX, batch))
+        total = part if total is None else tuple(None if t is None or q is None else t + q for t, q in zip(total, part))
+    return total
+
+
+def checkpoint_shape(batch, dim, seqlen, dstate):
+    """[batch][dim / 64][ceil(seqlen / 16)][dstate][64] fp32: the states before every 16-step tile, which the token-major forward scan writes for
+    zigma_selective_scan_bwd; None where that backward does not take the shape (plan_scan_bwd() of csrc/bwd_plan.h: dim % 64, dstate 8 or 16)"""
+    return (batch, dim // 64, (seqlen + 15) // 16, dstate, 64) if dim % 64 == 0 and dstate in (8, 16) else None
+
+
 _PLAN_FNS = {}
 
 
@@ -413,7 +436,8 @@ def plan(fn_name, params):
     would return and what zigma_last_kernel() would report after it (None: a refusal or an empty call).  The five forward entry points of the Mamba
     inner answer (plan_scan() of csrc/scan_plan.h, the plans of csrc/front_plan.h) and the three of the dense projections (plan_linear() and
     plan_linear_split() of csrc/linear_plan.h, plan_norm_linear() of csrc/norm_linear_plan.h), the operators around the blocks (csrc/outer_plan.h),
-    cross-attention in both directions and the glue backward (csrc/attn_plan.h) and the weight gradient (csrc/wgrad_plan.h).  Host only: nothing is launched or
+    cross-attention in both directions and the glue backward (csrc/attn_plan.h), the weight gradient (csrc/wgrad_plan.h), add-norm in both directions
+    (csrc/norm_plan.h) and the scan and conv backward (csrc/bwd_plan.h).  Host only: nothing is launched or
     dereferenced, so the block may describe tensors that are yet to be allocated."""
     fn = _PLAN_FNS.get(fn_name)
     if fn is None:

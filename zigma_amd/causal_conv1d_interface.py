@@ -3,7 +3,7 @@
 Mirrors the reference's `dis_causal_conv1d/causal_conv1d/causal_conv1d_interface.py`:
     causal_conv1d_fwd  <-> causal_conv1d_cuda.causal_conv1d_fwd   (causal_conv1d.cpp:130-189)
     causal_conv1d_fn   <-> causal_conv1d_fn                       (causal_conv1d_interface.py:37-46)
-Forward only (bwd / update are later scope rows).
+conv_bwd_tok binds the token-major backward (zigma_causal_conv1d_bwd); update is a later scope row.
 """
 import torch
 
@@ -64,6 +64,33 @@ def causal_conv1d_fn(x, weight, bias=None, activation=None):
     return causal_conv1d_raw(x, weight, bias, activation in ["silu", "swish"])
 
 
+def conv_bwd_block(x, weight, bias, dout, silu, x_row_index, dx, dw, db, reset_period=0):
+    """The parameter block of zigma_causal_conv1d_bwd but for its workspace: x, dout, dx (batch, seqlen, dim) with channel stride 1 in one type, weight
+    (dim, width), dw (dim, width) / db (dim) fp32.  Reads shapes, strides, dtypes and addresses only."""
+    Bsz, L, Dm = x.shape
+    if dout.shape != x.shape or x.stride(2) != 1 or dout.stride(2) != 1 or dout.dtype != x.dtype:
+        raise RuntimeError("x, dout must be (batch, seqlen, dim) with channel stride 1 and one dtype")
+    if dx.shape != x.shape or dx.stride(2) != 1 or dx.dtype != x.dtype:
+        raise RuntimeError("dx must be (batch, seqlen, dim) with channel stride 1 and the dtype of x")
+    P = _lib.ConvBwdParams()
+    P.batch, P.dim, P.seqlen, P.width = Bsz, Dm, L, weight.shape[1]
+    P.silu_activation, P.io_dtype, P.w_dtype, P.flags = int(bool(silu)), _lib.dtype_id(x), _lib.dtype_id(weight), 0
+    P.x_batch_stride, P.x_l_stride = x.stride(0), x.stride(1)
+    P.dout_batch_stride, P.dout_l_stride = dout.stride(0), dout.stride(1)
+    P.dx_batch_stride, P.dx_l_stride = dx.stride(0), dx.stride(1)
+    P.weight_c_stride, P.weight_width_stride = weight.stride(0), weight.stride(1)
+    P.x, P.weight, P.bias, P.dout, P.dx = _lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(dout), _lib.ptr(dx)
+    P.dweight, P.dbias = _lib.ptr(dw), _lib.ptr(db)
+    P.reset_period = int(reset_period)
+    if bias is not None and bias.dtype != weight.dtype:
+        raise RuntimeError("bias must have the dtype of weight")
+    if x_row_index is not None:
+        if x_row_index.dtype != torch.int32 or tuple(x_row_index.shape) != (L,) or not x_row_index.is_contiguous():
+            raise RuntimeError("x_row_index must be a contiguous int32 (seqlen,) table")
+        P.x_row_index = _lib.ptr(x_row_index)
+    return P
+
+
 def conv_bwd_tok(x, weight, bias, dout, silu, x_row_index=None, dx=None, reset_period=0):
     """Backward of the token-major causal conv (zigma_causal_conv1d_bwd; reference causal_conv1d_cuda.causal_conv1d_bwd,
     causal_conv1d.cpp:191-283).  x, dout: (batch, seqlen, dim), channel stride 1; dout in SCAN order; x is read through
@@ -71,39 +98,16 @@ def conv_bwd_tok(x, weight, bias, dout, silu, x_row_index=None, dx=None, reset_p
     dbias (dim) f32 or None.  reset_period > 0: independent sequences of that many positions along seqlen, as in the forward."""
     dev = _lib.require_device(x, weight, bias, dout, x_row_index)
     Bsz, L, Dm = x.shape
-    if dout.shape != x.shape or x.stride(2) != 1 or dout.stride(2) != 1 or dout.dtype != x.dtype:
-        raise RuntimeError("x, dout must be (batch, seqlen, dim) with channel stride 1 and one dtype")
-    w = weight.reshape(Dm, -1)
     if dx is None:
         dx = torch.empty(Bsz, L, Dm, device=x.device, dtype=x.dtype)
-    elif dx.shape != x.shape or dx.stride(2) != 1 or dx.dtype != x.dtype:
-        raise RuntimeError("dx must be (batch, seqlen, dim) with channel stride 1 and the dtype of x")
-    if Bsz > 65535:          # one launch rides the batch in a 16-bit grid dimension: slices, parameter gradients summed
-        dw = db = None
-        for a in range(0, Bsz, 65535):
-            b = min(a + 65535, Bsz)
-            _, dwi, dbi = conv_bwd_tok(x[a:b], weight, bias, dout[a:b], silu, x_row_index, dx=dx[a:b], reset_period=reset_period)
-            dw = dwi if dw is None else dw + dwi
-            db = dbi if db is None or dbi is None else db + dbi
+    if Bsz > _lib.GRID_DIM_MAX:
+        dw, db = _lib.sum_over_batch_slices(Bsz, lambda a, b: conv_bwd_tok(x[a:b], weight, bias, dout[a:b], silu, x_row_index, dx=dx[a:b],
+                                                                           reset_period=reset_period)[1:])
         return dx, dw, db
+    w = weight.reshape(Dm, -1)
     dw = torch.zeros(Dm, w.shape[1], device=x.device, dtype=torch.float32)
     db = torch.zeros(Dm, device=x.device, dtype=torch.float32) if bias is not None else None
-    P = _lib.ConvBwdParams()
-    P.batch, P.dim, P.seqlen, P.width = Bsz, Dm, L, w.shape[1]
-    P.silu_activation, P.io_dtype, P.w_dtype, P.flags = int(bool(silu)), _lib.dtype_id(x), _lib.dtype_id(w), 0
-    P.x_batch_stride, P.x_l_stride = x.stride(0), x.stride(1)
-    P.dout_batch_stride, P.dout_l_stride = dout.stride(0), dout.stride(1)
-    P.dx_batch_stride, P.dx_l_stride = dx.stride(0), dx.stride(1)
-    P.weight_c_stride, P.weight_width_stride = w.stride(0), w.stride(1)
-    P.x, P.weight, P.bias, P.dout, P.dx = _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(dout), _lib.ptr(dx)
-    P.dweight, P.dbias = _lib.ptr(dw), _lib.ptr(db)
-    P.reset_period = int(reset_period)
-    if bias is not None and bias.dtype != w.dtype:
-        raise RuntimeError("bias must have the dtype of weight")
-    if x_row_index is not None:
-        if x_row_index.dtype != torch.int32 or x_row_index.shape != (L,) or not x_row_index.is_contiguous():
-            raise RuntimeError("x_row_index must be a contiguous int32 (seqlen,) table")
-        P.x_row_index = _lib.ptr(x_row_index)
+    P = conv_bwd_block(x, w, bias, dout, silu, x_row_index, dx, dw, db, reset_period)
     ws = _lib.workspace("zigma_causal_conv1d_bwd", P, dev)
     _lib.call("zigma_causal_conv1d_bwd", P, dev)
     del ws

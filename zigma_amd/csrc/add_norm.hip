@@ -6,6 +6,7 @@
 // (model_zigma.py:53-54,441-458): the gate*branch residual of the previous sub-layer on the way in,
 // the adaLN modulate on the way out.  Pure HBM streaming: one wave owns one row, the row lives in
 // registers between the statistics and the normalisation, so every operand is read or written once.
+#include "norm_plan.h"
 #include "vec_io.h"
 
 namespace zigma {
@@ -104,85 +105,45 @@ __global__ __launch_bounds__(256) void add_norm_kernel(const zigma_norm_params_t
     }
 }
 
-static bool al(const void *ptr, size_t a) { return ptr == nullptr || reinterpret_cast<uintptr_t>(ptr) % a == 0; }
-
-template <typename XT, typename RT, typename WT, typename MT>
-static int launch_norm(const zigma_norm_params_t &p, hipStream_t stream) {
-    constexpr size_t xs = sizeof(typename XT::raw), rs = sizeof(typename RT::raw), ws = sizeof(typename WT::raw),
-                     ms = sizeof(typename MT::raw);
-    const bool vec = p.cols % 4 == 0 && p.x_row_stride % 4 == 0 && p.branch_row_stride % 4 == 0 && p.x_out_row_stride % 4 == 0 &&
-                     p.res_row_stride % 4 == 0 && p.res_out_row_stride % 4 == 0 && p.y_row_stride % 4 == 0 &&
-                     p.y_mod_row_stride % 4 == 0 && p.mod_batch_stride % 4 == 0 && al(p.x, 4 * xs) && al(p.branch, 4 * xs) &&
-                     al(p.x_out, 4 * xs) && al(p.y_out, 4 * xs) && al(p.y_mod, 4 * xs) && al(p.residual, 4 * rs) &&
-                     al(p.residual_out, 4 * rs) && al(p.weight, 4 * ws) && al(p.bias, 4 * ws) && al(p.gate, 4 * ms) &&
-                     al(p.shift, 4 * ms) && al(p.scale, 4 * ms);
-    const bool vec8 = vec && p.cols % 8 == 0 && p.x_row_stride % 8 == 0 && p.branch_row_stride % 8 == 0 && p.x_out_row_stride % 8 == 0 &&
-                      p.res_row_stride % 8 == 0 && p.res_out_row_stride % 8 == 0 && p.y_row_stride % 8 == 0 &&
-                      p.y_mod_row_stride % 8 == 0 && p.mod_batch_stride % 8 == 0 && al(p.x, 8 * xs) && al(p.branch, 8 * xs) &&
-                      al(p.x_out, 8 * xs) && al(p.y_out, 8 * xs) && al(p.y_mod, 8 * xs) && al(p.residual, 16) &&
-                      al(p.residual_out, 16) && al(p.weight, 8 * ws) && al(p.bias, 8 * ws) && al(p.gate, 8 * ms) &&
-                      al(p.shift, 8 * ms) && al(p.scale, 8 * ms) && xs == 2;
-    dim3 grid(static_cast<unsigned>((static_cast<int64_t>(p.rows) + 3) / 4)), block(256);
-#define ZIGMA_NORM(V_, I_) hipLaunchKernelGGL((add_norm_kernel<XT, RT, WT, MT, V_, I_>), grid, block, 0, stream, p)
-    // four rows per wave where a row is light (16-bit tensors only: 32 us against 44 for the pre-attention LayerNorm of the block);
-    // with the fp32 residual stream in and out a row is 5-6 KB and one row per wave is the faster form (117 against 121 us)
-    const bool light_rows = (p.residual == nullptr && p.residual_out == nullptr) || rs == 2;
-    if (vec8 && light_rows && p.cols % 128 == 0 && p.cols <= 128 * 8 && p.rows % 4 == 0 && !(p.flags & 1)) {
-        const dim3 grid4(static_cast<unsigned>((static_cast<int64_t>(p.rows) / 4 + 3) / 4));
-#define ZIGMA_NORM4(I_) hipLaunchKernelGGL((add_norm_kernel<XT, RT, WT, MT, 8, I_, 16>), grid4, block, 0, stream, p)
-        switch (p.cols / 128) {
-            case 1: ZIGMA_NORM4(1); break;
-            case 2: ZIGMA_NORM4(2); break;
-            case 3: ZIGMA_NORM4(3); break;
-            case 4: ZIGMA_NORM4(4); break;
-            case 5: ZIGMA_NORM4(5); break;
-            case 6: ZIGMA_NORM4(6); break;
-            case 7: ZIGMA_NORM4(7); break;
-            default: ZIGMA_NORM4(8); break;
+template <typename XT, typename RT, typename WT>
+static void launch_norm(const zigma_norm_params_t &p, const NormPlan &s, hipStream_t stream) {
+    const dim3 grid(s.gx), block(s.block);
+#define ZIGMA_NORM(V_, I_, L_) hipLaunchKernelGGL((add_norm_kernel<XT, RT, WT, XT, V_, I_, L_>), grid, block, 0, stream, p)
+    if (s.lpr == 16) {
+        switch (s.iters) {
+            case 1: ZIGMA_NORM(8, 1, 16); break;
+            case 2: ZIGMA_NORM(8, 2, 16); break;
+            case 3: ZIGMA_NORM(8, 3, 16); break;
+            case 4: ZIGMA_NORM(8, 4, 16); break;
+            case 5: ZIGMA_NORM(8, 5, 16); break;
+            case 6: ZIGMA_NORM(8, 6, 16); break;
+            case 7: ZIGMA_NORM(8, 7, 16); break;
+            default: ZIGMA_NORM(8, 8, 16); break;
         }
-#undef ZIGMA_NORM4
-        set_last_kernel("add_norm_v8x4");
-        return check_launch();
-    }
-    if (vec8 && p.cols <= 512 * 2) ZIGMA_NORM(8, 2);       // 16-byte accesses for 16-bit activations
-    else if (vec && p.cols <= 256 * 4) ZIGMA_NORM(4, 4);
-    else if (vec && p.cols <= 256 * 16) ZIGMA_NORM(4, 16);
-    else if (p.cols <= 64 * 16) ZIGMA_NORM(1, 16);
-    else if (p.cols <= 64 * 64) ZIGMA_NORM(1, 64);
-    else return ZIGMA_ERR_SHAPE;
+    } else if (s.vec == 8) ZIGMA_NORM(8, 2, 64);
+    else if (s.vec == 4 && s.iters == 4) ZIGMA_NORM(4, 4, 64);
+    else if (s.vec == 4) ZIGMA_NORM(4, 16, 64);
+    else if (s.iters == 16) ZIGMA_NORM(1, 16, 64);
+    else ZIGMA_NORM(1, 64, 64);
 #undef ZIGMA_NORM
-    set_last_kernel(vec ? "add_norm_v4" : "add_norm_v1");
-    return check_launch();
 }
 
 }  // namespace zigma
 
 using namespace zigma;
 
+extern "C" int zigma_add_norm_fwd_plan(const zigma_norm_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_norm(plan_add_norm(*pp), kernel) : ZIGMA_ERR_NULL;
+}
+
 extern "C" int zigma_add_norm_fwd(const zigma_norm_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();  // a stale error of an unrelated earlier call is not ours to report
     const zigma_norm_params_t &p = *pp;
-    if (!p.x) return ZIGMA_ERR_NULL;
-    if ((p.branch == nullptr) != (p.gate == nullptr)) return ZIGMA_ERR_NULL;
-    if ((p.shift == nullptr) != (p.scale == nullptr)) return ZIGMA_ERR_NULL;
-    if (p.shift && !p.y_mod) return ZIGMA_ERR_NULL;
-    if (!p.y_out && !p.y_mod) return ZIGMA_ERR_NULL;
-    if (p.rows < 0 || p.cols < 1 || p.rows_per_batch < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags & ~1) return ZIGMA_ERR_UNSUPPORTED;          // 1: one row per wave even where four fit (A/B probe)
-    if (p.rows == 0) return ZIGMA_OK;
+    const NormPlan s = plan_add_norm(p);
+    if (!s.kernel) return s.status;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // residual stream is f32 or the activation dtype; weights f32 or activation dtype; keep the
-    // instantiation set small: (x, res, w, mod) in {(T,F32|T,F32|T,T)}
-    ZIGMA_DISPATCH_DTYPE(p.x_dtype, XT, {
-        if (p.mod_dtype != p.x_dtype && (p.gate || p.shift)) return ZIGMA_ERR_DTYPE;
-        const bool res32 = p.res_dtype == ZIGMA_F32, w32 = p.w_dtype == ZIGMA_F32;
-        if (!res32 && p.res_dtype != p.x_dtype) return ZIGMA_ERR_DTYPE;
-        if (!w32 && p.w_dtype != p.x_dtype) return ZIGMA_ERR_DTYPE;
-        if (res32 && w32) return launch_norm<XT, F32, F32, XT>(p, stream);
-        if (res32) return launch_norm<XT, F32, XT, XT>(p, stream);
-        if (w32) return launch_norm<XT, XT, F32, XT>(p, stream);
-        return launch_norm<XT, XT, XT, XT>(p, stream);
-    })
-    return ZIGMA_ERR_DTYPE;
+    ZIGMA_DISPATCH_NORM_SLOT(p.x_dtype, s.res32, s.w32, XT, RT, WT, { launch_norm<XT, RT, WT>(p, s, stream); })
+    set_last_kernel(s.kernel);
+    return check_launch();
 }

@@ -11,10 +11,9 @@
 // adds them in a fixed order (the reference uses float atomics: not reproducible).
 // dx is scattered through the same row table the forward gathered with (a permutation): dx[row[k]] = dx'[k].
 #include "buffer_io.h"
+#include "bwd_plan.h"
 
 namespace zigma {
-
-constexpr int kCbLT = 16, kCbSeg = 128;   // positions per tile / per wave
 
 template <typename IO, typename WT, int W, bool SILU>
 __global__ __launch_bounds__(64) void conv_bwd_tok_kernel(const zigma_conv_bwd_params_t p, float *ws) {
@@ -149,13 +148,13 @@ __global__ __launch_bounds__(256) void conv_bwd_finish(const zigma_conv_bwd_para
 }
 
 template <typename IO, typename WT>
-static void launch_conv_bwd(const zigma_conv_bwd_params_t &p, int n_seg, hipStream_t stream) {
-    dim3 grid((p.dim / 4 + 63) / 64, n_seg, p.batch), block(64);
+static void launch_conv_bwd(const zigma_conv_bwd_params_t &p, const BwdPlan &s, hipStream_t stream) {
+    const dim3 grid(s.gx, s.gy, s.gz), block(s.block);
     float *ws = reinterpret_cast<float *>(p.workspace);
 #define ZIGMA_CB(W_)                                                                                                 \
-    if (p.silu_activation) hipLaunchKernelGGL((conv_bwd_tok_kernel<IO, WT, W_, true>), grid, block, 0, stream, p, ws); \
+    if (s.silu) hipLaunchKernelGGL((conv_bwd_tok_kernel<IO, WT, W_, true>), grid, block, 0, stream, p, ws);          \
     else hipLaunchKernelGGL((conv_bwd_tok_kernel<IO, WT, W_, false>), grid, block, 0, stream, p, ws);
-    switch (p.width) {
+    switch (s.inst) {
         case 2: ZIGMA_CB(2) break;
         case 3: ZIGMA_CB(3) break;
         default: ZIGMA_CB(4) break;
@@ -167,40 +166,23 @@ static void launch_conv_bwd(const zigma_conv_bwd_params_t &p, int n_seg, hipStre
 
 using namespace zigma;
 
-extern "C" int64_t zigma_causal_conv1d_bwd_workspace_bytes(const zigma_conv_bwd_params_t *p) {
-    if (!p || p->batch <= 0 || p->dim <= 0 || p->seqlen <= 0) return 0;
-    const int64_t n_seg = (p->seqlen + kCbSeg - 1) / kCbSeg;
-    return static_cast<int64_t>(p->batch) * n_seg * p->dim * (p->width + 1) * static_cast<int64_t>(sizeof(float));
+extern "C" int64_t zigma_causal_conv1d_bwd_workspace_bytes(const zigma_conv_bwd_params_t *p) { return p ? plan_conv_bwd(*p).need : 0; }
+
+extern "C" int zigma_causal_conv1d_bwd_plan(const zigma_conv_bwd_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_bwd(plan_conv_bwd(*pp), kernel) : ZIGMA_ERR_NULL;
 }
 
 extern "C" int zigma_causal_conv1d_bwd(const zigma_conv_bwd_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_conv_bwd_params_t &p = *pp;
-    if (p.width < 2 || p.width > 4) return ZIGMA_ERR_SHAPE;
-    if (p.batch < 0 || p.dim < 0 || p.seqlen < 0 || p.batch > 65535) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.reset_period < 0 || p.reset_period % kCbLT != 0) return ZIGMA_ERR_SHAPE;
-    if (p.batch == 0 || p.dim == 0 || p.seqlen == 0) return ZIGMA_OK;
-    if (!p.x || !p.weight || !p.dout || !p.dx || !p.dweight) return ZIGMA_ERR_NULL;
-    if (p.bias && !p.dbias) return ZIGMA_ERR_NULL;
-    if (!p.workspace || p.workspace_bytes < zigma_causal_conv1d_bwd_workspace_bytes(pp)) return ZIGMA_ERR_NULL;
-    const int es = p.io_dtype == ZIGMA_F32 ? 4 : 2;
-    auto bad = [&](const void *q, int64_t ls, int64_t bs) {
-        return reinterpret_cast<uintptr_t>(q) % (4 * es) != 0 || ls % 4 != 0 || bs % 4 != 0 || ls < 0 ||
-               (ls * p.seqlen + p.dim) * static_cast<int64_t>(es) >= (int64_t(1) << 31);
-    };
-    if (p.dim % 4 != 0 || bad(p.x, p.x_l_stride, p.x_batch_stride) || bad(p.dout, p.dout_l_stride, p.dout_batch_stride) ||
-        bad(p.dx, p.dx_l_stride, p.dx_batch_stride))
-        return ZIGMA_ERR_STRIDE;
+    const BwdPlan s = plan_conv_bwd(p);
+    if (!s.kernel) return s.status;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const int n_seg = (p.seqlen + kCbSeg - 1) / kCbSeg;
-    ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, {
-        ZIGMA_DISPATCH_DTYPE(p.w_dtype, WT, { launch_conv_bwd<IO, WT>(p, n_seg, stream); })
+    ZIGMA_DISPATCH_DTYPE(s.io, IO, {
+        ZIGMA_DISPATCH_DTYPE(s.wt, WT, { launch_conv_bwd<IO, WT>(p, s, stream); })
     })
-    const int n = p.dim * (p.width + 1);
-    hipLaunchKernelGGL(conv_bwd_finish, dim3((n + 63) / 64), dim3(256), 0, stream, p, reinterpret_cast<const float *>(p.workspace),
-                       n_seg * p.batch);
-    set_last_kernel("conv_bwd_tok");
+    hipLaunchKernelGGL(conv_bwd_finish, dim3(s.fin_gx), dim3(s.fin_block), 0, stream, p, reinterpret_cast<const float *>(p.workspace), s.n_parts);
+    set_last_kernel(s.kernel);
     return check_launch();
 }

@@ -10,11 +10,10 @@
 // One wave per row at a time, each wave walks rows with a fixed stride and keeps its partial dweight / dbias in
 // registers; the partials go to the workspace and a finishing kernel adds them in a fixed order (the reference
 // does the same with one partial per SM, layernorm.py:330-347).
+#include "norm_plan.h"
 #include "vec_io.h"
 
 namespace zigma {
-
-constexpr int kNbWaves = 4, kNbMaxWg = 512;
 
 template <typename XT, typename RT, typename WT, int VEC, int ITERS>
 __global__ __launch_bounds__(64 * kNbWaves) void add_norm_bwd_kernel(const zigma_norm_bwd_params_t p, float *ws) {
@@ -135,60 +134,37 @@ __global__ __launch_bounds__(256) void add_norm_bwd_finish(const zigma_norm_bwd_
     }
 }
 
-static int nb_grid(const zigma_norm_bwd_params_t &p) {
-    const int64_t wg = (static_cast<int64_t>(p.rows) + kNbWaves - 1) / kNbWaves;
-    return static_cast<int>(wg < kNbMaxWg ? (wg < 1 ? 1 : wg) : kNbMaxWg);
-}
-
 template <typename XT, typename RT, typename WT>
-static int launch_norm_bwd(const zigma_norm_bwd_params_t &p, hipStream_t stream) {
-    const int grid = nb_grid(p);
+static void launch_norm_bwd(const zigma_norm_bwd_params_t &p, const NormPlan &s, hipStream_t stream) {
     float *ws = reinterpret_cast<float *>(p.workspace);
-    constexpr size_t xs = sizeof(typename XT::raw), rs = sizeof(typename RT::raw), wsz = sizeof(typename WT::raw);
-    auto al = [](const void *q, size_t a) { return q == nullptr || reinterpret_cast<uintptr_t>(q) % a == 0; };
-    const bool vec = p.cols % 4 == 0 && p.xsum_row_stride % 4 == 0 && p.dy_row_stride % 4 == 0 && p.dres_out_row_stride % 4 == 0 &&
-                     p.dx_row_stride % 4 == 0 && p.dres_row_stride % 4 == 0 && al(p.xsum, 4 * rs) && al(p.dy, 4 * xs) &&
-                     al(p.dresidual_out, 4 * rs) && al(p.dx, 4 * xs) && al(p.dresidual, 4 * rs) && al(p.weight, 4 * wsz);
-#define ZIGMA_NB(V_, I_) hipLaunchKernelGGL((add_norm_bwd_kernel<XT, RT, WT, V_, I_>), dim3(grid), dim3(64 * kNbWaves), 0, stream, p, ws)
-    if (vec && p.cols <= 256 * 3) ZIGMA_NB(4, 3);
-    else if (vec && p.cols <= 256 * 8) ZIGMA_NB(4, 8);
-    else if (p.cols <= 64 * 4) ZIGMA_NB(1, 4);
-    else if (p.cols <= 64 * 12) ZIGMA_NB(1, 12);
-    else if (p.cols <= 64 * 32) ZIGMA_NB(1, 32);
-    else return ZIGMA_ERR_SHAPE;
+#define ZIGMA_NB(V_, I_) hipLaunchKernelGGL((add_norm_bwd_kernel<XT, RT, WT, V_, I_>), dim3(s.gx), dim3(s.block), 0, stream, p, ws)
+    if (s.vec == 4 && s.iters == 3) ZIGMA_NB(4, 3);
+    else if (s.vec == 4) ZIGMA_NB(4, 8);
+    else if (s.iters == 4) ZIGMA_NB(1, 4);
+    else if (s.iters == 12) ZIGMA_NB(1, 12);
+    else ZIGMA_NB(1, 32);
 #undef ZIGMA_NB
-    hipLaunchKernelGGL(add_norm_bwd_finish, dim3(2 * ((p.cols + 63) / 64)), dim3(256), 0, stream, p, ws, grid);
-    set_last_kernel("add_norm_bwd");
-    return check_launch();
+    hipLaunchKernelGGL(add_norm_bwd_finish, dim3(s.fin_gx), dim3(256), 0, stream, p, ws, static_cast<int>(s.gx));
 }
 
 }  // namespace zigma
 
 using namespace zigma;
 
-extern "C" int64_t zigma_add_norm_bwd_workspace_bytes(const zigma_norm_bwd_params_t *p) {
-    if (!p || p->rows <= 0 || p->cols <= 0) return 0;
-    return static_cast<int64_t>(nb_grid(*p)) * 2 * p->cols * static_cast<int64_t>(sizeof(float));
+extern "C" int64_t zigma_add_norm_bwd_workspace_bytes(const zigma_norm_bwd_params_t *p) { return p ? plan_add_norm_bwd(*p).need : 0; }
+
+extern "C" int zigma_add_norm_bwd_plan(const zigma_norm_bwd_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_norm(plan_add_norm_bwd(*pp), kernel) : ZIGMA_ERR_NULL;
 }
 
 extern "C" int zigma_add_norm_bwd(const zigma_norm_bwd_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_norm_bwd_params_t &p = *pp;
-    if (p.rows < 0 || p.cols < 1) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.rows == 0) return ZIGMA_OK;
-    if (!p.xsum || !p.dy || (!p.dx && !p.dresidual)) return ZIGMA_ERR_NULL;
-    if (!p.workspace || p.workspace_bytes < zigma_add_norm_bwd_workspace_bytes(pp)) return ZIGMA_ERR_NULL;
+    const NormPlan s = plan_add_norm_bwd(p);
+    if (!s.kernel) return s.status;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ZIGMA_DISPATCH_DTYPE(p.x_dtype, XT, {
-        const bool res32 = p.res_dtype == ZIGMA_F32, w32 = p.w_dtype == ZIGMA_F32;
-        if (!res32 && p.res_dtype != p.x_dtype) return ZIGMA_ERR_DTYPE;
-        if (!w32 && p.w_dtype != p.x_dtype) return ZIGMA_ERR_DTYPE;
-        if (res32 && w32) return launch_norm_bwd<XT, F32, F32>(p, stream);
-        if (res32) return launch_norm_bwd<XT, F32, XT>(p, stream);
-        if (w32) return launch_norm_bwd<XT, XT, F32>(p, stream);
-        return launch_norm_bwd<XT, XT, XT>(p, stream);
-    })
-    return ZIGMA_ERR_DTYPE;
+    ZIGMA_DISPATCH_NORM_SLOT(p.x_dtype, s.res32, s.w32, XT, RT, WT, { launch_norm_bwd<XT, RT, WT>(p, s, stream); })
+    set_last_kernel(s.kernel);
+    return check_launch();
 }

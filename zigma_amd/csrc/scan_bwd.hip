@@ -22,11 +22,11 @@
 // ahead); every wave reads its 4 states of a step with one wave-uniform ds_read_b128 per operand (a broadcast: no VALU slot, plain
 // operands) and the recurrences run two states per instruction (v_pk_mul_f32 / v_pk_fma_f32), as in scan_tok2_kernel.
 #include "buffer_io.h"
+#include "bwd_plan.h"
 #include "scan_helpers.h"
 
 namespace zigma {
 
-constexpr int kBT = 16;                       // steps per tile
 constexpr int kRedPitch = 260;                // floats per step of the transposition buffer (64 lanes x 4 states + 4)
 
 struct BwdWs {
@@ -381,64 +381,37 @@ __global__ void scan_bwd_finish_params(const zigma_scan_bwd_params_t p, const Bw
     else if (p.ddelta_bias) p.ddelta_bias[d] = acc;
 }
 
-static void bwd_ws_layout(const zigma_scan_bwd_params_t &p, int64_t &ck, int64_t &bc, int64_t &pa) {
-    const int64_t n_tiles = (p.seqlen + kBT - 1) / kBT, slabs = p.dim / 64;
-    ck = p.checkpoints ? 0 : static_cast<int64_t>(p.batch) * slabs * n_tiles * p.dstate * 64;
-    bc = static_cast<int64_t>(p.batch) * slabs * n_tiles * kBT * 2 * p.dstate;
-    pa = static_cast<int64_t>(p.batch) * p.dim * (p.dstate + 2);
-}
-
 template <typename IO>
-static void launch_bwd(const zigma_scan_bwd_params_t &p, const BwdWs &ws, hipStream_t stream) {
-    dim3 grid(p.dim / 64, p.batch);
-    if (p.dstate == 16) hipLaunchKernelGGL((scan_bwd_kernel<IO, 4>), grid, dim3(256), 0, stream, p, ws);
-    else hipLaunchKernelGGL((scan_bwd_kernel<IO, 2>), grid, dim3(128), 0, stream, p, ws);
+static void launch_bwd(const zigma_scan_bwd_params_t &p, const BwdPlan &s, const BwdWs &ws, hipStream_t stream) {
+    const dim3 grid(s.gx, s.gy), block(s.block);
+    if (s.inst == 4) hipLaunchKernelGGL((scan_bwd_kernel<IO, 4>), grid, block, 0, stream, p, ws);
+    else hipLaunchKernelGGL((scan_bwd_kernel<IO, 2>), grid, block, 0, stream, p, ws);
 }
 
 }  // namespace zigma
 
 using namespace zigma;
 
-extern "C" int64_t zigma_selective_scan_bwd_workspace_bytes(const zigma_scan_bwd_params_t *p) {
-    if (!p || p->batch <= 0 || p->dim <= 0 || p->seqlen <= 0 || p->dstate <= 0) return 0;
-    int64_t ck, bc, pa;
-    bwd_ws_layout(*p, ck, bc, pa);
-    return (ck + bc + pa) * static_cast<int64_t>(sizeof(float));
+extern "C" int64_t zigma_selective_scan_bwd_workspace_bytes(const zigma_scan_bwd_params_t *p) { return p ? plan_scan_bwd(*p).need : 0; }
+
+extern "C" int zigma_selective_scan_bwd_plan(const zigma_scan_bwd_params_t *pp, const char **kernel) {
+    return pp && kernel ? query_bwd(plan_scan_bwd(*pp), kernel) : ZIGMA_ERR_NULL;
 }
 
 extern "C" int zigma_selective_scan_bwd(const zigma_scan_bwd_params_t *pp, void *stream_) {
     if (!pp) return ZIGMA_ERR_NULL;
     (void)hipGetLastError();
     const zigma_scan_bwd_params_t &p = *pp;
-    if (p.batch < 0 || p.dim < 0 || p.seqlen < 0) return ZIGMA_ERR_SHAPE;
-    if (p.flags != 0) return ZIGMA_ERR_UNSUPPORTED;
-    if (p.dim % 64 != 0 || (p.dstate != 16 && p.dstate != 8) || p.batch > 65535) return ZIGMA_ERR_SHAPE;
-    if (p.reset_period < 0 || p.reset_period % kBT != 0) return ZIGMA_ERR_SHAPE;
-    if (p.batch == 0 || p.dim == 0 || p.seqlen == 0) return ZIGMA_OK;   // nothing to write (parameter gradients: caller zero-fills)
-    if (!p.u || !p.delta || !p.A || !p.B || !p.C || !p.dout || !p.du || !p.ddelta || !p.dA || !p.dB || !p.dC) return ZIGMA_ERR_NULL;
-    if (p.z && (!p.out || !p.dz)) return ZIGMA_ERR_NULL;
-    if ((p.D && !p.dD) || (p.delta_bias && !p.ddelta_bias)) return ZIGMA_ERR_NULL;
-    if (!p.workspace || p.workspace_bytes < zigma_selective_scan_bwd_workspace_bytes(pp)) return ZIGMA_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(p.workspace) % 16 != 0) return ZIGMA_ERR_STRIDE;
-    const int es = p.io_dtype == ZIGMA_F32 ? 4 : 2;
-    const int64_t lim = (int64_t(1) << 31) - 1;
-    const int64_t strides[] = {p.u_l_stride, p.delta_l_stride, p.z_l_stride, p.out_l_stride, p.dout_l_stride, p.du_l_stride,
-                               p.ddelta_l_stride, p.dz_l_stride, p.B_l_stride, p.C_l_stride};
-    for (int64_t s : strides)
-        if (s < 0 || (p.seqlen - 1) * s * es + static_cast<int64_t>(p.dim) * es > lim) return ZIGMA_ERR_STRIDE;
-    int64_t ck, bc, pa;
-    bwd_ws_layout(p, ck, bc, pa);
+    const BwdPlan s = plan_scan_bwd(p);
+    if (!s.kernel) return s.status;
     BwdWs ws;
     ws.ck = reinterpret_cast<float *>(p.workspace);
-    ws.bc = ws.ck + ck;
-    ws.pa = ws.bc + bc;
+    ws.bc = ws.ck + s.ck;
+    ws.pa = ws.bc + s.bc;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    ZIGMA_DISPATCH_DTYPE(p.io_dtype, IO, { launch_bwd<IO>(p, ws, stream); })
-    const int n_tiles = (p.seqlen + kBT - 1) / kBT, n_slabs = p.dim / 64;
-    const int64_t nbc = static_cast<int64_t>(p.batch) * p.seqlen * 2 * p.dstate;
-    hipLaunchKernelGGL(scan_bwd_finish_bc, dim3(static_cast<unsigned>((nbc + 255) / 256)), dim3(256), 0, stream, p, ws, n_slabs, n_tiles);
-    const int64_t npa = static_cast<int64_t>(p.dim) * (p.dstate + 2);
-    hipLaunchKernelGGL(scan_bwd_finish_params, dim3(static_cast<unsigned>((npa + 255) / 256)), dim3(256), 0, stream, p, ws);
-    set_last_kernel("scan_bwd_tok");
+    ZIGMA_DISPATCH_DTYPE(s.io, IO, { launch_bwd<IO>(p, s, ws, stream); })
+    hipLaunchKernelGGL(scan_bwd_finish_bc, dim3(s.fin_gx), dim3(s.fin_block), 0, stream, p, ws, s.n_slabs, s.n_tiles);
+    hipLaunchKernelGGL(scan_bwd_finish_params, dim3(s.fin2_gx), dim3(s.fin_block), 0, stream, p, ws);
+    set_last_kernel(s.kernel);
     return check_launch();
 }

@@ -179,6 +179,15 @@ void set_last_kernel(const char *name);
         default: return ZIGMA_ERR_DTYPE;                                   \
     }
 
+// add-norm in both directions: x in any of the three types, the residual stream and the weight in fp32 (RES32 / W32: the slot of csrc/norm_plan.h) or in x's
+#define ZIGMA_DISPATCH_NORM_SLOT(DT, RES32, W32, XT, RT, WT, ...)                               \
+    ZIGMA_DISPATCH_DTYPE(DT, XT, {                                                                \
+        if ((RES32) && (W32)) { using RT = ::zigma::F32; using WT = ::zigma::F32; __VA_ARGS__; } \
+        else if (RES32) { using RT = ::zigma::F32; using WT = XT; __VA_ARGS__; }                 \
+        else if (W32) { using RT = XT; using WT = ::zigma::F32; __VA_ARGS__; }                   \
+        else { using RT = XT; using WT = XT; __VA_ARGS__; }                                      \
+    })
+
 // the matrix-core kernels: the two 16-bit types only
 #define ZIGMA_DISPATCH_16BIT(DT, T, ...)                                   \
     switch (DT) {                                                          \

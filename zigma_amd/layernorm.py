@@ -12,9 +12,11 @@ from . import _lib
 NORM_FLAGS = 0      # 1: one row per wave even where four fit (A/B probe; tools set it directly)
 
 
-def _norm_call(x2, weight, bias, residual2, eps, is_rms, residual_dtype, *, rows_per_batch=None, branch=None,
-               gate=None, x_out=None, shift=None, scale=None, want_y=True, want_res=None):
-    dev = _lib.require_device(x2, weight, bias, residual2, branch, gate, shift, scale)
+def norm_block(x2, weight, bias, residual2, eps, is_rms, residual_dtype, *, rows_per_batch=None, branch=None, gate=None, x_out=None, shift=None,
+               scale=None, y=None, res_out=None, y_mod=None):
+    """The parameter block of zigma_add_norm_fwd: x2, branch, x_out, y, y_mod (rows, cols) rows in one type, residual2 / res_out in the residual stream's
+    (residual_dtype where there is no residual2; None: x's), gate / shift / scale (batch, cols) rows.  An output that is None is not written.  Reads
+    shapes, strides, dtypes and addresses only, so a description of a tensor that is yet to be allocated serves as well as the tensor."""
     rows, cols = x2.shape
     P = _lib.NormParams()
     P.rows, P.cols = rows, cols
@@ -22,18 +24,13 @@ def _norm_call(x2, weight, bias, residual2, eps, is_rms, residual_dtype, *, rows
     P.is_rms, P.eps, P.flags = int(is_rms), float(eps), NORM_FLAGS
     P.x_dtype = _lib.dtype_id(x2)
     P.x, P.x_row_stride = _lib.ptr(x2), x2.stride(0)
-    y = y_mod = res_out = None
-    if want_y:
-        y = torch.empty(rows, cols, device=x2.device, dtype=x2.dtype)
+    if y is not None:
         P.y_out, P.y_row_stride = _lib.ptr(y), y.stride(0)
     if residual2 is not None:
         P.residual, P.res_row_stride = _lib.ptr(residual2), residual2.stride(0)
         residual_dtype = residual2.dtype
     P.res_dtype = _lib._DT.get(residual_dtype if residual_dtype is not None else x2.dtype)
-    if want_res is None:
-        want_res = residual2 is not None or (residual_dtype is not None and residual_dtype != x2.dtype)
-    if want_res:
-        res_out = torch.empty(rows, cols, device=x2.device, dtype=residual_dtype or x2.dtype)
+    if res_out is not None:
         P.residual_out, P.res_out_row_stride = _lib.ptr(res_out), res_out.stride(0)
     P.w_dtype = _lib.dtype_id(weight) if weight is not None else P.x_dtype
     if weight is not None:
@@ -49,13 +46,27 @@ def _norm_call(x2, weight, bias, residual2, eps, is_rms, residual_dtype, *, rows
         if x_out is not None:
             P.x_out, P.x_out_row_stride = _lib.ptr(x_out), x_out.stride(0)
     if shift is not None:
-        y_mod = torch.empty(rows, cols, device=x2.device, dtype=x2.dtype)
         P.shift, P.scale = _lib.ptr(shift), _lib.ptr(scale)
         if shift.stride(0) != scale.stride(0) or (gate is not None and gate.stride(0) != shift.stride(0)):
             raise RuntimeError("gate / shift / scale must share a row pitch")
         P.mod_batch_stride = shift.stride(0)
         P.y_mod, P.y_mod_row_stride = _lib.ptr(y_mod), y_mod.stride(0)
-    _lib.call("zigma_add_norm_fwd", P, dev)
+    return P
+
+
+def _norm_call(x2, weight, bias, residual2, eps, is_rms, residual_dtype, *, rows_per_batch=None, branch=None,
+               gate=None, x_out=None, shift=None, scale=None, want_y=True, want_res=None):
+    dev = _lib.require_device(x2, weight, bias, residual2, branch, gate, shift, scale)
+    if residual2 is not None:
+        residual_dtype = residual2.dtype
+    if want_res is None:
+        want_res = residual2 is not None or (residual_dtype is not None and residual_dtype != x2.dtype)
+    rows, cols = x2.shape
+    y = torch.empty(rows, cols, device=x2.device, dtype=x2.dtype) if want_y else None
+    res_out = torch.empty(rows, cols, device=x2.device, dtype=residual_dtype or x2.dtype) if want_res else None
+    y_mod = torch.empty(rows, cols, device=x2.device, dtype=x2.dtype) if shift is not None else None
+    _lib.call("zigma_add_norm_fwd", norm_block(x2, weight, bias, residual2, eps, is_rms, residual_dtype, rows_per_batch=rows_per_batch, branch=branch,
+                                                gate=gate, x_out=x_out, shift=shift, scale=scale, y=y, res_out=res_out, y_mod=y_mod), dev)
     return y, res_out, y_mod
 
 
@@ -79,12 +90,9 @@ def _layer_norm_fwd(x, weight, bias, residual, eps, prenorm, residual_in_fp32, i
     return y.reshape(shape), (res_out.reshape(shape) if res_out is not None else x)
 
 
-def norm_bwd(xsum, weight, dy, dresidual_out, eps, is_rms, *, x_dtype, want_dx=True, want_dres=False, has_bias=False):
-    """zigma_add_norm_bwd (reference _layer_norm_bwd, layernorm.py:275-377).  xsum: the normalised tensor (..., cols);
-    returns dx (x_dtype) | None, dresidual (xsum.dtype) | None, dweight f32 | None, dbias f32 | None."""
-    dev = _lib.require_device(xsum, weight, dy, dresidual_out)
-    shape = xsum.shape
-    s2, dy2 = _flat(xsum), _flat(dy)
+def norm_bwd_block(s2, weight, dy2, dr2, eps, is_rms, *, x_dtype, dx=None, dres=None, dw=None, db=None):
+    """The parameter block of zigma_add_norm_bwd but for its workspace: s2 (the normalised tensor), dr2, dres (rows, cols) rows in the residual stream's
+    type, dy2, dx in x_dtype, weight (cols) contiguous, dw / db (cols) fp32.  Reads shapes, strides, dtypes and addresses only."""
     rows, cols = s2.shape
     P = _lib.NormBwdParams()
     P.rows, P.cols, P.is_rms, P.eps, P.flags = rows, cols, int(is_rms), float(eps), 0
@@ -93,26 +101,33 @@ def norm_bwd(xsum, weight, dy, dresidual_out, eps, is_rms, *, x_dtype, want_dx=T
     P.xsum, P.xsum_row_stride, P.dy, P.dy_row_stride = _lib.ptr(s2), s2.stride(0), _lib.ptr(dy2), dy2.stride(0)
     if dy2.dtype != x_dtype:
         raise RuntimeError("dy must have the dtype of the normalised output")
-    dx = dres = dw = db = None
-    if weight is not None:
-        weight = weight.contiguous()          # kept alive in this local until after the launch
-        P.weight = _lib.ptr(weight)
-        dw = torch.zeros(cols, device=xsum.device, dtype=torch.float32)
-        P.dweight = _lib.ptr(dw)
-    if has_bias:
-        db = torch.zeros(cols, device=xsum.device, dtype=torch.float32)
-        P.dbias = _lib.ptr(db)
-    if dresidual_out is not None:
-        dr2 = _flat(dresidual_out)
+    P.weight, P.dweight, P.dbias = _lib.ptr(weight), _lib.ptr(dw), _lib.ptr(db)
+    if dr2 is not None:
         if dr2.dtype != s2.dtype:
             raise RuntimeError("dresidual_out must have the dtype of the residual stream")
         P.dresidual_out, P.dres_out_row_stride = _lib.ptr(dr2), dr2.stride(0)
-    if want_dx:
-        dx = torch.empty(rows, cols, device=xsum.device, dtype=x_dtype)
+    if dx is not None:
         P.dx, P.dx_row_stride = _lib.ptr(dx), dx.stride(0)
-    if want_dres:
-        dres = torch.empty(rows, cols, device=xsum.device, dtype=s2.dtype)
+    if dres is not None:
         P.dresidual, P.dres_row_stride = _lib.ptr(dres), dres.stride(0)
+    return P
+
+
+def norm_bwd(xsum, weight, dy, dresidual_out, eps, is_rms, *, x_dtype, want_dx=True, want_dres=False, has_bias=False):
+    """zigma_add_norm_bwd (reference _layer_norm_bwd, layernorm.py:275-377).  xsum: the normalised tensor (..., cols);
+    returns dx (x_dtype) | None, dresidual (xsum.dtype) | None, dweight f32 | None, dbias f32 | None."""
+    dev = _lib.require_device(xsum, weight, dy, dresidual_out)
+    shape = xsum.shape
+    s2, dy2 = _flat(xsum), _flat(dy)
+    if weight is not None:
+        weight = weight.contiguous()          # kept alive in this local until after the launch
+    dr2 = _flat(dresidual_out) if dresidual_out is not None else None
+    rows, cols = s2.shape
+    dw = torch.zeros(cols, device=xsum.device, dtype=torch.float32) if weight is not None else None
+    db = torch.zeros(cols, device=xsum.device, dtype=torch.float32) if has_bias else None
+    dx = torch.empty(rows, cols, device=xsum.device, dtype=x_dtype) if want_dx else None
+    dres = torch.empty(rows, cols, device=xsum.device, dtype=s2.dtype) if want_dres else None
+    P = norm_bwd_block(s2, weight, dy2, dr2, eps, is_rms, x_dtype=x_dtype, dx=dx, dres=dres, dw=dw, db=db)
     ws = _lib.workspace("zigma_add_norm_bwd", P, dev)
     _lib.call("zigma_add_norm_bwd", P, dev)
     del ws

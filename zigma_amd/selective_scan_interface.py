@@ -392,67 +392,23 @@ def dt_proj_softplus(x_dbl, dt_rank, weight, bias=None, softplus=True):
     return out.reshape(*lead, n)
 
 
-BWD_MAX_BATCH = 65535        # batch limit of one zigma_selective_scan_bwd / zigma_causal_conv1d_bwd launch (grid dimension)
-
-
-def scan_bwd_tok(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus, *, dB=None, dC=None, dz=None,
-                 z_row_index=None, out_row_index=None, checkpoints=None, reset_period=0):
-    """Backward of the token-major selective scan (zigma_selective_scan_bwd; reference selective_scan_cuda.bwd,
-    selective_scan.cpp:338-492).
-
-    u, delta, z, out, dout: (batch, seqlen, dim), channel stride 1; out = the forward's UNGATED y (only with z).
-    B, C: (batch, seqlen, dstate)-shaped views (any strides), same dtype.  A (dim, dstate) f32, D / delta_bias f32.
-    dB, dC: optional preallocated float32 (batch, seqlen, dstate) views to write into (e.g. columns of d(x_dbl)).
-    dz: optional preallocated (batch, seqlen, dim) view (e.g. the z half of d(xz)).
-    z_row_index / out_row_index: the forward's int32 row tables — z / dz live at row z_row_index[k], out / dout at row
-    out_row_index[k] of their tensors (token order) while u, delta, B, C, du, ddelta, dB, dC are in scan order.
-    Returns du, ddelta, dA, dB, dC, dD, dz, ddelta_bias (None where the input was None); du/ddelta/dz in the input dtype,
-    the rest float32."""
-    dev = _lib.require_device(u, delta, A, B, C, D, z, delta_bias, dout, out)
+def scan_bwd_block(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus, du, ddelta, dA, dB, dC, dD, dz, dbias, *, z_row_index=None,
+                   out_row_index=None, checkpoints=None, reset_period=0):
+    """The parameter block of zigma_selective_scan_bwd but for its workspace, from the operands and the outputs of scan_bwd_tok (checked here).  Reads
+    shapes, strides, dtypes and addresses only, so a description of a tensor that is yet to be allocated serves as well as the tensor."""
     Bsz, L, Dm = u.shape
     N = A.shape[1]
-    if Bsz > BWD_MAX_BATCH:
-        # the kernel rides the batch in a 16-bit grid dimension: larger batches (the differentiable video temporal path reshapes to
-        # batch * tokens-per-frame rows) go in slices; per-sample outputs land in views of one allocation, the parameter gradients
-        # (dA, dD, ddelta_bias) are summed over the slices
-        du, ddelta = torch.empty_like(u, memory_format=torch.contiguous_format), torch.empty_like(u, memory_format=torch.contiguous_format)
-        if z is not None and dz is None:
-            dz = torch.empty_like(u, memory_format=torch.contiguous_format)
-        f32 = dict(device=u.device, dtype=torch.float32)
-        dB = torch.empty(Bsz, L, N, **f32) if dB is None else dB
-        dC = torch.empty(Bsz, L, N, **f32) if dC is None else dC
-        dA = dD = dbias = None
-        sl = lambda t, a, b: None if t is None else t[a:b]
-        for a in range(0, Bsz, BWD_MAX_BATCH):
-            b = min(a + BWD_MAX_BATCH, Bsz)
-            r = scan_bwd_tok(u[a:b], delta[a:b], A, B[a:b], C[a:b], D, sl(z, a, b), delta_bias, dout[a:b], sl(out, a, b), delta_softplus,
-                             dB=dB[a:b], dC=dC[a:b], dz=sl(dz, a, b), z_row_index=z_row_index, out_row_index=out_row_index,
-                             checkpoints=None if checkpoints is None else checkpoints[a:b], reset_period=reset_period)
-            du[a:b].copy_(r[0]); ddelta[a:b].copy_(r[1])
-            dA = r[2] if dA is None else dA + r[2]
-            dD = r[5] if dD is None or r[5] is None else dD + r[5]
-            dbias = r[7] if dbias is None or r[7] is None else dbias + r[7]
-        return du, ddelta, dA, dB, dC, dD, dz, dbias
     for t, nm in ((u, "u"), (delta, "delta"), (z, "z"), (out, "out"), (dout, "dout")):
-        if t is not None and (t.shape != (Bsz, L, Dm) or t.stride(2) != 1 or t.dtype != u.dtype):
+        if t is not None and (tuple(t.shape) != (Bsz, L, Dm) or t.stride(2) != 1 or t.dtype != u.dtype):
             raise RuntimeError(f"{nm} must be (batch, seqlen, dim) with channel stride 1 and the dtype of u")
-    if B.shape != (Bsz, L, N) or C.shape != (Bsz, L, N) or B.dtype != u.dtype or C.dtype != u.dtype:
+    if tuple(B.shape) != (Bsz, L, N) or tuple(C.shape) != (Bsz, L, N) or B.dtype != u.dtype or C.dtype != u.dtype:
         raise RuntimeError("B, C must be (batch, seqlen, dstate) views in the dtype of u")
     if A.dtype != torch.float32:
         raise RuntimeError("A must be float32")
     if z is not None and out is None:
         raise RuntimeError("the gated backward needs the forward's ungated `out`")
-    du, ddelta = torch.empty_like(u, memory_format=torch.contiguous_format), torch.empty_like(u, memory_format=torch.contiguous_format)
-    if z is not None and dz is None:
-        dz = torch.empty_like(u, memory_format=torch.contiguous_format)
-    if dz is not None and (dz.shape != u.shape or dz.stride(2) != 1 or dz.dtype != u.dtype):
+    if dz is not None and (tuple(dz.shape) != tuple(u.shape) or dz.stride(2) != 1 or dz.dtype != u.dtype):
         raise RuntimeError("dz must be (batch, seqlen, dim) with channel stride 1 and the dtype of u")
-    f32 = dict(device=u.device, dtype=torch.float32)
-    dA = torch.zeros(Dm, N, **f32)
-    dB = torch.empty(Bsz, L, N, **f32) if dB is None else dB
-    dC = torch.empty(Bsz, L, N, **f32) if dC is None else dC
-    dD = torch.zeros(Dm, **f32) if D is not None else None
-    dbias = torch.zeros(Dm, **f32) if delta_bias is not None else None
     P = _lib.ScanBwdParams()
     P.batch, P.dim, P.seqlen, P.dstate = Bsz, Dm, L, N
     P.delta_softplus, P.io_dtype, P.flags = int(bool(delta_softplus)), _lib.dtype_id(u), 0
@@ -475,14 +431,56 @@ def scan_bwd_tok(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus,
     P.D, P.delta_bias, P.dA, P.dD, P.ddelta_bias = _lib.ptr(D), _lib.ptr(delta_bias), _lib.ptr(dA), _lib.ptr(dD), _lib.ptr(dbias)
     for name, tab in (("z_row_index", z_row_index), ("out_row_index", out_row_index)):
         if tab is not None:
-            if tab.dtype != torch.int32 or tab.shape != (L,) or not tab.is_contiguous():
+            if tab.dtype != torch.int32 or tuple(tab.shape) != (L,) or not tab.is_contiguous():
                 raise RuntimeError(f"{name} must be a contiguous int32 (seqlen,) table")
             setattr(P, name, _lib.ptr(tab))
     if checkpoints is not None:            # written by the forward kernel (scan_raw(..., checkpoints=)): skip phase 1
-        if checkpoints.dtype != torch.float32 or not checkpoints.is_contiguous() or \
-                checkpoints.numel() != Bsz * (Dm // 64) * ((L + 15) // 16) * N * 64:
+        shape = _lib.checkpoint_shape(Bsz, Dm, L, N)           # (None: the library refuses the shape itself)
+        if checkpoints.dtype != torch.float32 or not checkpoints.is_contiguous() or (shape and checkpoints.numel() != math.prod(shape)):
             raise RuntimeError("checkpoints: float32 [batch][dim/64][ceil(seqlen/16)][dstate][64]")
         P.checkpoints = _lib.ptr(checkpoints)
+    return P
+
+
+def scan_bwd_tok(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus, *, dB=None, dC=None, dz=None,
+                 z_row_index=None, out_row_index=None, checkpoints=None, reset_period=0):
+    """Backward of the token-major selective scan (zigma_selective_scan_bwd; reference selective_scan_cuda.bwd,
+    selective_scan.cpp:338-492).
+
+    u, delta, z, out, dout: (batch, seqlen, dim), channel stride 1; out = the forward's UNGATED y (only with z).
+    B, C: (batch, seqlen, dstate)-shaped views (any strides), same dtype.  A (dim, dstate) f32, D / delta_bias f32.
+    dB, dC: optional preallocated float32 (batch, seqlen, dstate) views to write into (e.g. columns of d(x_dbl)).
+    dz: optional preallocated (batch, seqlen, dim) view (e.g. the z half of d(xz)).
+    z_row_index / out_row_index: the forward's int32 row tables — z / dz live at row z_row_index[k], out / dout at row
+    out_row_index[k] of their tensors (token order) while u, delta, B, C, du, ddelta, dB, dC are in scan order.
+    Returns du, ddelta, dA, dB, dC, dD, dz, ddelta_bias (None where the input was None); du/ddelta/dz in the input dtype,
+    the rest float32."""
+    dev = _lib.require_device(u, delta, A, B, C, D, z, delta_bias, dout, out)
+    Bsz, L, Dm = u.shape
+    N = A.shape[1]
+    du, ddelta = torch.empty_like(u, memory_format=torch.contiguous_format), torch.empty_like(u, memory_format=torch.contiguous_format)
+    if z is not None and dz is None:
+        dz = torch.empty_like(u, memory_format=torch.contiguous_format)
+    f32 = dict(device=u.device, dtype=torch.float32)
+    dB = torch.empty(Bsz, L, N, **f32) if dB is None else dB
+    dC = torch.empty(Bsz, L, N, **f32) if dC is None else dC
+    if Bsz > _lib.GRID_DIM_MAX:
+        # larger batches (the differentiable video temporal path reshapes to batch * tokens-per-frame rows) go in slices
+        sl = lambda t, a, b: None if t is None else t[a:b]
+
+        def run(a, b):
+            r = scan_bwd_tok(u[a:b], delta[a:b], A, B[a:b], C[a:b], D, sl(z, a, b), delta_bias, dout[a:b], sl(out, a, b), delta_softplus,
+                             dB=dB[a:b], dC=dC[a:b], dz=sl(dz, a, b), z_row_index=z_row_index, out_row_index=out_row_index,
+                             checkpoints=sl(checkpoints, a, b), reset_period=reset_period)
+            du[a:b].copy_(r[0]); ddelta[a:b].copy_(r[1])
+            return r[2], r[5], r[7]
+        dA, dD, dbias = _lib.sum_over_batch_slices(Bsz, run)
+        return du, ddelta, dA, dB, dC, dD, dz, dbias
+    dA = torch.zeros(Dm, N, **f32)
+    dD = torch.zeros(Dm, **f32) if D is not None else None
+    dbias = torch.zeros(Dm, **f32) if delta_bias is not None else None
+    P = scan_bwd_block(u, delta, A, B, C, D, z, delta_bias, dout, out, delta_softplus, du, ddelta, dA, dB, dC, dD, dz, dbias,
+                       z_row_index=z_row_index, out_row_index=out_row_index, checkpoints=checkpoints, reset_period=reset_period)
     ws = _lib.workspace("zigma_selective_scan_bwd", P, dev)
     _lib.call("zigma_selective_scan_bwd", P, dev)
     del ws
@@ -499,7 +497,7 @@ def z_preactivated_eligible(batch, seqlen, d_state):
     (plan_scan() of csrc/scan_plan.h: tok2_layout_ok() without `out`, no batch slices).  Stated here and not asked of the library: the choice is made
     before in_proj runs, when xz — and with it every operand of the scan's block — does not exist yet, and it only gates an in_proj epilogue
     (a scan the plan then does not serve pre-activated is refused by the library, never computed wrongly)."""
-    return d_state == 16 and seqlen % 16 == 0 and batch <= 65535 and not torch.is_grad_enabled()
+    return d_state == 16 and seqlen % 16 == 0 and batch <= _lib.GRID_DIM_MAX and not torch.is_grad_enabled()
 
 
 InnerPlan = namedtuple("InnerPlan", "front dt chunk_len accumulate")
@@ -579,7 +577,8 @@ class MambaInnerTokFn(torch.autograd.Function):
         y = torch.empty(L, Bsz, Di, device=xz.device, dtype=xz.dtype).transpose(0, 1) if not xz.is_contiguous() else torch.empty_like(out)
         # the states before every 16-step tile, for the backward's reverse sweep (the token-major kernel writes them on
         # its way: 4 * Di * N * L / 16 bytes per sample; anything else leaves the buffer alone and the backward recomputes)
-        ck = torch.empty(Bsz, Di // 64, (L + 15) // 16, N, 64, device=xz.device, dtype=torch.float32) if Di % 64 == 0 and N in (8, 16) else None
+        ck_shape = _lib.checkpoint_shape(Bsz, Di, L, N)
+        ck = torch.empty(*ck_shape, device=xz.device, dtype=torch.float32) if ck_shape else None
         info = []
         scan_raw(u.transpose(1, 2), delta.transpose(1, 2), A, Bm.transpose(1, 2).unsqueeze(1),
                  Cm.transpose(1, 2).unsqueeze(1), D, xz[:, :, Di:].transpose(1, 2), delta_bias, True,
